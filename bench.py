@@ -2,7 +2,16 @@
 """Benchmark of the per-frame calibration hot path on MI355X (metric of BASELINE.json).
 
     python bench.py --gpus N --steps K --warmup W [--workload c3|c4] [--dtype fp16x3|bf16|fp32|fp8] [--size 540p|1080p]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, runs max(W, 1) warm-up steps, times K steps and prints one JSON line whose headline is `value` (frames/s over
+the K timed steps) and `ms_per_step`; its `config` holds only what costs no GPU work.  `--full` adds everything that needs runs or
+instrumentation of its own: the per-launch profile of the last warm-up step and the dominant kernel's events inside the timed
+region (`roofline`, `kernels`), the solve stage and per-batch solve times, steady state, drain and the no-solve comparison
+(`config.solver`), `parity`, the other engines, `lanes2`, `input_stage` and `cpu_baseline` (`--no-parity` / `--no-cpu-baseline`
+leave the last ones out).  `--dump-outputs DIR` saves what the last timed step returned -- keypoints.npy (B,57,3) float32 and
+cameras.npy (B,19) float64 -- so that two builds can be compared output for output: the inputs are seeded and identical run to run.
 
 One step = one pass of the hot path over one batch of frames already resident in HBM (BASELINE config C3: HRNet-W48,
 960x540, batch 64 per GPU): NCHW->NHWC, all convolutions / fuse / head kernels, log-softmax + keypoint decode, and the
@@ -31,9 +40,9 @@ line) and 39 642 of 39 642 on 2048 frames with 2045 of 2045 cameras identical (t
 is the 16-bit dense MFMA peak / 3 (three executed products per reference product); `roofline.frac_of_16bit_dense_peak` prices the
 same reference-formulation work against the undivided hardware peak.  The bf16 throughput engine (2.6x faster, 1-3 % of the usable
 keypoints move by one cell on this workload) and the exact-fp32 engine are timed on the same frames outside the timed region and
-ride on the line as `bf16` and `fp32`.
+ride on the --full line as `bf16` and `fp32`.
 
-Parity of the benchmarked path rides on the same line (`parity`, computed OUTSIDE the timed region on the same frames):
+Parity of the benchmarked path rides on the --full line (`parity`, computed OUTSIDE the timed region on the same frames):
 the benchmarked engine against this build's exact-fp32 engine (the one pinned to the reference goldens by
 tests/test_hrnet_gpu.py): keypoint-index agreement, and the relative difference of the solved cameras' reprojection
 error; plus the fp32 engine's own frames/s.  With N > 1 every rank processes its own 64 frames per step (weak scaling, frames
@@ -410,13 +419,15 @@ def self_launch(args):
         if n_dev < args.gpus:
             raise SystemExit(f'--gpus {args.gpus}: only {n_dev} GPU(s) visible; refusing to report a smaller job under that label')
     import socket
+    import subprocess
     with socket.socket() as s:
         s.bind(('127.0.0.1', 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={args.gpus}',
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.abspath(__file__), *sys.argv[1:]]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    # a fresh child process, not an exec: the device count above may already have initialised the GPU runtime in this one
+    raise SystemExit(subprocess.call(cmd))
 
 
 def dry_dist(rank, world):
@@ -449,6 +460,21 @@ def dry_dist(rank, world):
         dist.destroy_process_group()
 
 
+def dump_outputs(path, kp, rec, cc):
+    """--dump-outputs: what the timed path returned for the last step's frames (CalibrationPipeline.submit: keypoints and camera
+    records) -> keypoints.npy (B,57,3) float32 (x, y, confidence) and cameras.npy (B,19) float64: position (3), rotation (9, row
+    major), fx, fy, cx, cy, rmse, status, n_points; the 17 camera columns of a frame without a camera (status 0) are NaN."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'keypoints.npy'), kp.cpu().numpy().astype(np.float32))
+    recs = cc.records(rec)
+    cams = np.full((len(recs), 19), np.nan, dtype=np.float64)
+    for i, r in enumerate(recs):
+        cams[i, 17:] = (r.status, r.n_points)
+        if r.status != 0:
+            cams[i, :17] = [*r.position, *r.rotation, r.fx, r.fy, r.cx, r.cy, r.rmse]
+    np.save(os.path.join(path, 'cameras.npy'), cams)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -470,8 +496,14 @@ def main():
                     help='distinct batches of synthetic frames resident in HBM, cycled step by step (default: 4 at 540p, 1 at 1080p): the '
                          'steps then solve different keypoint sets -- the solve time and the cameras found are not one sample')
     ap.add_argument('--batch', type=int, default=BATCH)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-parity', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, measure what takes runs of its own: kernel profile and roofline, solve-stage and per-batch '
+                         'solve times, steady state and drain, the no-solve and 200-iteration comparisons, parity against the fp32 '
+                         'engine, the other engines, lanes2, the JPEG input stage and the CPU baseline (default: the headline only)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, save what the last step returned (keypoints.npy float32, cameras.npy float64) to DIR')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: leave out the CPU baseline')
+    ap.add_argument('--no-parity', action='store_true', help='--full: leave out parity and the other engines')
     ap.add_argument('--lanes', type=int, default=1,
                     help='split the batch into this many independent sub-batches on their own streams (default 1; see DESIGN.md §5: '
                          '2 lanes fill kernel tails and launch gaps, but per-kernel HIP-event durations then measure a shared GPU, '
@@ -565,7 +597,7 @@ def main():
         cur['n'] += 1
         cur['last'] = si
         xs = XS_sets[si]
-        if L == 1 and not diag_nosolve:
+        if args.full and L == 1 and not diag_nosolve:
             step_marks.append(torch.cuda.Event(enable_timing=True))
             step_marks[-1].record()
         # forward + decode on the main stream; the solve of THESE keypoints on the pipeline's side stream (it overlaps the
@@ -598,24 +630,26 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # warm-up: the last warm-up step is profiled launch by launch (kernel time shares, and which variant dominates); the
+    # warm-up: max(W, 1) steps.  --full profiles the last one launch by launch (kernel time shares, and which variant dominates); the
     # timed region then times only that variant's launches -- the per-dispatch events cost ~4 us each, and the roofline
-    # object needs the dominant kernel's duration, not those of the other ~150 launches of a step
+    # object needs the dominant kernel's duration, not those of the other ~150 launches of a step.  A plain run profiles nothing.
     for _ in range(max(args.warmup - 1, 0)):
         step()
     fence()
-    for n in nets:
-        n.set_profiling(1)
+    if args.full:
+        for n in nets:
+            n.set_profiling(1)
     step()
     fence()
     warm = {}
-    for n in nets:
-        for q in n.get_profile():
-            m = warm.setdefault(q['kernel'], dict(q, ms=0.0, launches=0, flops=0.0, bytes=0.0))
-            for k in ('ms', 'launches', 'flops', 'bytes'):
-                m[k] += q[k]
-    for n in nets:
-        n.set_profiling(0 if diag_noprof else 2)
+    if args.full:
+        for n in nets:
+            for q in n.get_profile():
+                m = warm.setdefault(q['kernel'], dict(q, ms=0.0, launches=0, flops=0.0, bytes=0.0))
+                for k in ('ms', 'launches', 'flops', 'bytes'):
+                    m[k] += q[k]
+        for n in nets:
+            n.set_profiling(0 if diag_noprof else 2)
     step_marks.clear()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -624,16 +658,20 @@ def main():
     dt = time.perf_counter() - t0
     # everything below describes the LAST step's batch of frames (its keypoints and records are what `last` holds)
     frames_cpu, x, expect, xs = F_sets[cur['last']], X_sets[cur['last']], E_sets[cur['last']], XS_sets[cur['last']]
+    if args.dump_outputs and rank == 0 and not diag_nosolve:
+        dump_outputs(args.dump_outputs, torch.cat([last[i][0] for i in range(L)], dim=0),
+                     torch.cat([last[i][1] for i in range(L)], dim=0), cc)
     # steady state: head of step 0's forward to head of the last step's forward; what is left of dt is the pipeline's drain -- the
     # solve of the LAST batch has nothing to overlap with inside a timed region that must end with every solve complete
     steady_ms = step_marks[0].elapsed_time(step_marks[-1]) / (len(step_marks) - 1) if len(step_marks) > 1 else None
     merged = {}
-    for n in nets:
-        for q in n.get_profile():
-            m = merged.setdefault(q['kernel'], dict(q, ms=0.0, launches=0, flops=0.0, bytes=0.0))
-            for k in ('ms', 'launches', 'flops', 'bytes'):
-                m[k] += q[k]
-        n.set_profiling(False)
+    if args.full:
+        for n in nets:
+            for q in n.get_profile():
+                m = merged.setdefault(q['kernel'], dict(q, ms=0.0, launches=0, flops=0.0, bytes=0.0))
+                for k in ('ms', 'launches', 'flops', 'bytes'):
+                    m[k] += q[k]
+            n.set_profiling(False)
     prof = list(merged.values())
     if args.dump_gather and use_dist and rank == 0:      # the path's one collective, as it closed the timed region: K steps' records at once
         from sncal_amd.dist import pack_records
@@ -642,22 +680,23 @@ def main():
     if diag:                                             # diagnosis runs print the step time only
         print('diag', diag, round(dt / args.steps * 1e3, 3), 'ms/step', 'steady', round(steady_ms, 3) if steady_ms else None)
         return
-    # solve-stage time on the decoded keypoints, measured separately after the timed region (torch events see torch's
-    # current stream, which is the stream libsncal launches on)
     kp_fast = torch.cat([last[i][0] for i in range(L)], dim=0)
     rec_fast = torch.cat([last[i][1] for i in range(L)], dim=0)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    rec_tmp = cc.solve_device(kp_fast)
-    ev[0].record()
-    for _ in range(3):
-        cc.solve_device(kp_fast, out=rec_tmp)
-    ev[1].record()
-    torch.cuda.synchronize()
-    solve_ms = ev[0].elapsed_time(ev[1]) / 3
+    # --full: solve-stage time on the decoded keypoints, measured separately after the timed region (torch events see torch's
+    # current stream, which is the stream libsncal launches on)
+    if args.full:
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        rec_tmp = cc.solve_device(kp_fast)
+        ev[0].record()
+        for _ in range(3):
+            cc.solve_device(kp_fast, out=rec_tmp)
+        ev[1].record()
+        torch.cuda.synchronize()
+        solve_ms = ev[0].elapsed_time(ev[1]) / 3
     # ... and of every batch of frames the steps cycled through (one forward + one synchronous solve each, outside the timed region): the
     # solve's latency is set by its slowest Levenberg-Marquardt fit, which differs from batch to batch
     by_set = None
-    if rank == 0 and L == 1 and n_sets > 1 and not c4:
+    if args.full and rank == 0 and L == 1 and n_sets > 1 and not c4:
         by_set = []
         for si in range(n_sets):
             _, kps = nets[0].forward(XS_sets[si][0], want_heat=False, decode_size=(540, 960))
@@ -667,9 +706,16 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             by_set.append({'solve_ms': round(e0.elapsed_time(e1), 1), 'cameras_found': sum(1 for r in cc.records(rs) if r.status != 0)})
-    # what the solves cost the step: the same K steps of network + decode alone (no solve, no gather), outside the timed region
+    # the solver's settings; --full adds what the solves cost the step: the same K steps of network + decode alone (no solve, no
+    # gather), outside the timed region
     solver_note = None
     if rank == 0 and L == 1 and not diag:
+        solver_note = {'refine_max_iters': REFINE_CAP if REFINE_CAP > 0 else 20000, 'refine_eps': 1e-5,
+                       'criterion': ('DIAGNOSIS: SNCAL_BENCH_REFINE_CAP set, not the reference criterion' if REFINE_CAP > 0 else
+                                     'the reference\'s own (baseline/camera.py:116 solvePnPRefineLM criteria (20000, 1e-5)) = library default'),
+                       'solve_streams': pipes[0].max_in_flight // 2, 'solve_streams_cu_masked': bool(pipes[0].masked),
+                       'solve_cus_per_xcd': sncal_amd.pipeline.SOLVE_CUS_PER_XCD if pipes[0].masked else None}
+    if args.full and solver_note is not None:
         for n in nets:
             n.set_profiling(0)
         torch.cuda.synchronize()
@@ -678,19 +724,14 @@ def main():
             nets[0].forward(xs[0], want_heat=False, decode_size=(540, 960))
         torch.cuda.synchronize()
         ns_ms = (time.perf_counter() - t1) / args.steps * 1e3
-        solver_note = {'refine_max_iters': REFINE_CAP if REFINE_CAP > 0 else 20000, 'refine_eps': 1e-5,
-                       'criterion': ('DIAGNOSIS: SNCAL_BENCH_REFINE_CAP set, not the reference criterion' if REFINE_CAP > 0 else
-                                     'the reference\'s own (baseline/camera.py:116 solvePnPRefineLM criteria (20000, 1e-5)) = library default'),
-                       'solve_streams': pipes[0].max_in_flight // 2, 'solve_streams_cu_masked': bool(pipes[0].masked),
-                       'solve_cus_per_xcd': sncal_amd.pipeline.SOLVE_CUS_PER_XCD if pipes[0].masked else None,
-                       'nosolve_ms_per_step': round(ns_ms, 3),
-                       'step_over_nosolve': round(dt / args.steps * 1e3 / ns_ms, 4),
-                       'steady_state_ms_per_step': round(steady_ms, 3) if steady_ms else None,
-                       'steady_state_over_nosolve': round(steady_ms / ns_ms, 4) if steady_ms else None,
-                       'drain_ms': round(dt * 1e3 - steady_ms * args.steps, 1) if steady_ms else None,
-                       'note': 'ms_per_step = (K steps + drain) / K: the timed region ends with every solve complete, so the last batch\'s solve '
-                               '(one crawling Levenberg-Marquardt fit of 20000 iterations sets its latency) is exposed once per run; '
-                               'steady_state = head of forward to head of forward inside the region'}
+        solver_note.update({'nosolve_ms_per_step': round(ns_ms, 3),
+                            'step_over_nosolve': round(dt / args.steps * 1e3 / ns_ms, 4),
+                            'steady_state_ms_per_step': round(steady_ms, 3) if steady_ms else None,
+                            'steady_state_over_nosolve': round(steady_ms / ns_ms, 4) if steady_ms else None,
+                            'drain_ms': round(dt * 1e3 - steady_ms * args.steps, 1) if steady_ms else None,
+                            'note': 'ms_per_step = (K steps + drain) / K: the timed region ends with every solve complete, so the last batch\'s solve '
+                                    '(one crawling Levenberg-Marquardt fit of 20000 iterations sets its latency) is exposed once per run; '
+                                    'steady_state = head of forward to head of forward inside the region'})
         if REFINE_CAP == 0:             # and what a 200-iteration cap (rounds 1-4) would change on these frames: solve time, cameras that move
             cc_cap = sncal_amd.CameraCreator(sncal_amd.PITCH_POINTS, **dict(SOLVER_KW, refine_max_iters=200))
             ev2 = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -718,20 +759,6 @@ def main():
     hit = float(near[vis & (kpf[..., 2] >= 0.2)].mean()) if (vis & (kpf[..., 2] >= 0.2)).any() else 0.0
 
     if rank == 0:
-        # focus mode: every net timed only the variant that led ITS profile; with several nets / lanes they may differ -- the line reports the largest
-        assert 1 <= len(prof) <= len(nets), [p['kernel'] for p in prof]
-        dom = max(prof, key=lambda q: q['ms'])
-        warm = list(warm.values())
-        total_ms = sum(p['ms'] for p in warm)
-        warm_dom = next(p for p in warm if p['kernel'] == dom['kernel'])
-        ach = dom['flops'] / (dom['ms'] * 1e-3) / 1e12
-        traffic = None      # HBM bytes per launch from a separate rocprofv3 --pmc pass (tools/pmc_pass.sh -> profiles/pmc_traffic.json)
-        try:
-            with open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')) as f:
-                traffic = json.load(f).get(dom['kernel']) if args.size == '540p' else None      # the PMC pass ran the 960x540 shapes
-        except OSError:
-            pass
-        peak = PEAK_TFLOPS['fp8' if 'fp8' in dom['kernel'] else 'bf16' if args.dtype == 'fp8' else args.dtype]
         flop_frame = (FLOP_KEYPOINT_NET if args.size == '540p' else FLOP_KEYPOINT_NET_1080P) + (FLOP_LINE_NET if c4 else 0)
         dtype_label = args.dtype + (f' (fp8 layers: {args.fp8_layers})' if args.dtype == 'fp8' else '')
         wl = (f'C5: HRNet-W48 1920x1080, batch {B} per GPU, {dtype_label}, heatmap 540x960 + decode + batched camera solve (iterative_voter)'
@@ -745,68 +772,93 @@ def main():
             'vs_baseline': None, 'dtype': args.dtype,
             'data': 'synthetic (noise frames stamped with per-keypoint codes at the pitch template\'s projections through sampled cameras; '
                     'random-init HRNet-W48 with the deep signal path of synth.deep_state_dict: the codes travel through every backbone tensor -> peaked heatmaps; see bench.py docstring)',
+            'full': args.full,
             'config': {'workload': wl, 'frames_per_gpu': B, 'lanes': L,
                        'parallelism': f'frames sharded over {world} GPU(s), records stay on the rank, ONE all_gather of all {args.steps} steps\' records closes the timed region' if world > 1 else 'single GPU',
-                       'solve_ms_per_batch': round(solve_ms, 3), 'cameras_found': f'{n_cam}/{B}', 'solver': solver_note,
-                       'frame_sets': {'n': n_sets, 'what': 'distinct batches of frames resident in HBM, cycled step by step; the parity / hit-rate / cameras_found fields describe the last step\'s batch',
-                                      'by_set': by_set},
+                       'cameras_found': f'{n_cam}/{B}', 'solver': solver_note,
+                       'frame_sets': {'n': n_sets, 'what': 'distinct batches of frames resident in HBM, cycled step by step; the parity / hit-rate / cameras_found fields describe the last step\'s batch'},
                        'decoded_within_8px_of_stamp': round(hit, 4), 'visible_keypoint_conf_median': round(float(np.median(conf_vis)), 4),
-                       'network_tflops_reference_formulation': round(world * B * args.steps / dt * flop_frame / 1e12, 1),
-                       'kernel_time_share_last_warmup_step': {p['kernel']: round(p['ms'] / total_ms, 4) for p in sorted(warm, key=lambda q: -q['ms'])[:8]}},
-            'roofline': {'bound': 'mfma', 'kernel': dom['kernel'], 'achieved': round(ach, 2), 'peak': peak, 'unit': 'TFLOP/s',
-                         'frac': round(ach / peak, 4),
-                         **({'frac_of_split_ceiling': round(ach / peak * SPLIT_PRODUCTS[args.dtype], 4),
-                             'split_note': 'fp16x3: three executed 16-bit products per reference product; frac = algorithmic FLOPs / undivided 16-bit dense peak, '
-                                           'frac_of_split_ceiling = the same / (peak / 3)'} if args.dtype in SPLIT_PRODUCTS and 'x3' in dom['kernel'] else {}),
-                         'traffic': traffic, 'launches': dom['launches'],
-                         'avg_launch_us': round(dom['ms'] * 1e3 / dom['launches'], 2),
-                         'flops_per_launch': round(dom['flops'] / dom['launches'], 0),
-                         'share_of_gpu_time': round(warm_dom['ms'] / total_ms, 4)},
+                       'network_tflops_reference_formulation': round(world * B * args.steps / dt * flop_frame / 1e12, 1)},
         }
-        # the next kernels of the step (last warm-up step, every launch timed): fraction of the roof that bounds each + PMC traffic ratio
-        kernels = {}
-        try:
-            with open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')) as f:
-                pmc = json.load(f) if args.size == '540p' else {}
-        except OSError:
-            pmc = {}
-        for p in sorted(warm, key=lambda q: -q['ms'])[:6]:
-            if not p['ms'] or not p['launches']:
-                continue
-            k = p['kernel']
-            tf = p['flops'] / (p['ms'] * 1e-3) / 1e12
-            gbs = p['bytes'] / (p['ms'] * 1e-3) / 1e9
-            row = {'share_of_gpu_time': round(p['ms'] / total_ms, 4), 'launches_per_step': p['launches'], 'avg_launch_us': round(p['ms'] * 1e3 / p['launches'], 1),
-                   'tflops': round(tf, 1), 'frac_mfma': round(tf / (PEAK_TFLOPS['fp8'] if 'fp8' in k else PEAK_TFLOPS['f32' if 'f32' in k else 'bf16']), 4),
-                   **({'frac_of_split_ceiling': round(tf / PEAK_TFLOPS['fp16x3'] * 3.0, 4)} if 'x3' in k else {}),
-                   'algorithmic_gb_s': round(gbs, 0), 'frac_hbm': round(gbs / 8000.0, 4)}
-            if k in pmc:
-                row['pmc_bytes_per_launch'] = pmc[k]
-                row['pmc_over_algorithmic'] = round(pmc[k] / (p['bytes'] / p['launches']), 3) if p['bytes'] else None
-                row['pmc_gb_s'] = round(pmc[k] / (p['ms'] * 1e-3 / p['launches']) / 1e9, 0)
-            kernels[k] = row
-        out['kernels'] = kernels
-        if world == 1 and not args.no_parity:
-            for n in nets[1:] + lnets:
-                n._ws = None
-            npar = B if args.size == '540p' else min(B, 16)
-            out['parity'], out['fp32'], other, out_other = parity_leg(sncal_amd, cfg_name, sd, x[:npar], cc, kp_fast[:npar], rec_fast[:npar], dev,
-                                                                   flop_frame=FLOP_KEYPOINT_NET if args.size == '540p' else FLOP_KEYPOINT_NET_1080P,
-                                                                   main_dtype=args.dtype, steps_fp32=args.steps if args.size == '540p' else None,
-                                                                   steps=args.steps if args.size == '540p' else 3)
-            out[other] = out_other
-            if args.size == '540p' and not c4 and L == 1 and args.dtype != 'fp8':
-                out['lanes2'] = lanes_leg(sncal_amd, cfg_name, sd, x, cc, dev, args.dtype, steps=args.steps)      # (the headline's step count: the same drain share)
-        if world == 1 and not args.no_parity and args.size == '540p' and not c4 and args.dtype != 'fp8':
-            try:
-                out['input_stage'] = input_stage_leg(sncal_amd, nets[0], cc, dev)
-            except Exception as e:                                   # (a box without the golden file: the line stays valid)
-                out['input_stage'] = {'error': f'{type(e).__name__}: {e}'}
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(sd, cfg_name, frames_cpu, kpf, nb=8 if args.size == '540p' else 2)
+        if args.full:
+            out.update(full_line(args, out['config'], prof, warm, nets, solve_ms, by_set))
+            full_legs(args, out, sncal_amd, cfg_name, sd, x, cc, kp_fast, rec_fast, kpf, frames_cpu, nets, lnets, world, B, L, c4, dev)
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()
+
+
+def full_line(args, config, prof, warm, nets, solve_ms, by_set):
+    """--full: the measured fields of the line beyond the headline -- solve stage, per-batch solves and kernel time shares (added to
+    `config` in place), and the returned {'roofline', 'kernels'}: the dominant kernel and the next kernels of the step."""
+    # focus mode: every net timed only the variant that led ITS profile; with several nets / lanes they may differ -- the line reports the largest
+    assert 1 <= len(prof) <= len(nets), [p['kernel'] for p in prof]
+    dom = max(prof, key=lambda q: q['ms'])
+    warm = list(warm.values())
+    total_ms = sum(p['ms'] for p in warm)
+    warm_dom = next(p for p in warm if p['kernel'] == dom['kernel'])
+    ach = dom['flops'] / (dom['ms'] * 1e-3) / 1e12
+    # HBM bytes per launch from a separate rocprofv3 --pmc pass (tools/pmc_pass.sh -> profiles/pmc_traffic.json); the PMC pass ran the
+    # 960x540 shapes
+    try:
+        with open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')) as f:
+            pmc = json.load(f) if args.size == '540p' else {}
+    except OSError:
+        pmc = {}
+    peak = PEAK_TFLOPS['fp8' if 'fp8' in dom['kernel'] else 'bf16' if args.dtype == 'fp8' else args.dtype]
+    config['solve_ms_per_batch'] = round(solve_ms, 3)
+    config['frame_sets']['by_set'] = by_set
+    config['kernel_time_share_last_warmup_step'] = {p['kernel']: round(p['ms'] / total_ms, 4) for p in sorted(warm, key=lambda q: -q['ms'])[:8]}
+    roofline = {'bound': 'mfma', 'kernel': dom['kernel'], 'achieved': round(ach, 2), 'peak': peak, 'unit': 'TFLOP/s',
+                'frac': round(ach / peak, 4),
+                **({'frac_of_split_ceiling': round(ach / peak * SPLIT_PRODUCTS[args.dtype], 4),
+                    'split_note': 'fp16x3: three executed 16-bit products per reference product; frac = algorithmic FLOPs / undivided 16-bit dense peak, '
+                                  'frac_of_split_ceiling = the same / (peak / 3)'} if args.dtype in SPLIT_PRODUCTS and 'x3' in dom['kernel'] else {}),
+                'traffic': pmc.get(dom['kernel']), 'launches': dom['launches'],
+                'avg_launch_us': round(dom['ms'] * 1e3 / dom['launches'], 2),
+                'flops_per_launch': round(dom['flops'] / dom['launches'], 0),
+                'share_of_gpu_time': round(warm_dom['ms'] / total_ms, 4)}
+    # the next kernels of the step (last warm-up step, every launch timed): fraction of the roof that bounds each + PMC traffic ratio
+    kernels = {}
+    for p in sorted(warm, key=lambda q: -q['ms'])[:6]:
+        if not p['ms'] or not p['launches']:
+            continue
+        k = p['kernel']
+        tf = p['flops'] / (p['ms'] * 1e-3) / 1e12
+        gbs = p['bytes'] / (p['ms'] * 1e-3) / 1e9
+        row = {'share_of_gpu_time': round(p['ms'] / total_ms, 4), 'launches_per_step': p['launches'], 'avg_launch_us': round(p['ms'] * 1e3 / p['launches'], 1),
+               'tflops': round(tf, 1), 'frac_mfma': round(tf / (PEAK_TFLOPS['fp8'] if 'fp8' in k else PEAK_TFLOPS['f32' if 'f32' in k else 'bf16']), 4),
+               **({'frac_of_split_ceiling': round(tf / PEAK_TFLOPS['fp16x3'] * 3.0, 4)} if 'x3' in k else {}),
+               'algorithmic_gb_s': round(gbs, 0), 'frac_hbm': round(gbs / 8000.0, 4)}
+        if k in pmc:
+            row['pmc_bytes_per_launch'] = pmc[k]
+            row['pmc_over_algorithmic'] = round(pmc[k] / (p['bytes'] / p['launches']), 3) if p['bytes'] else None
+            row['pmc_gb_s'] = round(pmc[k] / (p['ms'] * 1e-3 / p['launches']) / 1e9, 0)
+        kernels[k] = row
+    return {'roofline': roofline, 'kernels': kernels}
+
+
+def full_legs(args, out, sncal_amd, cfg_name, sd, x, cc, kp_fast, rec_fast, kpf, frames_cpu, nets, lnets, world, B, L, c4, dev):
+    """--full: the legs outside the timed region that run work of their own -- parity against the exact-fp32 engine and the other
+    engines, lanes2, the JPEG input stage and the CPU baseline -- added to `out`."""
+    if world == 1 and not args.no_parity:
+        for n in nets[1:] + lnets:
+            n._ws = None
+        npar = B if args.size == '540p' else min(B, 16)
+        out['parity'], out['fp32'], other, out_other = parity_leg(sncal_amd, cfg_name, sd, x[:npar], cc, kp_fast[:npar], rec_fast[:npar], dev,
+                                                               flop_frame=FLOP_KEYPOINT_NET if args.size == '540p' else FLOP_KEYPOINT_NET_1080P,
+                                                               main_dtype=args.dtype, steps_fp32=args.steps if args.size == '540p' else None,
+                                                               steps=args.steps if args.size == '540p' else 3)
+        out[other] = out_other
+        if args.size == '540p' and not c4 and L == 1 and args.dtype != 'fp8':
+            out['lanes2'] = lanes_leg(sncal_amd, cfg_name, sd, x, cc, dev, args.dtype, steps=args.steps)      # (the headline's step count: the same drain share)
+    if world == 1 and not args.no_parity and args.size == '540p' and not c4 and args.dtype != 'fp8':
+        try:
+            out['input_stage'] = input_stage_leg(sncal_amd, nets[0], cc, dev)
+        except Exception as e:                                   # (a box without the golden file: the line stays valid)
+            out['input_stage'] = {'error': f'{type(e).__name__}: {e}'}
+    if world == 1 and not args.no_cpu_baseline:
+        out['cpu_baseline'] = cpu_baseline(sd, cfg_name, frames_cpu, kpf, nb=8 if args.size == '540p' else 2)
 
 
 if __name__ == '__main__':

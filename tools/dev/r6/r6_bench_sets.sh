@@ -1,8 +1,8 @@
 #!/bin/bash
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6i; mkdir -p $O; cd $R
-python bench.py --steps 20 --warmup 5 > $O/bench_c3_sets4.json 2> $O/bench_c3_sets4.err; echo "rc=$?"
-python bench.py --steps 20 --warmup 5 --frame-sets 1 --no-cpu-baseline --no-parity > $O/bench_c3_sets1.json 2> $O/bench_c3_sets1.err; echo "rc=$?"
-python bench.py --workload c4 --steps 20 --warmup 5 --no-cpu-baseline --no-parity > $O/bench_c4_sets4.json 2> $O/bench_c4_sets4.err; echo "rc=$?"
+python bench.py --full --steps 20 --warmup 5 > $O/bench_c3_sets4.json 2> $O/bench_c3_sets4.err; echo "rc=$?"
+python bench.py --full --steps 20 --warmup 5 --frame-sets 1 --no-cpu-baseline --no-parity > $O/bench_c3_sets1.json 2> $O/bench_c3_sets1.err; echo "rc=$?"
+python bench.py --full --workload c4 --steps 20 --warmup 5 --no-cpu-baseline --no-parity > $O/bench_c4_sets4.json 2> $O/bench_c4_sets4.err; echo "rc=$?"
 timeout 600 python -m pytest tests/test_dist_gpu.py -x -q 2>&1 | tail -2
 for f in bench_c3_sets4 bench_c3_sets1 bench_c4_sets4; do python - $O/$f.json <<'PY'
 import json,sys

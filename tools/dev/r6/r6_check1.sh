@@ -3,10 +3,10 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6a; mkdir -p $O; cd $R
 timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc $?" >> $O/pytest.log
 tail -5 $O/pytest.log
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-parity > $O/c3_plain.json 2> $O/c3_plain.err
-SNCAL_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29511 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-parity > $O/c3_dist.json 2> $O/c3_dist.err
-python bench.py --workload c4 --steps 20 --warmup 5 --no-cpu-baseline --no-parity > $O/c4_plain.json 2> $O/c4_plain.err
-SNCAL_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29512 python bench.py --workload c4 --steps 20 --warmup 5 --no-cpu-baseline --no-parity > $O/c4_dist.json 2> $O/c4_dist.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity > $O/c3_plain.json 2> $O/c3_plain.err
+SNCAL_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29511 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity > $O/c3_dist.json 2> $O/c3_dist.err
+python bench.py --full --workload c4 --steps 20 --warmup 5 --no-cpu-baseline --no-parity > $O/c4_plain.json 2> $O/c4_plain.err
+SNCAL_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29512 python bench.py --full --workload c4 --steps 20 --warmup 5 --no-cpu-baseline --no-parity > $O/c4_dist.json 2> $O/c4_dist.err
 for f in c3_plain c3_dist c4_plain c4_dist; do python - $O/$f.json <<'PY'
 import json,sys
 try:

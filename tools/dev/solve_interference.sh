@@ -10,7 +10,7 @@ for mode in base nosolve old; do
   [ $mode = nosolve ] && env="SNCAL_BENCH_DIAG=nosolve"
   [ $mode = base ] && env="SNCAL_SOLVE_TASKS=1"
   [ $mode = old ] && env="SNCAL_SOLVE_TASKS=0"
-  env $env rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$mode -o trace -- python $R/bench.py --no-cpu-baseline --no-parity > $O/$mode.out 2> $O/$mode.err
+  env $env rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$mode -o trace -- python $R/bench.py --full --no-cpu-baseline --no-parity > $O/$mode.out 2> $O/$mode.err
   find $O/prof_$mode -name "*kernel_stats.csv" -exec cp {} $O/stats_$mode.csv \;
   find $O/prof_$mode -name "*kernel_trace.csv" -exec cp {} $O/trace_$mode.csv \;
   rm -rf $O/prof_$mode
