@@ -100,6 +100,43 @@ struct Tensor {
     size_t offset = 0, bytes = 0;
 };
 
+// ---- launch schedule: which kernel runs which ops, decided once per (layout, sub-batch size) -------------------------
+enum LaunchKind {
+    LK_INPUT,        // NCHW fp32 / HWC u8 frames -> NHWC
+    LK_CONV,         // one convolution on the generic kernel (conv.hpp)
+    LK_TT,           // one to three independent convolutions on the two-team kernel (conv_tt.hip)
+    LK_GROUP,        // two or three independent convolutions as one grouped launch of the generic kernel
+    LK_SHARED_S2,    // the chain-starting stride-2 convolutions of one input tensor as one launch (conv_shared_s2_kernel)
+    LK_BNECK_TAIL,   // layer1 block 0: downsample branch + conv3 (bneckx3.hip)
+    LK_BNECK_SEAM,   // layer1: conv3 of a Bottleneck + conv1 of the next (bneckx3.hip)
+    LK_BBLOCKX3,     // 48-channel BasicBlock in split arithmetic (bblockx3.hip)
+    LK_BBLOCK48,     // 48-channel BasicBlock, bf16 (bblock.hip)
+    LK_UPADD,        // upsample + add (ops.hip)
+    LK_HEAD,         // fused head (head.hip / head32.hip / headx3.hip)
+    LK_TAIL,         // softmax, or the part of the keypoint decode fused with it
+    LK_DECODE,       // keypoint decode (decode.hip)
+};
+enum DecodeAt { DEC_NONE, DEC_HEAD, DEC_TAIL };    // where the keypoint decode runs when a call wants keypoints only
+
+struct Member {                     // what the schedule resolved for one op a launch covers
+    const ConvVariant* v = nullptr; // generic kernel: variant, tile width factor, tiles, dynamic LDS bytes, LDS-transposed epilogue
+    int twf = 1, tiles_x = 0, tiles_y = 0;
+    size_t lds = 0;
+    bool epi_lds = false;
+    bool twin = false, f32 = true;  // the launch writes the output's split twin / the output itself
+};
+struct TTPlanDev { TTItem* items = nullptr; uint32_t* first = nullptr; int n_wgs = 0; int lazy = 0; int cfg = 0; };
+struct Prof { std::string kernel; double flops = 0, bytes = 0; };
+struct Launch {
+    LaunchKind kind = LK_CONV;
+    int op = 0, n = 1;              // covers the ops [op, op + n), all active
+    Member m[3];
+    bool split_in = false;          // LK_BBLOCKX3: the input's split twin is made in front of the launch
+    TTPlanDev plan;                 // LK_TT: work lists (cfg set by the schedule, uploaded by the first launch)
+    Prof prof, prof_kp;             // profile row; LK_TAIL: prof_kp when the call wants keypoints only
+};
+struct Schedule { int sb = 0; DecodeAt dec = DEC_NONE; std::vector<Launch> launches; };
+
 }  // namespace sncal
 
 using namespace sncal;
@@ -122,20 +159,16 @@ struct sncal_hrnet {
     bool fused_enabled = true, use_fused = false;
     // exact-fp32 engine: the head in its restructured form (per-source 1x1 products at native resolution, one bilinear sum) on the
     // generic fp32 kernels -- the 784 -> 784 product at 270x480 (31 % of the reference's MACs) shrinks ninefold
-    bool has_split = false;
-    bool split_enabled = getenv("SNCAL_SPLIT_HEAD") ? atoi(getenv("SNCAL_SPLIT_HEAD")) != 0 : true, use_split = false;
+    bool has_split = false, use_split = false;
     // wide 3x3 stride-1 convolutions (96 / 192 / 384 channels) on the two-team persistent kernel (conv_tt.hip), bf16 path
     bool use_conv_tt = getenv("SNCAL_CONV_TT") ? atoi(getenv("SNCAL_CONV_TT")) != 0 : true;
-    bool use_s2p = getenv("SNCAL_S2P") ? atoi(getenv("SNCAL_S2P")) != 0 : false;     // fp16x3: 3x3 stride-2 convolutions on the pipelined persistent kernel (conv_s2p.hip): bit-identical, measured slower -> off
-    struct TTPlanDev { sncal::TTItem* items = nullptr; uint32_t* first = nullptr; int n_wgs = 0; int lazy = 0; int cfg = 0; };
-    std::map<int, TTPlanDev> tt_plans;    // work lists per launch (key: index of its first op), rebuilt when the layout changes
-    int n_cus = 0;
+    std::vector<Schedule> schedules;      // per sub-batch size at the current layout (SB and the last sub-batch's), dropped with the layout
+    int n_cus = 0;                        // compute units of the device (queried at finalize)
     // C5: fp8 (OCP e4m3) arithmetic for the wide 3x3 stride-1 convolutions, everything else as the bf16 engine
     bool fp8 = false, fp8_calibrated = false, calibrating = false;
-    bool x3_res_twin = true;     // bf16x3 engine: residuals of the two-team convolutions from the split twin (SNCAL_X3_RES_TWIN=0: from fp32)
-    bool x3_producer_twins = !(getenv("SNCAL_X3_SPLIT_PASS") && atoi(getenv("SNCAL_X3_SPLIT_PASS")) != 0);   // bf16x3: twins from the producers' epilogues, not from split_f32_kernel
-    bool x3_generic = false;     // bf16x3 engine: generic convolutions on the x3_t variants (packed weights [4 hi | 4 lo] bf16 per k-group)
-    bool x3 = false;                          // SNCAL_BF16X3: the fp32 engine with split-bf16 arithmetic in the 3x3 stride-1 convolutions of stages 2-4
+    // SNCAL_BF16X3: the fp32 engine with split-bf16 arithmetic in the 3x3 stride-1 convolutions of stages 2-4 and in the generic
+    // convolutions (x3_t variants: packed weights [4 hi | 4 lo] per k-group); residuals of the two-team convolutions come from split twins
+    bool x3 = false;
     unsigned fp8_stages = 0;                  // bit s: stage s selected (0 = all stages)
     std::vector<int> fp8_widths;              // selected channel widths (empty = all)
     unsigned* d_amax = nullptr;               // calibration: per-tensor max |x| (float bit patterns)
@@ -144,7 +177,6 @@ struct sncal_hrnet {
     bool fuse_bblock = getenv("SNCAL_FUSE_BBLOCK") ? atoi(getenv("SNCAL_FUSE_BBLOCK")) != 0 : true;   // 48-channel BasicBlocks as one kernel (bblock.hip), bf16 path
     // split engines, layer1 (bneckx3.hip): bit 0 = conv3 of a Bottleneck + conv1 of the next as one pass, bit 1 = block 0's downsample branch inside its conv3
     int fuse_bneck = getenv("SNCAL_FUSE_BNECK") ? atoi(getenv("SNCAL_FUSE_BNECK")) : 3;
-    bool fuse_bbx3 = getenv("SNCAL_FUSE_BBX3") ? atoi(getenv("SNCAL_FUSE_BBX3")) != 0 : true;         // ... and in split arithmetic (bblockx3.hip), bf16x3 engine
     void *d_hw0 = nullptr, *d_hw1 = nullptr;
     void *d_hw0_32 = nullptr, *d_hw1_32 = nullptr;      // head32.hip packing (null when K1 is not a multiple of 16)
     void *d_hw0_32l = nullptr, *d_hw1_32l = nullptr;    // bf16x3 engine (headx3.hip): lo parts of the split weights; d_hw0_32 / d_hw1_32 then hold the hi parts
@@ -170,10 +202,8 @@ struct sncal_hrnet {
     std::vector<Interval> intervals;
     std::vector<hipEvent_t> event_pool;
     size_t events_used = 0;
-    std::string last_kernel;
-    double last_flops = 0, last_bytes = 0;
-    // work tickets of the persistent kernels that deal their work dynamically (bneckx3.hip, bblockx3.hip): 64 zeroed words, re-armed by the
-    // kernels themselves; launches of one network are ordered on its stream, so they share the words
+    // work tickets of the persistent kernels that deal their work dynamically (TICKET_*): zeroed words, re-armed by the kernels
+    // themselves; launches of one network are ordered on its stream, so they share the words
     unsigned* d_tickets = nullptr;
     // range flag of the split-fp16 engine (x3.hpp x3_report): [0] wavefronts that split a value beyond +-65504, [1] workgroups of the
     // layout kernel that met a NaN / infinite input value.  Sticky until sncal_hrnet_range_status(clear = 1); allocated at finalize
@@ -327,11 +357,10 @@ struct Builder {
     // can run them as ONE launch that fetches the input once (conv.hpp conv_shared_s2_kernel).  A list scheduler over the section's own data
     // dependences: ops go out in the reference's order as they become ready; a group goes out as a whole, when its last member is ready
     // (members never depend on each other: a chain's first convolution reads a module input, and its accumulate operand comes from chains
-    // of OTHER inputs).  Sums are accumulated in the reference's order: same bits.  SNCAL_SHARE_S2=0 keeps the reference's op order.
+    // of OTHER inputs).  Sums are accumulated in the reference's order: same bits.
     void schedule_fuse_section(size_t begin) {
-        static const bool off = getenv("SNCAL_SHARE_S2") && atoi(getenv("SNCAL_SHARE_S2")) == 0;
         const size_t n = net.ops.size() - begin;
-        if (off || n < 3) return;
+        if (n < 3) return;
         std::vector<Op> sec(net.ops.begin() + begin, net.ops.end());
         std::map<int, int> producer;                         // tensor -> op of the section that writes it
         for (size_t i = 0; i < n; ++i) if (sec[i].out >= 0) producer[sec[i].out] = (int)i;
@@ -584,25 +613,13 @@ void choose_packing(sncal_hrnet& net, ConvLayer& L) {
     const int ge = net.ge;
     const int cout_frags = (L.cout + 15) / 16;
     double best = -1;
-    static const int force_mi = getenv("SNCAL_FORCE_MI") ? atoi(getenv("SNCAL_FORCE_MI")) : 0;   // tuning aid
     for (int v = 0; v < net.nvariants; ++v) {
         const ConvVariant& V = net.variants[v];
         if (V.ks != L.k || V.stride != L.stride) continue;
-        if (force_mi && L.k == 3 && L.stride == 1 && V.mi != force_mi && cout_frags % force_mi == 0) continue;
-        { static const int force_mi_s2 = getenv("SNCAL_FORCE_MI_S2") ? atoi(getenv("SNCAL_FORCE_MI_S2")) : 0;
+        { static const int force_mi_s2 = getenv("SNCAL_FORCE_MI_S2") ? atoi(getenv("SNCAL_FORCE_MI_S2")) : 0;     // tuning aids
           if (force_mi_s2 && L.k == 3 && L.stride == 2 && L.cin_phys >= 48 && V.mi != force_mi_s2 && cout_frags % force_mi_s2 == 0) continue; }
         { static const int force_g_s2 = getenv("SNCAL_FORCE_G_S2") ? atoi(getenv("SNCAL_FORCE_G_S2")) : 0;
           if (force_g_s2 && L.k == 3 && L.stride == 2 && L.cin_phys >= 48 && V.g != force_g_s2) continue; }
-        { static const int force_g = getenv("SNCAL_FORCE_G") ? atoi(getenv("SNCAL_FORCE_G")) : 0;
-          if (force_g && L.k == 3 && L.stride == 1 && L.cin_phys >= 96 && V.g != force_g) continue;
-          static const int force_g48 = getenv("SNCAL_FORCE_G48") ? atoi(getenv("SNCAL_FORCE_G48")) : 0;
-          if (force_g48 && L.k == 3 && L.stride == 1 && L.cin_phys == 48 && L.cout == 48 && V.g != force_g48) continue; }
-        {   // tuning aid: SNCAL_FORCE_PACK="k,stride,cin,cout,mi,g" pins the packing of the layers of that shape (cout 0 = any)
-            static const char* fp = getenv("SNCAL_FORCE_PACK");
-            int fk, fs, fci, fco, fmi, fg;
-            if (fp && sscanf(fp, "%d,%d,%d,%d,%d,%d", &fk, &fs, &fci, &fco, &fmi, &fg) == 6 && L.k == fk && L.stride == fs && L.cin_phys == fci &&
-                (fco == 0 || L.cout == fco) && (V.mi != fmi || V.g != fg)) continue;
-        }
         const int chunks = (L.cin_phys + V.g * ge - 1) / (V.g * ge);
         const int nks = conv_nks(V.ks, V.g);
         const double k_eff = (double)(L.k * L.k * L.cin_phys / ge) / (double)(chunks * nks * 4);
@@ -653,7 +670,7 @@ int pack_layer(sncal_hrnet& net, ConvLayer& L) {
                             if (ci >= L.cin) continue;
                             const float v = L.w[(((size_t)co * L.cin + ci) * KS + tap / KS) * KS + tap % KS] * L.scale[co];
                             if (net.dtype == SNCAL_BF16) { const uint16_t b = f2bf(v); memcpy(dst + e * 2, &b, 2); }
-                            else if (net.x3_generic) {          // [4 hi | 4 lo]: hi = rne16(w), lo = rne16(w - hi) (x3.hpp)
+                            else if (net.x3) {                  // [4 hi | 4 lo]: hi = rne16(w), lo = rne16(w - hi) (x3.hpp)
                                 uint16_t h, l;
                                 x3_split_host(v, &h, &l);
                                 memcpy(dst + e * 2, &h, 2); memcpy(dst + 8 + e * 2, &l, 2);
@@ -692,8 +709,7 @@ bool x3_shape_ok(const sncal_hrnet& net, const ConvLayer& L) {
 int pack_layer_x3(sncal_hrnet& net, ConvLayer& L) {
     if (L.d_w_x3) { (void)hipFree(L.d_w_x3); L.d_w_x3 = nullptr; }
     if (!x3_shape_ok(net, L)) return SNCAL_OK;
-    static const bool blk64 = !(getenv("SNCAL_X3_BLK64") && atoi(getenv("SNCAL_X3_BLK64")) == 0);
-    L.x3_blk = (L.cout % TT_COUT == 0 || !blk64) ? TT_COUT : 64;       // 48 channels: one padded 64-channel block (25 % zero rows) instead of 96 (50 %)
+    L.x3_blk = L.cout % TT_COUT == 0 ? TT_COUT : 64;       // 48 channels: one padded 64-channel block (25 % zero rows) instead of 96 (50 %)
     const int MBk = L.x3_blk / 32;
     const int chunks = L.cin / 16, nblk = (L.cout + L.x3_blk - 1) / L.x3_blk;
     std::vector<uint16_t> host((size_t)nblk * chunks * 9 * 2 * MBk * 64 * 8, 0);
@@ -951,10 +967,17 @@ inline bool op_active(const sncal_hrnet& net, const Op& op) {
 
 bool tt_eligible(const sncal_hrnet& net, const Op& op, int sb);
 
+// the layout and the launch schedules built on it are void: the next forward lays out again
+void drop_layout(sncal_hrnet& net) {
+    for (Schedule& s : net.schedules)
+        for (Launch& e : s.launches) { if (e.plan.items) (void)hipFree(e.plan.items); if (e.plan.first) (void)hipFree(e.plan.first); }
+    net.schedules.clear();
+    net.lay_sb = -1;
+}
+
 int layout(sncal_hrnet& net, int sb, int H, int W) {
     if (net.lay_sb == sb && net.lay_h == H && net.lay_w == W) return SNCAL_OK;
-    for (auto& kv : net.tt_plans) { (void)hipFree(kv.second.items); (void)hipFree(kv.second.first); }
-    net.tt_plans.clear();
+    drop_layout(net);
     std::vector<Tensor>& T = net.tensors;
     {   // does the fused head apply?  (bf16 path; the direct tensor must already sit at head resolution)
         auto half = [](int v) { return (v + 2 - 3) / 2 + 1; };
@@ -968,7 +991,7 @@ int layout(sncal_hrnet& net, int sb, int H, int W) {
             const float sx2 = sw > 1 ? (float)(w2 - 1) / (float)(sw - 1) : 0.f, sx3 = sw > 1 ? (float)(w3 - 1) / (float)(sw - 1) : 0.f;
             net.use_fused = 2 * ((int)(sx2 * 31) + 3) <= 16 && 2 * ((int)(sx3 * 31) + 3) <= 16;
         }
-        net.use_split = !net.use_fused && net.split_enabled && net.has_split && net.dtype == SNCAL_F32 && dims_ok;
+        net.use_split = !net.use_fused && net.has_split && net.dtype == SNCAL_F32 && dims_ok;
     }
     for (const Op& op : net.ops) {
         if (!op_active(net, op)) continue;
@@ -1016,7 +1039,7 @@ int layout(sncal_hrnet& net, int sb, int H, int W) {
         if (op.out >= 0) { if (T[op.out].first < 0) T[op.out].first = (int)i; T[op.out].last = std::max(T[op.out].last, (int)i); }
     }
     for (Tensor& t : T) t.last_read = t.last;
-    {   // Two consecutive convolutions of which the second reads the first one's output may run as ONE kernel (forward_impl: the fused
+    {   // Two consecutive convolutions of which the second reads the first one's output may run as ONE kernel (build_schedule: the fused
         // BasicBlocks, layer1's Bottleneck seams conv3 + next conv1, block 0's downsample tail).  That kernel reads the FIRST op's inputs
         // while it already writes the SECOND op's output, so for every such pair -- a superset of what the executor really fuses: the
         // predicates there depend on packing and sizes -- the first op's inputs outlive the second op and the second op's output exists
@@ -1065,7 +1088,7 @@ int layout(sncal_hrnet& net, int sb, int H, int W) {
             auto bf = [&](int t) { if (t >= 0) net.need_bf16[t] = 1; };
             // bf16x3: the second convolution of a BasicBlock takes its residual from the block input's split twin (the first convolution
             // read it), so that inside a chain of blocks nobody needs -- and no epilogue writes -- the fp32 form
-            op.res_twin = net.x3_res_twin && op.type == OP_CONV && op.res >= 0 && net.layers[op.conv].x3_on && T[op.res].twin >= 0 && twin_used[op.res] &&
+            op.res_twin = op.type == OP_CONV && op.res >= 0 && net.layers[op.conv].x3_on && T[op.res].twin >= 0 && twin_used[op.res] &&
                           op.out_coff == 0 && T[op.out].C == net.layers[op.conv].cout && T[op.res].C == net.layers[op.conv].cout;
             if (!op.res_twin) bf(op.res);
             bf(op.base); bf(op.dims_from); bf(op.head_direct);
@@ -1125,108 +1148,9 @@ int layout(sncal_hrnet& net, int sb, int H, int W) {
     return SNCAL_OK;
 }
 
-// parameters, kernel variant and dynamic LDS size of one convolution op (no launch)
-int prepare_conv(sncal_hrnet& net, const Op& op, int sb, char* ws, ConvParams& p, const ConvVariant*& bestv, size_t& best_lds) {
-    const ConvLayer& L = net.layers[op.conv];
-    const Tensor& ti = net.tensors[op.in];
-    const Tensor& to = net.tensors[op.out];
-    memset(&p, 0, sizeof(p));
-    p.range = net.d_range;
-    p.in = ws + ti.offset; p.out = ws + to.offset;
-    p.res = op.res >= 0 ? ws + net.tensors[op.res].offset : nullptr;
-    p.w = L.d_w; p.bias = L.d_bias;
-    p.N = sb; p.Hin = ti.H; p.Win = ti.W; p.Cin = ti.C;
-    p.Hout = to.H; p.Wout = to.W; p.cout_frags = L.cout_frags; p.cout = L.cout;
-    p.out_cstride = to.C; p.out_coff = op.out_coff;
-    p.cin_chunks = L.chunks; p.relu = op.relu ? 1 : 0; p.out_f32 = op.out_f32 ? 1 : 0;
-    // one IMAGE of the input / output tensor is a buffer-descriptor range in the kernel (int byte counts, out-of-range sentinel 0x80000000)
-    if ((size_t)ti.H * ti.W * ti.C * 4 >= (1u << 31) || (size_t)to.H * to.W * to.C * 4 >= (1u << 31)) {
-        set_error("conv %s: one image of a tensor reaches 2 GB (%dx%dx%d -> %dx%dx%d): unsupported", L.name.c_str(), ti.H, ti.W, ti.C, to.H, to.W, to.C);
-        return SNCAL_ERR_UNSUPPORTED;
-    }
-    // pick NI / tile shape / sub-tiles per weight chunk for this spatial size
-    bestv = nullptr;
-    best_lds = 0;
-    int best_twf = 1; double best_score = -1;
-    static const int force_ni = getenv("SNCAL_FORCE_NI") ? atoi(getenv("SNCAL_FORCE_NI")) : 0;   // tuning aids
-    static const double three_gain = getenv("SNCAL_THREE_GAIN") ? atof(getenv("SNCAL_THREE_GAIN")) : 1.15;
-    bool has_forced = false;
-    for (int v = 0; v < net.nvariants; ++v) {
-        const ConvVariant& V = net.variants[v];
-        if (V.ks == L.k && V.stride == L.stride && V.mi == L.mi && V.g == L.g && V.ni == force_ni) has_forced = true;
-    }
-    for (int v = 0; v < net.nvariants; ++v) {
-        const ConvVariant& V = net.variants[v];
-        if (V.ks != L.k || V.stride != L.stride || V.mi != L.mi || V.g != L.g) continue;
-        if (force_ni && has_forced && L.k == 3 && L.stride == 1 && V.ni != force_ni) continue;
-        const int F = 4 * V.ni;
-        const size_t wchunk = (size_t)conv_nks(V.ks, V.g) * V.mi * 1024;
-        static const int force_twf = getenv("SNCAL_FORCE_TWF") ? atoi(getenv("SNCAL_FORCE_TWF")) : 0;   // tuning aid
-        for (int twf = 1; twf <= F; twf *= 2) {
-            if (F % twf) continue;
-            if (force_twf && L.k == 3 && L.stride == 1 && L.cin >= 96 && twf != force_twf) continue;
-            const int th = F / twf;
-            const size_t lds = conv_stage_bytes(V.ks, V.stride, V.ni, V.mi, V.g, twf);
-            if (lds > 160 * 1024 || lds - wchunk > 64 * 1024) continue;   // halo tiles are capped at 64 DMA pieces
-            const long ty = (to.H + th - 1) / th, tx = (to.W + 16 * twf - 1) / (16 * twf);
-            const double eff = (double)to.H * to.W / ((double)ty * th * tx * 16 * twf);
-            const long blocks = ty * tx * sb * L.nblk;
-            const int per_cu = (int)std::min<size_t>(conv_resident_wgs(V.ks, V.ni, V.mi, V.g), (160 * 1024) / lds);
-            const double fill = std::min(1.0, (double)blocks / (256.0 * per_cu));
-            const double reuse = (double)(V.mi * V.ni) / (V.mi + V.ni);       // MFMAs per LDS fragment read
-            // exposed staging latency is hidden by co-resident workgroups only (see conv.hpp)
-            const double overlap = per_cu >= 3 ? three_gain : per_cu >= 2 ? 1.0 : 0.55;
-            const double score = eff * (0.3 + 0.7 * fill) * std::pow(reuse, 0.6) * overlap;
-            if (score > best_score + 1e-9) { best_score = score; bestv = &V; best_twf = twf; best_lds = lds; }
-        }
-    }
-    if (!bestv) { set_error("no conv variant for %s (k=%d s=%d mi=%d g=%d)", L.name.c_str(), L.k, L.stride, L.mi, L.g); return SNCAL_ERR_STATE; }
-    const int th = 4 * bestv->ni / best_twf;
-    p.twf = best_twf;
-    p.twf_log2 = 0;
-    while ((1 << p.twf_log2) < best_twf) ++p.twf_log2;
-    p.halo_w_magic = 0xFFFFFFFFu / (unsigned)((16 * best_twf - 1) * L.stride + L.k) + 1u;
-    p.tiles_x = (to.W + 16 * best_twf - 1) / (16 * best_twf);
-    p.tiles_y = (to.H + th - 1) / th;
-    {   // LDS-transposed epilogue: the fp32 tile of the 4 waves is staged in the (grown, if that keeps two
-        // workgroups per CU) dynamic LDS; needs whole 8-channel groups
-        static const int epi = getenv("SNCAL_EPI_LDS") ? atoi(getenv("SNCAL_EPI_LDS")) : 1;
-        const int wgs = conv_resident_wgs(L.k, bestv->ni, L.mi, L.g);
-        const size_t need = (size_t)4 * conv_epi_frags(L.k, bestv->ni, L.mi, L.g) * 16 * (L.mi * 16 + 4) * 4;
-        // bf16: whole 8-channel groups; fp32 / bf16x3 engines (epilogue F): whole 4-channel groups (SNCAL_EPI_F32=0: the direct epilogue)
-        static const int epi32 = getenv("SNCAL_EPI_F32") ? atoi(getenv("SNCAL_EPI_F32")) : 1;
-        const bool shape_ok = net.dtype == SNCAL_BF16 ? (!op.out_f32 && L.cout % 8 == 0 && to.C % 8 == 0 && op.out_coff % 8 == 0)
-                                                     : (epi32 && L.cout % 4 == 0 && to.C % 4 == 0 && op.out_coff % 4 == 0);
-        const size_t now_per_cu = std::min<size_t>(wgs, (160 * 1024) / best_lds);
-        const bool fits = need <= best_lds || need <= (160 * 1024) / now_per_cu || need <= 52 * 1024;
-        p.epi_lds = (epi && shape_ok && fits) ? 1 : 0;
-        if (p.epi_lds && need > best_lds) best_lds = need;
-    }
-    { static const int abl = getenv("SNCAL_ABLATE") ? atoi(getenv("SNCAL_ABLATE")) : 0; p.ablate = abl; }
-    p.w_bytes = (unsigned)((size_t)L.nblk * L.chunks * conv_nks(L.k, L.g) * L.mi * 1024);
-    { static const int extra = getenv("SNCAL_EXTRA_LDS") ? atoi(getenv("SNCAL_EXTRA_LDS")) : 0; best_lds = std::min<size_t>(best_lds + extra, 160 * 1024); }
-    { static const bool dbg = getenv("SNCAL_CONV_DEBUG") != nullptr;
-      if (dbg) fprintf(stderr, "[conv] %-44s %dx%d cin %d cout %d: NI%d MI%d G%d twf %d lds %zu grid %dx%d epi_lds %d\n", L.name.c_str(), to.H, to.W, L.cin, L.cout,
-                       bestv->ni, L.mi, L.g, best_twf, best_lds, p.tiles_x * p.tiles_y * sb, L.nblk, p.epi_lds); }
-    p.nblk = L.nblk;
-    p.n_work = (unsigned)(p.tiles_x * p.tiles_y * sb * L.nblk);
-    p.per_xcd = (p.n_work + 7) / 8;
-    p.nblk_magic = conv_magic((unsigned)L.nblk); p.tiles_x_magic = conv_magic((unsigned)p.tiles_x); p.tiles_y_magic = conv_magic((unsigned)p.tiles_y);
-    return SNCAL_OK;
-}
-
-void conv_profile_entry(sncal_hrnet& net, const Op& op, int sb, const ConvVariant* bestv, bool add) {
-    const ConvLayer& L = net.layers[op.conv];
-    const Tensor& ti = net.tensors[op.in];
-    const Tensor& to = net.tensors[op.out];
-    net.last_kernel = fmt("conv<%s,k%d,s%d,NI%d,MI%d,G%d>", net.dtype == SNCAL_BF16 ? "bf16" : net.x3_generic ? SNCAL_X3_NAME : "f32", L.k, L.stride, bestv ? bestv->ni : 0, L.mi, L.g);
-    static const bool detail = getenv("SNCAL_PROFILE_DETAIL") != nullptr;      // tuning aid: one profile row per layer shape
-    if (detail) net.last_kernel += fmt("@%dx%d:%d->%d%s", to.H, to.W, L.cin, L.cout, op.res >= 0 ? "+res" : "");
-    const double px = (double)sb * to.H * to.W;
-    if (!add) { net.last_flops = 0; net.last_bytes = 0; }
-    net.last_flops += 2.0 * px * L.cout * L.cin * L.k * L.k;
-    net.last_bytes += (double)sb * ti.H * ti.W * ti.C * net.esize + px * L.cout * (op.out_f32 ? 4 : net.esize) * (op.res >= 0 ? 2 : 1) +
-                      (double)L.cout * L.cin * L.k * L.k * net.esize;
+bool profile_detail() {          // tuning aid: one profile row per layer shape / two-team launch kind
+    static const bool detail = getenv("SNCAL_PROFILE_DETAIL") != nullptr;
+    return detail;
 }
 
 // ---- two-team persistent kernel for the wide 3x3 stride-1 convolutions (conv_tt.hip) --------------------------------
@@ -1251,42 +1175,162 @@ bool tt_eligible(const sncal_hrnet& net, const Op& op, int sb) {
     return in_bytes < (1u << 31) && out_elems < (1ull << 32) && (size_t)L.nblk * L.chunks * 9 * 6 * 1024 < (1u << 31);
 }
 
-// does the active op that produced tensor t write its e4m3 twin itself (an fp8 convolution on the two-team kernel)?
+// does the active op that produced tensor t write its e4m3 / split twin itself?
 bool twin_written_by_producer(const sncal_hrnet& net, int t, int sb) {
-    static const bool no_twin_out = getenv("SNCAL_FP8_NO_TWIN_OUT") != nullptr;      // debugging aid: every twin through the quantise kernel
-    if (no_twin_out) return false;
     const int pi = t >= 0 && t < (int)net.producer.size() ? net.producer[t] : -1;
     if (pi < 0) return false;
     const Op& po = net.ops[pi];
-    if (po.type == OP_CONV && net.layers[po.conv].x3_on && tt_eligible(net, po, sb)) {        // bf16x3: the producer's epilogue writes the split twin
-        static const bool x3_split_always = getenv("SNCAL_X3_NO_TWIN_OUT") != nullptr;            // (dense outputs only)
-        return !x3_split_always && po.out_coff == 0 && net.tensors[po.out].C == net.layers[po.conv].cout;
-    }
-    if (net.x3 && net.x3_producer_twins && net.dtype == SNCAL_F32) {
+    if (po.type == OP_CONV && net.layers[po.conv].x3_on && tt_eligible(net, po, sb))        // bf16x3: the producer's epilogue writes the split twin
+        return po.out_coff == 0 && net.tensors[po.out].C == net.layers[po.conv].cout;     // (dense outputs only)
+    if (net.x3 && net.dtype == SNCAL_F32) {
         // bf16x3: the generic split-arithmetic convolution and the fp32 fuse sum write the twin of a dense output in their epilogues
-        if (po.type == OP_CONV && net.x3_generic && !net.layers[po.conv].x3_on && po.out_coff == 0 && !po.out_f32 &&
+        if (po.type == OP_CONV && !net.layers[po.conv].x3_on && po.out_coff == 0 && !po.out_f32 &&
             net.tensors[po.out].C == net.layers[po.conv].cout && net.layers[po.conv].cout % 16 == 0) return true;
         if (po.type == OP_UPADD && po.out_coff == 0 && net.tensors[po.out].C % 16 == 0) return true;
     }
     return po.type == OP_CONV && net.layers[po.conv].fp8_on && tt_eligible(net, po, sb);
 }
 
-// bf16x3: the split twin a generic producer (convolution / fuse sum) writes for tensor t, or null; *skip_f32 = nobody reads the fp32 form
-void* producer_twin(const sncal_hrnet& net, int t, int sb, char* ws, bool* skip_f32) {
-    *skip_f32 = false;
-    if (!net.x3 || t < 0) return nullptr;
+// bf16x3: does a generic producer (convolution / fuse sum) write the split twin of tensor t?
+bool writes_twin(const sncal_hrnet& net, int t, int sb) {
+    if (!net.x3 || t < 0) return false;
     const Tensor& to = net.tensors[t];
-    if (to.twin < 0 || net.tensors[to.twin].first < 0 || !twin_written_by_producer(net, t, sb)) return nullptr;
-    *skip_f32 = !net.need_bf16[t];
-    return ws + net.tensors[to.twin].offset;
+    return to.twin >= 0 && net.tensors[to.twin].first >= 0 && twin_written_by_producer(net, t, sb);
+}
+
+// the generic kernel's variant, tile shape and dynamic LDS size for one convolution op at this layout (no launch)
+int choose_conv(const sncal_hrnet& net, const Op& op, int sb, Member& m) {
+    const ConvLayer& L = net.layers[op.conv];
+    const Tensor& ti = net.tensors[op.in];
+    const Tensor& to = net.tensors[op.out];
+    // one IMAGE of the input / output tensor is a buffer-descriptor range in the kernel (int byte counts, out-of-range sentinel 0x80000000)
+    if ((size_t)ti.H * ti.W * ti.C * 4 >= (1u << 31) || (size_t)to.H * to.W * to.C * 4 >= (1u << 31)) {
+        set_error("conv %s: one image of a tensor reaches 2 GB (%dx%dx%d -> %dx%dx%d): unsupported", L.name.c_str(), ti.H, ti.W, ti.C, to.H, to.W, to.C);
+        return SNCAL_ERR_UNSUPPORTED;
+    }
+    // pick NI / tile shape / sub-tiles per weight chunk for this spatial size
+    m.v = nullptr;
+    m.lds = 0;
+    m.twf = 1;
+    double best_score = -1;
+    static const double three_gain = getenv("SNCAL_THREE_GAIN") ? atof(getenv("SNCAL_THREE_GAIN")) : 1.15;     // tuning aid
+    for (int v = 0; v < net.nvariants; ++v) {
+        const ConvVariant& V = net.variants[v];
+        if (V.ks != L.k || V.stride != L.stride || V.mi != L.mi || V.g != L.g) continue;
+        const int F = 4 * V.ni;
+        const size_t wchunk = (size_t)conv_nks(V.ks, V.g) * V.mi * 1024;
+        for (int twf = 1; twf <= F; twf *= 2) {
+            if (F % twf) continue;
+            const int th = F / twf;
+            const size_t lds = conv_stage_bytes(V.ks, V.stride, V.ni, V.mi, V.g, twf);
+            if (lds > 160 * 1024 || lds - wchunk > 64 * 1024) continue;   // halo tiles are capped at 64 DMA pieces
+            const long ty = (to.H + th - 1) / th, tx = (to.W + 16 * twf - 1) / (16 * twf);
+            const double eff = (double)to.H * to.W / ((double)ty * th * tx * 16 * twf);
+            const long blocks = ty * tx * sb * L.nblk;
+            const int per_cu = (int)std::min<size_t>(conv_resident_wgs(V.ks, V.ni, V.mi, V.g), (160 * 1024) / lds);
+            const double fill = std::min(1.0, (double)blocks / (256.0 * per_cu));
+            const double reuse = (double)(V.mi * V.ni) / (V.mi + V.ni);       // MFMAs per LDS fragment read
+            // exposed staging latency is hidden by co-resident workgroups only (see conv.hpp)
+            const double overlap = per_cu >= 3 ? three_gain : per_cu >= 2 ? 1.0 : 0.55;
+            const double score = eff * (0.3 + 0.7 * fill) * std::pow(reuse, 0.6) * overlap;
+            if (score > best_score + 1e-9) { best_score = score; m.v = &V; m.twf = twf; m.lds = lds; }
+        }
+    }
+    if (!m.v) { set_error("no conv variant for %s (k=%d s=%d mi=%d g=%d)", L.name.c_str(), L.k, L.stride, L.mi, L.g); return SNCAL_ERR_STATE; }
+    const int th = 4 * m.v->ni / m.twf;
+    m.tiles_x = (to.W + 16 * m.twf - 1) / (16 * m.twf);
+    m.tiles_y = (to.H + th - 1) / th;
+    {   // LDS-transposed epilogue: the fp32 tile of the 4 waves is staged in the (grown, if that keeps two
+        // workgroups per CU) dynamic LDS; bf16: whole 8-channel groups, fp32 / bf16x3 engines (epilogue F): whole 4-channel groups
+        const int wgs = conv_resident_wgs(L.k, m.v->ni, L.mi, L.g);
+        const size_t need = (size_t)4 * conv_epi_frags(L.k, m.v->ni, L.mi, L.g) * 16 * (L.mi * 16 + 4) * 4;
+        const bool shape_ok = net.dtype == SNCAL_BF16 ? (!op.out_f32 && L.cout % 8 == 0 && to.C % 8 == 0 && op.out_coff % 8 == 0)
+                                                     : (L.cout % 4 == 0 && to.C % 4 == 0 && op.out_coff % 4 == 0);
+        const size_t now_per_cu = std::min<size_t>(wgs, (160 * 1024) / m.lds);
+        const bool fits = need <= m.lds || need <= (160 * 1024) / now_per_cu || need <= 52 * 1024;
+        m.epi_lds = shape_ok && fits;
+        if (m.epi_lds && need > m.lds) m.lds = need;
+    }
+    if (net.x3) {            // bf16x3: the split twin for the two-team convolution that reads this output; fp32 only if somebody reads it
+        m.twin = writes_twin(net, op.out, sb);
+        m.f32 = !m.twin || net.need_bf16[op.out];
+    }
+    return SNCAL_OK;
+}
+
+// parameters of one convolution op on the generic kernel
+void conv_params(const sncal_hrnet& net, const Op& op, int sb, char* ws, const Member& m, ConvParams& p) {
+    const ConvLayer& L = net.layers[op.conv];
+    const Tensor& ti = net.tensors[op.in];
+    const Tensor& to = net.tensors[op.out];
+    memset(&p, 0, sizeof(p));
+    p.range = net.d_range;
+    p.in = ws + ti.offset;
+    p.out = m.f32 ? ws + to.offset : nullptr;
+    p.out_twin = m.twin ? ws + net.tensors[to.twin].offset : nullptr;
+    p.res = op.res >= 0 ? ws + net.tensors[op.res].offset : nullptr;
+    p.w = L.d_w; p.bias = L.d_bias;
+    p.N = sb; p.Hin = ti.H; p.Win = ti.W; p.Cin = ti.C;
+    p.Hout = to.H; p.Wout = to.W; p.cout_frags = L.cout_frags; p.cout = L.cout;
+    p.out_cstride = to.C; p.out_coff = op.out_coff;
+    p.cin_chunks = L.chunks; p.relu = op.relu ? 1 : 0; p.out_f32 = op.out_f32 ? 1 : 0;
+    p.twf = m.twf;
+    p.twf_log2 = 0;
+    while ((1 << p.twf_log2) < m.twf) ++p.twf_log2;
+    p.halo_w_magic = 0xFFFFFFFFu / (unsigned)((16 * m.twf - 1) * L.stride + L.k) + 1u;
+    p.tiles_x = m.tiles_x; p.tiles_y = m.tiles_y;
+    p.epi_lds = m.epi_lds ? 1 : 0;
+    { static const int abl = getenv("SNCAL_ABLATE") ? atoi(getenv("SNCAL_ABLATE")) : 0; p.ablate = abl; }
+    p.w_bytes = (unsigned)((size_t)L.nblk * L.chunks * conv_nks(L.k, L.g) * L.mi * 1024);
+    p.nblk = L.nblk;
+    p.n_work = (unsigned)(p.tiles_x * p.tiles_y * sb * L.nblk);
+    p.per_xcd = (p.n_work + 7) / 8;
+    p.nblk_magic = conv_magic((unsigned)L.nblk); p.tiles_x_magic = conv_magic((unsigned)p.tiles_x); p.tiles_y_magic = conv_magic((unsigned)p.tiles_y);
+}
+
+// profile row of one convolution op (a launch of several members sums them; the last one names the row)
+Prof conv_prof(const sncal_hrnet& net, const Op& op, int sb, const ConvVariant* v) {
+    const ConvLayer& L = net.layers[op.conv];
+    const Tensor& ti = net.tensors[op.in];
+    const Tensor& to = net.tensors[op.out];
+    Prof r;
+    r.kernel = fmt("conv<%s,k%d,s%d,NI%d,MI%d,G%d>", net.dtype == SNCAL_BF16 ? "bf16" : net.x3 ? SNCAL_X3_NAME : "f32", L.k, L.stride, v ? v->ni : 0, L.mi, L.g);
+    if (profile_detail()) r.kernel += fmt("@%dx%d:%d->%d%s", to.H, to.W, L.cin, L.cout, op.res >= 0 ? "+res" : "");
+    const double px = (double)sb * to.H * to.W;
+    r.flops = 2.0 * px * L.cout * L.cin * L.k * L.k;
+    r.bytes = (double)sb * ti.H * ti.W * ti.C * net.esize + px * L.cout * (op.out_f32 ? 4 : net.esize) * (op.res >= 0 ? 2 : 1) +
+              (double)L.cout * L.cin * L.k * L.k * net.esize;
+    return r;
+}
+
+void add_prof(Prof& sum, const Prof& member) { sum.kernel = member.kernel; sum.flops += member.flops; sum.bytes += member.bytes; }
+
+// which outputs a two-team member writes: the fp32 / bf16 tensor, its twin
+void tt_outputs(const sncal_hrnet& net, const Op& op, int sb, bool* out, bool* twin) {
+    const ConvLayer& L = net.layers[op.conv];
+    const Tensor& to = net.tensors[op.out];
+    const bool alive = to.twin >= 0 && net.tensors[to.twin].first >= 0;
+    *out = true;
+    *twin = false;
+    if (L.x3_on) {          // the split twin when a bf16x3 convolution reads this tensor next, the fp32 tensor when anybody else does
+        *twin = alive && twin_written_by_producer(net, op.out, sb);
+        *out = !*twin || net.need_bf16[op.out];
+    }
+    if (L.fp8_on) {         // bf16 if anybody reads it, twin if an fp8 conv follows
+        *twin = alive;
+        *out = net.need_bf16[op.out];
+    }
 }
 
 void tt_member(const sncal_hrnet& net, const Op& op, int sb, char* ws, TTMember& m) {
     const ConvLayer& L = net.layers[op.conv];
     const Tensor& ti = net.tensors[op.in];
     const Tensor& to = net.tensors[op.out];
+    bool out = true, twin = false;
+    tt_outputs(net, op, sb, &out, &twin);
     memset(&m, 0, sizeof(m));
-    m.in = ws + ti.offset; m.out = ws + to.offset; m.res = op.res >= 0 ? ws + net.tensors[op.res].offset : nullptr;
+    m.in = ws + ti.offset; m.out = out ? ws + to.offset : nullptr; m.res = op.res >= 0 ? ws + net.tensors[op.res].offset : nullptr;
+    m.out8 = twin ? ws + net.tensors[to.twin].offset : nullptr;
     m.w = L.d_w_tt; m.bias = L.d_bias;
     m.N = sb; m.H = ti.H; m.W = ti.W; m.Cin = L.cin; m.chunks = L.cin / TT_CIN;
     m.cout = L.cout; m.out_cstride = to.C; m.out_coff = op.out_coff; m.relu = op.relu ? 1 : 0;
@@ -1300,25 +1344,33 @@ void tt_member(const sncal_hrnet& net, const Op& op, int sb, char* ws, TTMember&
         m.chunks = L.cin / 16;
         m.w = L.d_w_x3;
         m.w_bytes = (unsigned)((size_t)((L.cout + L.x3_blk - 1) / L.x3_blk) * m.chunks * 9 * 2 * (L.x3_blk / 32) * 1024);
-        // outputs: the split twin when a bf16x3 convolution reads this tensor next, the fp32 tensor when anybody else does
-        const bool twin_out = to.twin >= 0 && net.tensors[to.twin].first >= 0 && twin_written_by_producer(net, op.out, sb);
-        m.out8 = twin_out ? ws + net.tensors[to.twin].offset : nullptr;
-        if (twin_out && !net.need_bf16[op.out]) m.out = nullptr;
         if (op.res_twin) { m.res = ws + net.tensors[net.tensors[op.res].twin].offset; m.res_split = 1; }
     }
-    if (L.fp8_on) {          // C5: e4m3 twin in, 64-channel stages, e4m3 weights; outputs: bf16 if anybody reads it, twin if an fp8 conv follows
+    if (L.fp8_on) {          // C5: e4m3 twin in, 64-channel stages, e4m3 weights
         m.in = ws + net.tensors[ti.twin].offset;
         m.in_bytes = (unsigned)((size_t)sb * ti.H * ti.W * ti.C);
         m.chunks = (L.cin + 63) / 64;
         m.w = L.d_w8;
         m.w_bytes = (unsigned)((size_t)(L.cout / TT_COUT) * m.chunks * 9 * 6 * 1024);
         m.oscale = L.d_oscale;
-        const bool twin_out = to.twin >= 0 && net.tensors[to.twin].first >= 0;
-        m.out8 = twin_out ? ws + net.tensors[to.twin].offset : nullptr;
-        m.out8_inv_scale = twin_out && to.scale > 0.f ? 1.0f / to.scale : 1.0f;
-        if (!net.need_bf16[op.out]) m.out = nullptr;
-        if (getenv("SNCAL_FP8_NO_TWIN_OUT")) { m.out8 = nullptr; m.out = ws + to.offset; }
+        m.out8_inv_scale = twin && to.scale > 0.f ? 1.0f / to.scale : 1.0f;
     }
+}
+
+// Work-list tile of a two-team launch: 0 = 96 x 8 x 32, 1 = 64 x 12 x 32 (bf16x3, 48-channel branch), 2 = 96 x 4 x 32.  Small launches of the
+// split-arithmetic engine (round 5): below two 8-row items per team the launch lasts as long as its longest item while most teams hold short
+// ones or nothing -- the 96 x 4 x 32 tile (conv_tt.hip, c31) halves the items instead
+int tt_cfg(const sncal_hrnet& net, const Op* ops, int n, int sb) {
+    const ConvLayer& L0 = net.layers[ops[0].conv];
+    if (!L0.x3_on) return 0;
+    if (n == 1 && L0.x3_blk == 64) return 1;
+    const int per_team = getenv("SNCAL_TT_SMALL_ITEMS") ? atoi(getenv("SNCAL_TT_SMALL_ITEMS")) : 2;      // (read per plan: tests run both tiles in one process; 0 = never)
+    long items = 0;
+    for (int i = 0; i < n; ++i) {
+        const Tensor& ti = net.tensors[ops[i].in];
+        items += (long)((sb * (ti.H + 1) + TT_TH - 1) / TT_TH) * ((ti.W + TT_TW - 1) / TT_TW) * ((net.layers[ops[i].conv].cout + TT_COUT - 1) / TT_COUT);
+    }
+    return items < (long)per_team * 2 * net.n_cus ? 2 : 0;
 }
 
 // The work items of the member convolutions as eight queues, one per XCD.  Workgroup b runs on XCD b % 8 (observed
@@ -1328,13 +1380,8 @@ void tt_member(const sncal_hrnet& net, const Op& op, int sb, char* ws, TTMember&
 // (longest-processing-time order: the teams, which take the next item when they finish one, end within one cheap item
 // of each other).  Rounds 2-4 dealt the items to the teams HERE (static lists); a workgroup whose CU was held by a
 // camera-solve wavefront then started when the first other workgroup had finished, and the launch lasted twice as long.
-int tt_build_plan(sncal_hrnet& net, const TTMember* mem, int n, sncal_hrnet::TTPlanDev& out, hipStream_t stream, int tile_h = TT_TH, int cout_blk = TT_COUT) {
-    if (!net.n_cus) {
-        int dev = 0, cus = 0;
-        SNCAL_CHECK_HIP(hipGetDevice(&dev));
-        SNCAL_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        net.n_cus = cus > 0 ? cus : 256;
-    }
+int tt_build_plan(const sncal_hrnet& net, const TTMember* mem, int n, TTPlanDev& out, hipStream_t stream) {
+    const int tile_h = out.cfg == 1 ? 12 : out.cfg == 2 ? 4 : TT_TH, cout_blk = out.cfg == 1 ? 64 : TT_COUT;
     const int n_wgs = net.n_cus;
     const int n_xcd = n_wgs >= 8 ? 8 : 1;                  // (fewer than 8 workgroups: every workgroup reads queue b % 8, so only queue 0.. exist)
     std::vector<std::vector<TTItem>> per_xcd(8);
@@ -1378,18 +1425,367 @@ int tt_build_plan(sncal_hrnet& net, const TTMember* mem, int n, sncal_hrnet::TTP
     return SNCAL_OK;
 }
 
-// ticket words of a network: [0, 9) and [16, 25) the fused blocks, [32, 48) the two-team kernel, [48, 57) layer1's seams, [64, 73) the
-// pipelined stride-2 kernel
+// ticket words of a network: the first word of each kernel's own range
+constexpr int TICKET_SEAM = 0;       // layer1's seams and block 0's tail (bneckx3.hip)
+constexpr int TICKET_BBX3 = 16;      // fused BasicBlock, split arithmetic (bblockx3.hip)
+constexpr int TICKET_TT = 32;        // two-team kernel (conv_tt.hip)
+constexpr int TICKET_BB48 = 48;      // fused BasicBlock, bf16 (bblock.hip)
 constexpr int TICKET_WORDS = 96;
-static int ensure_tickets(sncal_hrnet* net, hipStream_t stream) {
-    if (net->d_tickets) return SNCAL_OK;
-    SNCAL_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->d_tickets), TICKET_WORDS * sizeof(unsigned)));
-    SNCAL_CHECK_HIP(hipMemsetAsync(net->d_tickets, 0, TICKET_WORDS * sizeof(unsigned), stream));
+
+// ---- the schedule builder: fusion predicates, asked once per (layout, sub-batch size) --------------------------------
+
+// layer1 block 0's tail (bneckx3.hip): op i is the downsample branch, op i + 1 the conv3 that adds it
+bool fuses_bneck_tail(const sncal_hrnet& net, size_t i, int sb) {
+    const Op& op = net.ops[i];
+    if (!(net.fuse_bneck & 2) || !net.x3 || op.relu || op.res >= 0 || op.out_f32 || op.out_coff != 0 || i + 1 >= net.ops.size() ||
+        !net.layers[op.conv].d_w_bnp || net.layers[op.conv].cout != BNP_WIDE || net.layers[op.conv].x3_on || op.launch_group >= 0) return false;
+    const Op& nx = net.ops[i + 1];
+    return nx.type == OP_CONV && op_active(net, nx) && nx.res == op.out && nx.relu && !nx.out_f32 && nx.out_coff == 0 && nx.launch_group < 0 &&
+           net.layers[nx.conv].d_w_bnp && net.layers[nx.conv].cout == BNP_WIDE && !net.layers[nx.conv].x3_on &&
+           net.tensors[op.in].C == BNP_MID && net.tensors[nx.in].C == BNP_MID && net.tensors[nx.out].C == BNP_WIDE &&
+           net.tensors[op.in].H == net.tensors[nx.in].H && net.tensors[op.in].W == net.tensors[nx.in].W &&
+           net.tensors[op.out].last_read == (int)i + 1 &&      // nobody else reads the downsample branch
+           !writes_twin(net, nx.out, sb);
+}
+
+// layer1 (bneckx3.hip): conv3 (+ residual, ReLU) of a Bottleneck and conv1 (+ ReLU) of the next one in one pass over the pixels: the
+// 256-channel tensor between them is written once (the next residual) and not read back
+bool fuses_bneck_seam(const sncal_hrnet& net, size_t i, int sb) {
+    const Op& op = net.ops[i];
+    if (!(net.fuse_bneck & 1) || !net.x3 || !op.relu || op.res < 0 || op.out_f32 || op.out_coff != 0 || i + 1 >= net.ops.size() ||
+        !net.layers[op.conv].d_w_bnp || net.layers[op.conv].cout != BNP_WIDE || net.layers[op.conv].x3_on) return false;
+    const Op& nx = net.ops[i + 1];
+    const Tensor& t_in = net.tensors[op.in];
+    const Tensor& t_res = net.tensors[op.res];
+    const Tensor& t_y = net.tensors[op.out];
+    return nx.type == OP_CONV && op_active(net, nx) && nx.in == op.out && nx.res < 0 && nx.relu && !nx.out_f32 && nx.out_coff == 0 &&
+           nx.launch_group < 0 && net.layers[nx.conv].d_w_bnp && net.layers[nx.conv].cout == BNP_MID && !net.layers[nx.conv].x3_on &&
+           t_in.C == BNP_MID && t_res.C == BNP_WIDE && t_y.C == BNP_WIDE && net.tensors[nx.out].C == BNP_MID &&
+           t_res.H == t_y.H && t_res.W == t_y.W &&
+           !writes_twin(net, op.out, sb) && !writes_twin(net, nx.out, sb);      // neither output may owe somebody a split twin (they feed generic kernels)
+}
+
+// bf16x3 engine, 48-channel BasicBlock: conv1 -> mid tile in LDS as hi / lo planes -> conv2 + residual (bblockx3.hip); the mid tensor and
+// its twin are not written at all
+bool fuses_bblockx3(const sncal_hrnet& net, size_t i, int sb) {
+    const Op& op = net.ops[i];
+    if (!net.x3 || !op.relu || op.res >= 0 || op.out_f32 || i + 1 >= net.ops.size() || !net.layers[op.conv].x3_on ||
+        !net.layers[op.conv].d_w_bbx || !tt_eligible(net, op, sb)) return false;
+    const Op& nx = net.ops[i + 1];
+    return nx.type == OP_CONV && op_active(net, nx) && nx.in == op.out && nx.res == op.in && nx.relu && !nx.out_f32 && op.out_coff == 0 &&
+           net.layers[nx.conv].x3_on && net.layers[nx.conv].d_w_bbx && tt_eligible(net, nx, sb) && net.tensors[op.in].C == 48 &&
+           net.tensors[op.in].twin >= 0 && net.tensors[net.tensors[op.in].twin].first >= 0;
+}
+
+// bf16 engine, 48-channel BasicBlock: conv1 + conv2 (+ residual) fused when the next active op is its second convolution and both layers
+// carry the (MI = 3, G = 3) packing (bblock.hip)
+bool fuses_bblock48(const sncal_hrnet& net, size_t i) {
+    const Op& op = net.ops[i];
+    if (!net.fuse_bblock || net.dtype != SNCAL_BF16 || !op.relu || op.res >= 0 || op.out_f32 || i + 1 >= net.ops.size()) return false;
+    const Op& nx = net.ops[i + 1];
+    if (nx.type != OP_CONV || !op_active(net, nx) || nx.in != op.out || nx.res != op.in || !nx.relu || nx.out_f32 || nx.out_coff != 0 || op.out_coff != 0)
+        return false;
+    auto ok = [](const ConvLayer& L) { return L.k == 3 && L.stride == 1 && L.cin == 48 && L.cout == 48 && L.cin_phys == 48 && L.mi == 3 && L.g == 3 &&
+                                              L.chunks == 2 && L.nblk == 1; };
+    return ok(net.layers[op.conv]) && ok(net.layers[nx.conv]) && net.tensors[op.in].C == 48 && net.tensors[nx.out].C == 48;
+}
+
+// The members [i, i + n) of a launch group (independent convolutions, consecutive ops) as ONE launch when they can share one: all on the
+// two-team kernel, the shared-input stride-2 kernel, or one grouped variant of the generic kernel.  Otherwise e stays untouched (e.n == 1)
+// and the caller takes the first member alone, then tries the rest again.
+int plan_group(const sncal_hrnet& net, size_t i, int n, int sb, Launch& e) {
+    if (n < 2 || n > 3) return SNCAL_OK;
+    const Op* ops = &net.ops[i];
+    bool all_tt = true, any_fp8 = false, all_fp8 = true;
+    int couts = 0;
+    for (int k = 0; k < n; ++k) {
+        const ConvLayer& L = net.layers[ops[k].conv];
+        all_tt = all_tt && tt_eligible(net, ops[k], sb) && L.fp8_on == net.layers[ops[0].conv].fp8_on && !(L.x3_on && L.x3_blk != TT_COUT);
+        couts += (L.cout + TT_COUT - 1) / TT_COUT * TT_COUT;
+        any_fp8 = any_fp8 || L.fp8_on;
+        all_fp8 = all_fp8 && L.fp8_on;
+    }
+    if (any_fp8 && !all_fp8) return SNCAL_OK;     // fp8 and bf16 members (layer selection by width) cannot share one launch
+    if (all_tt && couts <= TT_COUT_MAX) {         // (the tables' last 16 floats carry the ticket queue's slots)
+        e.kind = LK_TT; e.n = n; e.plan.cfg = tt_cfg(net, ops, n, sb);
+        return SNCAL_OK;
+    }
+    // the chain-starting stride-2 convolutions of one input tensor (schedule_fuse_section): one launch, tile-major (conv.hpp)
+    if (ops[0].shared_in && !net.x3) return SNCAL_OK;        // (the other engines run them one by one)
+    Member m[3];
+    for (int k = 0; k < n; ++k) {
+        const int rc = choose_conv(net, ops[k], sb, m[k]);
+        if (rc) return rc;
+    }
+    if (ops[0].shared_in) {
+        for (int k = 0; k < n; ++k) {
+            const ConvVariant* v = m[k].v;
+            if (ops[k].in != ops[0].in || v->ks != 3 || v->stride != 2 || v->ni != 2 || v->g != 3 || (v->mi != 6 && v->mi != 3) ||
+                m[k].tiles_x != m[0].tiles_x || m[k].tiles_y != m[0].tiles_y || m[k].twf != m[0].twf) return SNCAL_OK;
+        }
+        e.kind = LK_SHARED_S2;
+    } else {
+        for (int k = 0; k < n; ++k)
+            if (m[k].v != m[0].v || !m[k].v->launch_group) return SNCAL_OK;
+        e.kind = LK_GROUP;
+    }
+    e.n = n;
+    std::copy(m, m + n, e.m);
     return SNCAL_OK;
 }
 
-// the ops [ops, ops + n) (independent, all eligible, all bf16 or all fp8) as ONE launch of the two-team kernel
-int run_conv_tt(sncal_hrnet& net, const Op* ops, int n, int key, int sb, char* ws, hipStream_t stream) {
+void profile_launch(const sncal_hrnet& net, const Schedule& s, Launch& e) {
+    const Op& op = net.ops[e.op];
+    const Op* ops = &op;
+    const int sb = s.sb, C = net.desc.num_classes;
+    const Tensor& th = net.tensors[net.t_heat];
+    Prof& r = e.prof;
+    switch (e.kind) {
+        case LK_INPUT: {
+            const Tensor& t = net.tensors[op.out];
+            r = {"nchw_to_nhwc", 0, (double)sb * t.H * t.W * (3 * 4 + net.ge * net.esize)};
+            break;
+        }
+        case LK_CONV: r = conv_prof(net, op, sb, e.m[0].v); break;
+        case LK_GROUP: for (int k = 0; k < e.n; ++k) add_prof(r, conv_prof(net, ops[k], sb, e.m[0].v)); break;
+        case LK_SHARED_S2: {
+            for (int k = 0; k < e.n; ++k) add_prof(r, conv_prof(net, ops[k], sb, e.m[k].v));
+            const Tensor& ti = net.tensors[op.in];
+            r.bytes -= (double)(e.n - 1) * sb * ti.H * ti.W * ti.C * net.esize;      // the members' common input counts once
+            if (!profile_detail()) r.kernel = "conv_shared_s2<" SNCAL_X3_NAME ",k3,NI2,G3>";     // (its own row: not the first member's variant)
+            break;
+        }
+        case LK_TT: {
+            for (int k = 0; k < e.n; ++k) add_prof(r, conv_prof(net, ops[k], sb, nullptr));
+            const ConvLayer& L0 = net.layers[op.conv];
+            r.kernel = L0.fp8_on ? "conv_tt<fp8,k3,s1,8x32x96>" : e.plan.cfg == 1 ? "conv_tt<" SNCAL_X3_NAME ",k3,s1,12x32x64>" :
+                       e.plan.cfg == 2 ? "conv_tt<" SNCAL_X3_NAME ",k3,s1,4x32x96>" : L0.x3_on ? "conv_tt<" SNCAL_X3_NAME ",k3,s1,8x32x96>" :
+                       "conv_tt<bf16,k3,s1,8x32x96>";
+            if (profile_detail()) {      // one profile row per launch kind
+                bool out = true, twin = false;
+                tt_outputs(net, op, sb, &out, &twin);
+                r.kernel += fmt("@%d members%s%s%s", e.n, op.res >= 0 ? "+res" : "", out ? "+f32" : "", twin ? "+twin" : "");
+            }
+            break;
+        }
+        case LK_BNECK_TAIL: case LK_BNECK_SEAM: {
+            const bool tail = e.kind == LK_BNECK_TAIL;
+            const Tensor& t_y = net.tensors[ops[tail ? 1 : 0].out];
+            const long long P = (long long)sb * t_y.H * t_y.W;
+            r.kernel = tail ? "bneck_tail_ds_x3" : "bneck_seam_x3";
+            r.flops = 2.0 * 2.0 * (double)P * BNP_MID * BNP_WIDE;
+            r.bytes = tail ? (double)P * 4.0 * (BNP_MID + BNP_MID + BNP_WIDE) + 2.0 * BNP_W_BYTES
+                           : (double)P * 4.0 * (BNP_MID + BNP_WIDE + BNP_WIDE + BNP_MID) + 2.0 * BNP_W_BYTES;
+            break;
+        }
+        case LK_BBLOCKX3: case LK_BBLOCK48: {
+            const Tensor& ti = net.tensors[op.in];
+            const double px = (double)sb * ti.H * ti.W;
+            r.flops = 2.0 * 2.0 * px * 48 * 48 * 9;
+            if (e.kind == LK_BBLOCKX3) { r.kernel = "bblockx3_fused"; r.bytes = px * 48 * 4 * (1.0 + (e.m[1].twin ? 1.0 : 0.0) + (e.m[1].f32 ? 1.0 : 0.0)) + 2.0 * BBX_W_BYTES; }
+            else { r.kernel = "bblock48_fused"; r.bytes = 2.0 * px * 48 * 2 + 2.0 * 48 * 48 * 9 * 2; }
+            break;
+        }
+        case LK_UPADD: {
+            const Tensor& to = net.tensors[op.out];
+            double b = 0;
+            for (int s2 = 0; s2 < op.nsrc; ++s2) { const Tensor& ts = net.tensors[op.srcs[s2]]; b += (double)sb * ts.H * ts.W * ts.C * net.esize; }
+            const int C0 = op.nsrc ? net.tensors[op.srcs[0]].C : to.C;
+            r = {"upsample_add", 0, b + (double)sb * to.H * to.W * C0 * net.esize * (op.base >= 0 ? 2 : 1)};
+            break;
+        }
+        case LK_HEAD: {
+            const Tensor& td = net.tensors[op.head_direct];
+            const Tensor& to = net.tensors[op.out];
+            const double px = (double)sb * to.H * to.W;
+            r.kernel = net.x3 ? "headx3_fused" : "head_fused";
+            r.flops = 2.0 * px * net.head_hp * (net.head_k + net.head_m2 * 16);
+            r.bytes = px * (td.C * 2 + to.C * 4);
+            for (int s2 = 0; s2 < op.head_nsrc; ++s2) { const Tensor& ts = net.tensors[op.head_src[s2]]; r.bytes += (double)sb * ts.H * ts.W * ts.C * 2; }
+            for (int s2 = 0; s2 < op.head_nfold; ++s2) { const Tensor& tf = net.tensors[op.head_fold[s2]]; r.bytes += (double)sb * tf.H * tf.W * tf.C * 2; }
+            break;
+        }
+        case LK_TAIL: {
+            const Tensor& tl = net.tensors[op.in];
+            r = {"softmax_nchw", 0, (double)sb * C * th.H * th.W * 4 * 2};
+            e.prof_kp = s.dec == DEC_HEAD ? Prof{"kp_finish", 0, (double)head32_decode_scratch(sb, C, tl.H, tl.W)}
+                      : s.dec == DEC_TAIL ? Prof{"logsoftmax_decode_fused", 0, (double)sb * tl.H * tl.W * tl.C * 4} : r;
+            break;
+        }
+        case LK_DECODE: r = {"kp_decode", 0, (double)sb * C * th.H * th.W * 4}; break;
+    }
+}
+
+// the fused head's parameters that do not point into the workspace
+void head_params(const sncal_hrnet& net, const Op& op, int sb, HeadParams& hp) {
+    const Tensor& td = net.tensors[op.head_direct];
+    const Tensor& to = net.tensors[op.out];
+    memset(&hp, 0, sizeof(hp));
+    hp.range = net.d_range;
+    hp.Cd = td.C;
+    hp.w0 = net.d_hw0; hp.bias0 = net.d_hb0; hp.w1 = net.d_hw1; hp.bias1 = net.d_hb1;
+    hp.w0_32 = net.d_hw0_32; hp.w1_32 = net.d_hw1_32; hp.ks16 = net.head_ks16;
+    hp.w0_32_lo = net.d_hw0_32l; hp.w1_32_lo = net.d_hw1_32l;
+    hp.nsrc = op.head_nsrc;
+    for (int s2 = 0; s2 < op.head_nsrc; ++s2) {
+        const Tensor& ts = net.tensors[op.head_src[s2]];
+        hp.Hs[s2] = ts.H; hp.Ws[s2] = ts.W;
+        hp.sy[s2] = to.H > 1 ? (float)(ts.H - 1) / (float)(to.H - 1) : 0.f;
+        hp.sx[s2] = to.W > 1 ? (float)(ts.W - 1) / (float)(to.W - 1) : 0.f;
+    }
+    hp.nfold = op.head_nfold; hp.ks1 = net.head_ks1;
+    for (int s2 = 0; s2 < op.head_nfold; ++s2) {
+        const Tensor& tf = net.tensors[op.head_fold[s2]];
+        hp.Cf[s2] = tf.C; hp.Hf[s2] = tf.H; hp.Wf[s2] = tf.W;
+        hp.fsy[s2] = to.H > 1 ? (float)(tf.H - 1) / (float)(to.H - 1) : 0.f;
+        hp.fsx[s2] = to.W > 1 ? (float)(tf.W - 1) / (float)(to.W - 1) : 0.f;
+    }
+    hp.N = sb; hp.H = to.H; hp.W = to.W; hp.HP = net.head_hp; hp.NQ = net.head_hp / 32; hp.LC = to.C;
+}
+
+// Where the keypoint decode runs when a call wants keypoints and no heatmap: inside the head (head32.hip / headx3.hip: log-softmax and the
+// tiles' maxima, the logits tensor's own workspace slot -- alive from the head to the softmax op -- holds the partial maxima, kp_finish
+// completes them), else fused with the log-softmax (the (B,C,h,w) tensor is never written; its workspace slot serves as the much smaller
+// scratch), else after a plain softmax.
+DecodeAt decode_at(const sncal_hrnet& net, const Schedule& s) {
+    static const bool fuse_decode = !(getenv("SNCAL_FUSE_DECODE") && atoi(getenv("SNCAL_FUSE_DECODE")) == 0);
+    static const bool head_decode = !(getenv("SNCAL_HEAD_DECODE") && atoi(getenv("SNCAL_HEAD_DECODE")) == 0);
+    const int C = net.desc.num_classes, sb = s.sb;
+    const Tensor& th = net.tensors[net.t_heat];
+    if (!fuse_decode || net.desc.head_softmax) return DEC_NONE;
+    for (const Launch& e : s.launches) {
+        const Op& op = net.ops[e.op];
+        if (e.kind == LK_HEAD) {
+            const Tensor& to = net.tensors[op.out];
+            HeadParams hp;
+            head_params(net, op, sb, hp);
+            if (head_decode && C > 32 && C <= 64 && (net.x3 ? headx3_applies(hp) : head32_applies(hp)) &&
+                head32_decode_scratch(sb, C, to.H, to.W) <= to.bytes && th.H == to.H && th.W == to.W) return DEC_HEAD;
+        }
+        if (e.kind == LK_TAIL) {
+            const Tensor& tl = net.tensors[op.in];
+            if (logsoftmax_decode_scratch(sb, C, tl.H, tl.W) <= (size_t)sb * C * th.H * th.W * sizeof(float)) return DEC_TAIL;
+        }
+    }
+    return DEC_NONE;
+}
+
+// The launch schedule of a sub-batch of sb frames at the current layout.  Fusions, in this order of priority: a launch group over the
+// remaining consecutive members; layer1's downsample tail, then its seams, then the split-arithmetic BasicBlock, then the bf16 one; else
+// the op alone, on the two-team kernel when it is eligible.
+int build_schedule(const sncal_hrnet& net, int sb, Schedule& s) {
+    s.sb = sb;
+    for (size_t i = 0; i < net.ops.size();) {
+        const Op& op = net.ops[i];
+        if (!op_active(net, op)) { ++i; continue; }
+        Launch e;
+        e.op = (int)i;
+        switch (op.type) {
+            case OP_INPUT: e.kind = LK_INPUT; break;
+            case OP_CONV: {
+                int n = 0;
+                if (op.launch_group >= 0)
+                    while (i + n < net.ops.size() && net.ops[i + n].launch_group == op.launch_group && net.ops[i + n].type == OP_CONV &&
+                           op_active(net, net.ops[i + n])) ++n;
+                int rc = plan_group(net, i, n, sb, e);
+                if (rc) return rc;
+                if (e.n > 1) break;
+                if (fuses_bneck_tail(net, i, sb)) { e.kind = LK_BNECK_TAIL; e.n = 2; }
+                else if (fuses_bneck_seam(net, i, sb)) { e.kind = LK_BNECK_SEAM; e.n = 2; }
+                else if (fuses_bblockx3(net, i, sb)) {
+                    const int out = net.ops[i + 1].out;
+                    e.kind = LK_BBLOCKX3; e.n = 2;
+                    e.split_in = !twin_written_by_producer(net, op.in, sb);      // the fp32 input's split twin, unless its producer wrote it
+                    e.m[1].twin = writes_twin(net, out, sb);
+                    e.m[1].f32 = !e.m[1].twin || net.need_bf16[out];
+                }
+                else if (fuses_bblock48(net, i)) { e.kind = LK_BBLOCK48; e.n = 2; }
+                else if (tt_eligible(net, op, sb)) { e.kind = LK_TT; e.plan.cfg = tt_cfg(net, &op, 1, sb); }
+                else {
+                    e.kind = LK_CONV;
+                    rc = choose_conv(net, op, sb, e.m[0]);
+                    if (rc) return rc;
+                }
+                break;
+            }
+            case OP_UPADD:
+                e.kind = LK_UPADD;
+                e.m[0].twin = writes_twin(net, op.out, sb);
+                e.m[0].f32 = !e.m[0].twin || net.need_bf16[op.out];
+                break;
+            case OP_HEAD: e.kind = LK_HEAD; break;
+            case OP_SOFTMAX: e.kind = LK_TAIL; break;
+            case OP_DECODE: e.kind = LK_DECODE; break;
+        }
+        i += e.n;
+        s.launches.push_back(e);
+    }
+    s.dec = decode_at(net, s);
+    for (Launch& e : s.launches) profile_launch(net, s, e);
+    return SNCAL_OK;
+}
+
+// the schedule of sub-batch size sb at the current layout, built on first use
+int schedule_for(sncal_hrnet& net, int sb, Schedule** out) {
+    for (Schedule& s : net.schedules)
+        if (s.sb == sb) { *out = &s; return SNCAL_OK; }
+    Schedule s;
+    const int rc = build_schedule(net, sb, s);
+    if (rc) return rc;
+    net.schedules.push_back(std::move(s));
+    *out = &net.schedules.back();
+    return SNCAL_OK;
+}
+
+// ---- the launches ---------------------------------------------------------------------------------------------------
+struct Call {                    // what one sub-batch of a forward call hands the launches
+    int b0, sb, img_h, img_w;
+    char* ws;
+    const float* x;              // the frames: fp32 NCHW or u8 HWC
+    const unsigned char* x8;
+    float* heat;                 // the caller's heatmap, or the heat tensor's workspace slot
+    float* kpts;                 // this sub-batch's keypoints, or null
+    DecodeAt dec;                // where the decode runs in this call
+    hipStream_t stream;
+};
+
+// tuning aids: write a device buffer of n_trace timestamps to `file` and free it (synchronises the stream)
+void dump_trace(unsigned long long* d_trace, size_t n_trace, const char* file, hipStream_t stream) {
+    std::vector<unsigned long long> h(n_trace);
+    (void)hipStreamSynchronize(stream);
+    (void)hipMemcpy(h.data(), d_trace, n_trace * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(d_trace);
+    if (FILE* f = fopen(file, "wb")) { fwrite(h.data(), 8, n_trace, f); fclose(f); }
+}
+
+int run_input(const sncal_hrnet& net, const Launch& e, const Call& c) {
+    const Tensor& t = net.tensors[net.ops[e.op].out];
+    if (c.x8) return launch_u8hwc_to_nhwc(net.dtype, c.x8 + (size_t)c.b0 * 3 * t.H * t.W, c.ws + t.offset, c.sb, t.H, t.W, c.stream);
+    return launch_nchw_to_nhwc(net.dtype, c.x + (size_t)c.b0 * 3 * t.H * t.W, c.ws + t.offset, c.sb, 3, t.H, t.W, c.stream, net.d_range);
+}
+
+int run_conv(const sncal_hrnet& net, const Launch& e, const Call& c) {
+    const Op& op = net.ops[e.op];
+    ConvParams p;
+    conv_params(net, op, c.sb, c.ws, e.m[0], p);
+    // tuning aid: SNCAL_CONV_TRACE=<layer name> dumps per-workgroup phase timestamps of that layer's last launch to conv_trace.bin
+    static const char* trace_name = getenv("SNCAL_CONV_TRACE");
+    unsigned long long* d_trace = nullptr; size_t n_trace = 0;
+    if (trace_name && net.layers[op.conv].name == trace_name) {
+        n_trace = (size_t)8 * ((p.n_work + 7) / 8) * 16;
+        if (hipMalloc(&d_trace, n_trace * 8) == hipSuccess) { (void)hipMemsetAsync(d_trace, 0, n_trace * 8, c.stream); p.trace = d_trace; }
+    }
+    e.m[0].v->launch(p, dim3(8 * p.per_xcd), e.m[0].lds, c.stream);
+    SNCAL_CHECK_LAUNCH();
+    if (d_trace) dump_trace(d_trace, n_trace, "conv_trace.bin", c.stream);
+    return SNCAL_OK;
+}
+
+// the members on the two-team kernel (independent, all eligible, all bf16 or all fp8)
+int run_tt(sncal_hrnet& net, Launch& e, const Call& c) {
+    const Op* ops = &net.ops[e.op];
+    const int n = e.n, sb = c.sb;
+    hipStream_t stream = c.stream;
     TTParams tp;
     memset(&tp, 0, sizeof(tp));
     tp.range = net.d_range;
@@ -1397,50 +1793,28 @@ int run_conv_tt(sncal_hrnet& net, const Op* ops, int n, int key, int sb, char* w
     const sncal::LaunchEvents armed = sncal::launch_events();        // the profiling event pair belongs to the convolution launch,
     sncal::launch_events() = sncal::LaunchEvents{};                  // not to the calibration / quantisation helpers in front of it
     for (int i = 0; i < n; ++i) {
-        if (net.calibrating && net.tensors[ops[i].in].twin >= 0) {        // C5 calibration: max |x| of every candidate input tensor
-            const Tensor& ti = net.tensors[ops[i].in];
-            const int rc = launch_absmax_bf16(ws + ti.offset, (size_t)sb * ti.H * ti.W * ti.C, net.d_amax + ops[i].in, stream);
+        const Tensor& ti = net.tensors[ops[i].in];
+        if (net.calibrating && ti.twin >= 0) {        // C5 calibration: max |x| of every candidate input tensor
+            const int rc = launch_absmax_bf16(c.ws + ti.offset, (size_t)sb * ti.H * ti.W * ti.C, net.d_amax + ops[i].in, stream);
             if (rc) return rc;
         }
         if (x3 && !twin_written_by_producer(net, ops[i].in, sb)) {       // bf16x3: the fp32 input's split twin, unless its producer wrote it
-            const Tensor& ti = net.tensors[ops[i].in];
-            const int rc = launch_split_f32(ws + ti.offset, ws + net.tensors[ti.twin].offset, (size_t)sb * ti.H * ti.W * ti.C, stream, net.d_range);
+            const int rc = launch_split_f32(c.ws + ti.offset, c.ws + net.tensors[ti.twin].offset, (size_t)sb * ti.H * ti.W * ti.C, stream, net.d_range);
             if (rc) return rc;
         }
         if (fp8 && !twin_written_by_producer(net, ops[i].in, sb)) {      // first fp8 conv of a chain: quantise its input here
-            const Tensor& ti = net.tensors[ops[i].in];
-            const int rc = launch_quantize_fp8(ws + ti.offset, ws + net.tensors[ti.twin].offset, (size_t)sb * ti.H * ti.W * ti.C, ti.scale, stream);
+            const int rc = launch_quantize_fp8(c.ws + ti.offset, c.ws + net.tensors[ti.twin].offset, (size_t)sb * ti.H * ti.W * ti.C, ti.scale, stream);
             if (rc) return rc;
         }
-        tt_member(net, ops[i], sb, ws, tp.m[i]);
+        tt_member(net, ops[i], sb, c.ws, tp.m[i]);
     }
     sncal::launch_events() = armed;
-    const bool cfg64 = x3 && n == 1 && net.layers[ops[0].conv].x3_blk == 64;   // bf16x3, 48-channel branch: tile 64 x 12 x 32
-    if (fp8) key += 1 << 30;                                               // fp8 plans have their own stage counts
-    auto it = net.tt_plans.find(key);
-    if (it == net.tt_plans.end() || it->second.n_wgs == 0) {       // static per layout: built on the first forward
-        sncal_hrnet::TTPlanDev pd;
-        // Small launches of the split-arithmetic engine (round 5): below two 8-row items per team the launch lasts as long as its longest item
-        // while most teams hold short ones or nothing -- the 96 x 4 x 32 tile (conv_tt.hip, c31) halves the items instead
-        int tile_h = cfg64 ? 12 : TT_TH;
-        pd.cfg = cfg64 ? 1 : 0;
-        if (x3 && !cfg64) {
-            const int per_team = getenv("SNCAL_TT_SMALL_ITEMS") ? atoi(getenv("SNCAL_TT_SMALL_ITEMS")) : 2;      // (read per plan: tests run both tiles in one process; 0 = never)
-            long items = 0;
-            for (int i = 0; i < n; ++i)
-                items += (long)((tp.m[i].N * (tp.m[i].H + 1) + TT_TH - 1) / TT_TH) * ((tp.m[i].W + TT_TW - 1) / TT_TW) * ((tp.m[i].cout + TT_COUT - 1) / TT_COUT);
-            int cus = net.n_cus;
-            if (!cus) { int dev = 0; (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev); if (cus <= 0) cus = 256; }
-            if (items < (long)per_team * 2 * cus) { tile_h = 4; pd.cfg = 2; }
-        }
-        const int rc = tt_build_plan(net, tp.m, n, pd, stream, tile_h, cfg64 ? 64 : TT_COUT);
+    if (!e.plan.n_wgs) {       // static per layout: uploaded by the first launch
+        const int rc = tt_build_plan(net, tp.m, n, e.plan, stream);
         if (rc) return rc;
-        it = net.tt_plans.insert({key, pd}).first;
     }
-    const int cfg = it->second.cfg;
-    tp.items = it->second.items; tp.xcd_first = it->second.first; tp.lazy = it->second.lazy;
-    { const int rc = ensure_tickets(&net, stream); if (rc) return rc; }
-    tp.queue = net.d_tickets + 32;
+    tp.items = e.plan.items; tp.xcd_first = e.plan.first; tp.lazy = e.plan.lazy;
+    tp.queue = net.d_tickets + TICKET_TT;
     // tuning aid: SNCAL_TT_TRACE=<file> dumps the per-team phase timestamps of the LAST launch with 3 members
     // (SNCAL_TT_TRACE_CFG64=1: of the last launch of the 64-channel tile instead)
     static const char* trace_file = getenv("SNCAL_TT_TRACE");
@@ -1448,190 +1822,27 @@ int run_conv_tt(sncal_hrnet& net, const Op* ops, int n, int key, int sb, char* w
     static const int trace_nth = getenv("SNCAL_TT_TRACE_NTH") ? atoi(getenv("SNCAL_TT_TRACE_NTH")) : -1;      // only the n-th such launch of the process
     static int trace_seen = 0;
     unsigned long long* d_trace = nullptr;
-    const size_t n_trace = (size_t)it->second.n_wgs * 2 * 256;
-    if (trace_file && (trace_cfg64 ? cfg64 : n == 3) && (trace_nth < 0 || trace_seen++ == trace_nth) && hipMalloc(&d_trace, n_trace * 8) == hipSuccess) { (void)hipMemsetAsync(d_trace, 0, n_trace * 8, stream); tp.trace = d_trace; }
+    const size_t n_trace = (size_t)e.plan.n_wgs * 2 * 256;
+    if (trace_file && (trace_cfg64 ? e.plan.cfg == 1 : n == 3) && (trace_nth < 0 || trace_seen++ == trace_nth) && hipMalloc(&d_trace, n_trace * 8) == hipSuccess) { (void)hipMemsetAsync(d_trace, 0, n_trace * 8, stream); tp.trace = d_trace; }
     { static const int abl = getenv("SNCAL_TT_ABLATE") ? atoi(getenv("SNCAL_TT_ABLATE")) : 0; tp.ablate = abl; }
-    launch_conv_tt(tp, it->second.n_wgs, fp8 ? 1 : x3 ? 2 : 0, stream, cfg);
+    launch_conv_tt(tp, e.plan.n_wgs, fp8 ? 1 : x3 ? 2 : 0, stream, e.plan.cfg);
     SNCAL_CHECK_LAUNCH();
-    if (d_trace) {
-        std::vector<unsigned long long> h(n_trace);
-        (void)hipStreamSynchronize(stream);
-        (void)hipMemcpy(h.data(), d_trace, n_trace * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(d_trace);
-        if (FILE* f = fopen(trace_file, "wb")) { fwrite(h.data(), 8, n_trace, f); fclose(f); }
-    }
-    static const bool fp8_debug = getenv("SNCAL_FP8_DEBUG") != nullptr;      // tuning aid: range of every fp8 launch's bf16 outputs
-    if (fp8 && fp8_debug) {
-        (void)hipStreamSynchronize(stream);
-        for (int i = 0; i < n; ++i) {
-            const Tensor& to = net.tensors[ops[i].out];
-            const Tensor& ti = net.tensors[ops[i].in];
-            const size_t ne = (size_t)sb * to.H * to.W * to.C;
-            std::vector<uint16_t> h(ne);
-            double mx = 0, sum = 0; size_t bad = 0;
-            unsigned long long ck8 = 0, ckin = 0;
-            if (tp.m[i].out8) { std::vector<uint8_t> h8(ne); (void)hipMemcpy(h8.data(), tp.m[i].out8, ne, hipMemcpyDeviceToHost); for (size_t k = 0; k < ne; ++k) ck8 = ck8 * 1315423911ull + h8[k]; }
-            { const size_t ni = (size_t)sb * ti.H * ti.W * ti.C; std::vector<uint8_t> h8(ni); (void)hipMemcpy(h8.data(), tp.m[i].in, ni, hipMemcpyDeviceToHost); for (size_t k = 0; k < ni; ++k) ckin = ckin * 1315423911ull + h8[k]; }
-            fprintf(stderr, "[ck] %s in %016llx out8 %016llx\n", net.layers[ops[i].conv].name.c_str(), ckin, ck8);
-            if (tp.m[i].out) {
-                (void)hipMemcpy(h.data(), tp.m[i].out, ne * 2, hipMemcpyDeviceToHost);
-                for (size_t k = 0; k < ne; ++k) { uint32_t u = (uint32_t)h[k] << 16; float f; memcpy(&f, &u, 4); if (!(std::fabs(f) < 1e3f)) { if (bad < 48) fprintf(stderr, "   bad %g at n %zu y %zu x %zu c %zu\n", f, k / ((size_t)to.H * to.W * to.C), (k / ((size_t)to.W * to.C)) % to.H, (k / to.C) % to.W, k % to.C); ++bad; } else { mx = std::max(mx, (double)std::fabs(f)); sum += std::fabs(f); } }
-            }
-            fprintf(stderr, "[fp8] %-44s in_scale %.4g out_scale %.4g bf16_out %d twin_out %d  |out| max %.4g mean %.4g bad %zu\n", net.layers[ops[i].conv].name.c_str(),
-                    ti.scale, to.scale, tp.m[i].out != nullptr, tp.m[i].out8 != nullptr, mx, ne ? sum / ne : 0.0, bad);
-        }
-    }
-    if (net.profiling) {
-        for (int i = 0; i < n; ++i) conv_profile_entry(net, ops[i], sb, nullptr, i > 0);
-        net.last_kernel = fp8 ? "conv_tt<fp8,k3,s1,8x32x96>" : cfg64 ? "conv_tt<" SNCAL_X3_NAME ",k3,s1,12x32x64>" : cfg == 2 ? "conv_tt<" SNCAL_X3_NAME ",k3,s1,4x32x96>" : x3 ? "conv_tt<" SNCAL_X3_NAME ",k3,s1,8x32x96>" : "conv_tt<bf16,k3,s1,8x32x96>";
-        static const bool detail = getenv("SNCAL_PROFILE_DETAIL") != nullptr;      // tuning aid: one profile row per launch kind
-        if (detail) net.last_kernel += fmt("@%d members%s%s%s", n, tp.m[0].res ? "+res" : "", tp.m[0].out ? "+f32" : "", tp.m[0].out8 ? "+twin" : "");
-    }
+    if (d_trace) dump_trace(d_trace, n_trace, trace_file, stream);
     return SNCAL_OK;
 }
 
-int run_conv(sncal_hrnet& net, const Op& op, int sb, char* ws, hipStream_t stream) {
-    const ConvLayer& L = net.layers[op.conv];
-    if (tt_eligible(net, op, sb)) return run_conv_tt(net, &op, 1, (int)(&op - net.ops.data()) * 4096 + sb, sb, ws, stream);
-    ConvParams p;
-    const ConvVariant* bestv = nullptr;
-    size_t best_lds = 0;
-    const int rc = prepare_conv(net, op, sb, ws, p, bestv, best_lds);
-    if (rc) return rc;
-    if (net.x3_generic) {        // bf16x3: the split twin for the two-team convolution that reads this output; fp32 only if somebody reads it
-        bool skip_f32 = false;
-        p.out_twin = producer_twin(net, op.out, sb, ws, &skip_f32);
-        if (p.out_twin && skip_f32) p.out = nullptr;
-    }
-    // tuning aid: SNCAL_CONV_TRACE=<layer name> dumps per-workgroup phase timestamps of that layer's last launch
-    static const char* trace_name = getenv("SNCAL_CONV_TRACE");
-    unsigned long long* d_trace = nullptr; size_t n_trace = 0;
-    if (trace_name && L.name == trace_name) {
-        n_trace = (size_t)8 * ((p.n_work + 7) / 8) * 16;
-        if (hipMalloc(&d_trace, n_trace * 8) == hipSuccess) { (void)hipMemsetAsync(d_trace, 0, n_trace * 8, stream); p.trace = d_trace; }
-    }
-    const bool s2p = net.x3_generic && net.use_s2p && !d_trace && !p.ablate && bestv->ks == 3 && bestv->stride == 2 && bestv->ni == 2 && bestv->g == 3 &&
-                     (bestv->mi == 6 || bestv->mi == 3);
-    if (s2p) {               // the one-member case of the pipelined stride-2 kernel
-        ConvSharedParams sp;
-        memset(&sp, 0, sizeof(sp));
-        sp.p[0] = p; sp.mi[0] = bestv->mi;
-        sp.first[0] = 0;
-        for (int i = 1; i < 4; ++i) sp.first[i] = (unsigned)p.nblk;
-        sp.n = 1;
-        sp.tiles = (unsigned)(p.tiles_x * p.tiles_y * sb);
-        sp.tiles_per_xcd = (sp.tiles + 7) / 8;
-        { const int rc2 = ensure_tickets(&net, stream); if (rc2) return rc2; }
-        const int rc2 = launch_conv_s2p_x3(sp, net.d_tickets + 64, stream);
-        if (rc2) return rc2;
-        if (net.profiling) { conv_profile_entry(net, op, sb, bestv, false); static const bool detail = getenv("SNCAL_PROFILE_DETAIL") != nullptr; if (!detail) net.last_kernel = "conv_s2p<" SNCAL_X3_NAME ",k3,s2>"; }
-        return SNCAL_OK;
-    }
-    bestv->launch(p, dim3(8 * p.per_xcd), best_lds, stream);
-    SNCAL_CHECK_LAUNCH();
-    if (d_trace) {
-        std::vector<unsigned long long> h(n_trace);
-        (void)hipStreamSynchronize(stream);
-        (void)hipMemcpy(h.data(), d_trace, n_trace * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(d_trace);
-        if (FILE* f = fopen(getenv("SNCAL_CONV_TRACE_FILE") ? getenv("SNCAL_CONV_TRACE_FILE") : "conv_trace.bin", "wb")) { fwrite(h.data(), 8, n_trace, f); fclose(f); }
-    }
-    if (net.profiling) conv_profile_entry(net, op, sb, bestv, false);
-    return SNCAL_OK;
-}
-
-// the members of a launch group (independent convs, consecutive ops): one grouped launch when they agree on the kernel
-// variant and that variant has a grouped instantiation; otherwise *done = false and the caller runs them one by one
-int run_conv_group(sncal_hrnet& net, const Op* ops, int n, int sb, char* ws, hipStream_t stream, bool* done) {
-    *done = false;
-    if (n < 2 || n > 3) return SNCAL_OK;
-    {
-        bool all_tt = true;
-        int couts = 0;
-        for (int i = 0; i < n; ++i) {
-            all_tt = all_tt && tt_eligible(net, ops[i], sb) && net.layers[ops[i].conv].fp8_on == net.layers[ops[0].conv].fp8_on;
-            couts += (net.layers[ops[i].conv].cout + TT_COUT - 1) / TT_COUT * TT_COUT;
-            all_tt = all_tt && !(net.layers[ops[i].conv].x3_on && net.layers[ops[i].conv].x3_blk != TT_COUT);
-        }
-        static const bool fp8_singles = getenv("SNCAL_FP8_SINGLES") != nullptr;          // debugging aid
-        bool any_fp8 = false;
-        for (int i = 0; i < n; ++i) any_fp8 = any_fp8 || net.layers[ops[i].conv].fp8_on;
-        bool all_fp8 = true;
-        for (int i = 0; i < n; ++i) all_fp8 = all_fp8 && net.layers[ops[i].conv].fp8_on;
-        // a group that mixes fp8 and bf16 members (layer selection by width) cannot share one launch: *done stays false and the
-        // caller runs the members one by one (run_conv)
-        if (any_fp8 && (!all_fp8 || fp8_singles)) return SNCAL_OK;
-        if (all_tt && couts <= TT_COUT_MAX) {      // (the tables' last 16 floats carry the ticket queue's slots)
-            const int rc = run_conv_tt(net, ops, n, (int)(ops - net.ops.data()) * 4096 + sb, sb, ws, stream);
-            *done = rc == SNCAL_OK;
-            return rc;
-        }
-    }
-    if (ops[0].shared_in) {
-        // the chain-starting stride-2 convolutions of one input tensor (schedule_fuse_section): one launch, tile-major (conv.hpp)
-        if (!net.x3_generic) return SNCAL_OK;                 // (the other engines run them one by one)
-        ConvSharedParams sp;
-        memset(&sp, 0, sizeof(sp));
-        const ConvVariant* vs[3] = {nullptr, nullptr, nullptr};
-        size_t lds_s = 0;
-        unsigned ipt = 0;
-        for (int i = 0; i < n; ++i) {
-            size_t l = 0;
-            const int rc = prepare_conv(net, ops[i], sb, ws, sp.p[i], vs[i], l);
-            if (rc) return rc;
-            bool skip_f32 = false;
-            sp.p[i].out_twin = producer_twin(net, ops[i].out, sb, ws, &skip_f32);
-            if (sp.p[i].out_twin && skip_f32) sp.p[i].out = nullptr;
-            const ConvVariant* v = vs[i];
-            const bool ok = ops[i].in == ops[0].in && v->ks == 3 && v->stride == 2 && v->ni == 2 && v->g == 3 && (v->mi == 6 || v->mi == 3) &&
-                            sp.p[i].tiles_x == sp.p[0].tiles_x && sp.p[i].tiles_y == sp.p[0].tiles_y && sp.p[i].twf == sp.p[0].twf;
-            if (!ok) return SNCAL_OK;                          // *done stays false: one by one
-            sp.mi[i] = v->mi;
-            sp.first[i] = ipt;
-            ipt += (unsigned)sp.p[i].nblk;
-            lds_s = std::max(lds_s, l);
-        }
-        for (int i = n; i < 4; ++i) sp.first[i] = ipt;
-        sp.n = n;
-        sp.tiles = (unsigned)(sp.p[0].tiles_x * sp.p[0].tiles_y * sb);
-        sp.tiles_per_xcd = (sp.tiles + 7) / 8;
-        if (net.use_s2p && !sp.p[0].ablate) {
-            { const int rc2 = ensure_tickets(&net, stream); if (rc2) return rc2; }
-            const int rc2 = launch_conv_s2p_x3(sp, net.d_tickets + 64, stream);
-            if (rc2) return rc2;
-        } else {
-            launch_conv_shared_s2_x3(sp, 8u * sp.tiles_per_xcd * ipt, lds_s, stream);
-            SNCAL_CHECK_LAUNCH();
-        }
-        if (net.profiling) {
-            for (int i = 0; i < n; ++i) conv_profile_entry(net, ops[i], sb, vs[i], i > 0);
-            const Tensor& ti = net.tensors[ops[0].in];
-            net.last_bytes -= (double)(n - 1) * sb * ti.H * ti.W * ti.C * net.esize;      // the members' common input counts once
-            static const bool detail = getenv("SNCAL_PROFILE_DETAIL") != nullptr;
-            if (!detail) net.last_kernel = net.use_s2p ? "conv_s2p_shared<" SNCAL_X3_NAME ",k3,s2>" : "conv_shared_s2<" SNCAL_X3_NAME ",k3,NI2,G3>";     // (its own row: not the first member's variant)
-        }
-        *done = true;
-        return SNCAL_OK;
-    }
+// the members as one grouped launch of their common generic variant
+int run_group(const sncal_hrnet& net, const Launch& e, const Call& c) {
+    const Op* ops = &net.ops[e.op];
+    const int n = e.n;
     ConvGroupParams gp;
     memset(&gp, 0, sizeof(gp));
-    const ConvVariant* v0 = nullptr;
     size_t lds = 0;
     ConvParams mp[3];
     double cost[3];
     for (int i = 0; i < n; ++i) {
-        const ConvVariant* v = nullptr;
-        size_t l = 0;
-        const int rc = prepare_conv(net, ops[i], sb, ws, mp[i], v, l);
-        if (rc) return rc;
-        if (net.x3_generic) {
-            bool skip_f32 = false;
-            mp[i].out_twin = producer_twin(net, ops[i].out, sb, ws, &skip_f32);
-            if (mp[i].out_twin && skip_f32) mp[i].out = nullptr;
-        }
-        if (i == 0) v0 = v;
-        if (v != v0 || !v->launch_group) return SNCAL_OK;
-        lds = std::max(lds, l);
+        conv_params(net, ops[i], c.sb, c.ws, e.m[i], mp[i]);
+        lds = std::max(lds, e.m[i].lds);
         cost[i] = (double)net.layers[ops[i].conv].chunks;            // K-chunks per work item
     }
     int order[3] = {0, 1, 2};
@@ -1643,11 +1854,161 @@ int run_conv_group(sncal_hrnet& net, const Op* ops, int n, int sb, char* ws, hip
         blocks += gp.per_xcd[i];
     }
     gp.n = n;
-    v0->launch_group(gp, dim3(8 * blocks), lds, stream);
+    e.m[0].v->launch_group(gp, dim3(8 * blocks), lds, c.stream);
     SNCAL_CHECK_LAUNCH();
-    if (net.profiling) for (int i = 0; i < n; ++i) conv_profile_entry(net, ops[i], sb, v0, i > 0);
-    *done = true;
     return SNCAL_OK;
+}
+
+// the chain-starting stride-2 convolutions of one input tensor: one launch, tile-major (conv.hpp)
+int run_shared_s2(const sncal_hrnet& net, const Launch& e, const Call& c) {
+    const Op* ops = &net.ops[e.op];
+    const int n = e.n;
+    ConvSharedParams sp;
+    memset(&sp, 0, sizeof(sp));
+    size_t lds = 0;
+    unsigned ipt = 0;
+    for (int i = 0; i < n; ++i) {
+        conv_params(net, ops[i], c.sb, c.ws, e.m[i], sp.p[i]);
+        sp.mi[i] = e.m[i].v->mi;
+        sp.first[i] = ipt;
+        ipt += (unsigned)sp.p[i].nblk;
+        lds = std::max(lds, e.m[i].lds);
+    }
+    for (int i = n; i < 4; ++i) sp.first[i] = ipt;
+    sp.n = n;
+    sp.tiles = (unsigned)(sp.p[0].tiles_x * sp.p[0].tiles_y * c.sb);
+    sp.tiles_per_xcd = (sp.tiles + 7) / 8;
+    launch_conv_shared_s2_x3(sp, 8u * sp.tiles_per_xcd * ipt, lds, c.stream);
+    SNCAL_CHECK_LAUNCH();
+    return SNCAL_OK;
+}
+
+// layer1's seam (a = conv3 of block b, its output read by b = conv1 of block b + 1) or block 0's tail (a = downsample branch, b = conv3)
+int run_bneck(const sncal_hrnet& net, const Launch& e, const Call& c) {
+    const Op& a = net.ops[e.op];
+    const Op& b = net.ops[e.op + 1];
+    const bool tail = e.kind == LK_BNECK_TAIL;
+    const Op& conv3 = tail ? b : a;
+    const Tensor& t_y = net.tensors[conv3.out];
+    BneckPairParams bp;
+    memset(&bp, 0, sizeof(bp));
+    bp.range = net.d_range;
+    bp.h2 = reinterpret_cast<const float*>(c.ws + net.tensors[conv3.in].offset);
+    bp.y = reinterpret_cast<float*>(c.ws + t_y.offset);
+    bp.w3 = net.layers[conv3.conv].d_w_bnp; bp.b3 = net.layers[conv3.conv].d_bias;
+    if (tail) {
+        bp.x0 = reinterpret_cast<const float*>(c.ws + net.tensors[a.in].offset);
+        bp.wds = net.layers[a.conv].d_w_bnp; bp.bds = net.layers[a.conv].d_bias;
+    } else {
+        bp.res = reinterpret_cast<const float*>(c.ws + net.tensors[a.res].offset);
+        bp.h1 = reinterpret_cast<float*>(c.ws + net.tensors[b.out].offset);
+        bp.w1 = net.layers[b.conv].d_w_bnp; bp.b1 = net.layers[b.conv].d_bias;
+    }
+    bp.P = (long long)c.sb * t_y.H * t_y.W;
+    bp.ticket = net.d_tickets + TICKET_SEAM;
+    return launch_bneck_pair_x3(bp, net.n_cus, c.stream);
+}
+
+int run_bblockx3(const sncal_hrnet& net, const Launch& e, const Call& c) {
+    const Op& a = net.ops[e.op];
+    const Op& b = net.ops[e.op + 1];
+    const Tensor& ti = net.tensors[a.in];
+    const Tensor& to = net.tensors[b.out];
+    if (e.split_in) {         // (a helper in front of the launch: not what the profiling events time)
+        const sncal::LaunchEvents armed = sncal::launch_events();
+        sncal::launch_events() = sncal::LaunchEvents{};
+        const int rc = launch_split_f32(c.ws + ti.offset, c.ws + net.tensors[ti.twin].offset, (size_t)c.sb * ti.H * ti.W * ti.C, c.stream, net.d_range);
+        if (rc) return rc;
+        sncal::launch_events() = armed;
+    }
+    BBlockX3Params bp;
+    memset(&bp, 0, sizeof(bp));
+    bp.range = net.d_range;
+    bp.x = c.ws + net.tensors[ti.twin].offset;
+    bp.out_twin = e.m[1].twin ? c.ws + net.tensors[to.twin].offset : nullptr;
+    bp.out = e.m[1].f32 ? reinterpret_cast<float*>(c.ws + to.offset) : nullptr;
+    bp.w1 = net.layers[a.conv].d_w_bbx; bp.b1 = net.layers[a.conv].d_bias;
+    bp.w2 = net.layers[b.conv].d_w_bbx; bp.b2 = net.layers[b.conv].d_bias;
+    bp.N = c.sb; bp.H = ti.H; bp.W = ti.W; bp.out_cstride = to.C; bp.out_coff = b.out_coff;
+    bp.ticket = net.d_tickets + TICKET_BBX3;
+    return launch_bblockx3(bp, c.stream);
+}
+
+int run_bblock48(const sncal_hrnet& net, const Launch& e, const Call& c) {
+    const Op& a = net.ops[e.op];
+    const Op& b = net.ops[e.op + 1];
+    const Tensor& ti = net.tensors[a.in];
+    BBlockParams bp;
+    bp.x = c.ws + ti.offset; bp.out = c.ws + net.tensors[b.out].offset;
+    bp.w1 = net.layers[a.conv].d_w; bp.b1 = net.layers[a.conv].d_bias;
+    bp.w2 = net.layers[b.conv].d_w; bp.b2 = net.layers[b.conv].d_bias;
+    bp.N = c.sb; bp.H = ti.H; bp.W = ti.W; bp.tiles_x = bp.tiles_y = 0; bp.trace = nullptr;
+    bp.ticket = net.d_tickets + TICKET_BB48;
+    return launch_bblock48(bp, c.stream);
+}
+
+int run_upadd(const sncal_hrnet& net, const Launch& e, const Call& c) {
+    const Op& op = net.ops[e.op];
+    const Tensor& to = net.tensors[op.out];
+    UpsampleAddParams p;
+    memset(&p, 0, sizeof(p));
+    p.range = net.d_range;
+    p.base = op.base >= 0 ? c.ws + net.tensors[op.base].offset : nullptr;
+    p.nsrc = op.nsrc;
+    int C0 = to.C;
+    for (int s = 0; s < op.nsrc; ++s) {
+        const Tensor& ts = net.tensors[op.srcs[s]];
+        p.src[s] = c.ws + ts.offset; p.Hs[s] = ts.H; p.Ws[s] = ts.W;
+        p.sy[s] = to.H > 1 ? (float)(ts.H - 1) / (float)(to.H - 1) : 0.f;
+        p.sx[s] = to.W > 1 ? (float)(ts.W - 1) / (float)(to.W - 1) : 0.f;
+        C0 = ts.C;
+    }
+    p.out = e.m[0].f32 ? c.ws + to.offset : nullptr;
+    p.out_twin = e.m[0].twin ? c.ws + net.tensors[to.twin].offset : nullptr;
+    p.N = c.sb; p.H = to.H; p.W = to.W; p.C = C0;
+    p.out_cstride = to.C; p.out_coff = op.out_coff; p.relu = op.relu ? 1 : 0;
+    return launch_upsample_add(net.dtype, p, c.stream);
+}
+
+int run_head(const sncal_hrnet& net, const Launch& e, const Call& c) {
+    const Op& op = net.ops[e.op];
+    const Tensor& to = net.tensors[op.out];
+    HeadParams hp;
+    head_params(net, op, c.sb, hp);
+    hp.direct = c.ws + net.tensors[op.head_direct].offset;
+    for (int s2 = 0; s2 < op.head_nsrc; ++s2) hp.src[s2] = c.ws + net.tensors[op.head_src[s2]].offset;
+    for (int s2 = 0; s2 < op.head_nfold; ++s2) hp.fold[s2] = c.ws + net.tensors[op.head_fold[s2]].offset;
+    hp.logits = reinterpret_cast<float*>(c.ws + to.offset);
+    if (c.dec == DEC_HEAD) {      // log-softmax and the decode's partial maxima in place of the logits
+        int rp, cp;
+        head32_decode_parts(to.H, to.W, &rp, &cp);
+        hp.dec_row = hp.logits; hp.dec_col = hp.logits + (size_t)c.sb * (net.desc.num_classes - 1) * to.H * rp; hp.dec_C = net.desc.num_classes;
+    }
+    if (!net.x3) return launch_head_fused(hp, net.head_m2, c.stream);
+    if (!launch_headx3(hp, c.stream)) { set_error("bf16x3 head: configuration not served by headx3 (set SNCAL_HEADX3=0)"); return SNCAL_ERR_STATE; }
+    SNCAL_CHECK_LAUNCH();
+    return SNCAL_OK;
+}
+
+int run_tail(const sncal_hrnet& net, const Launch& e, const Call& c) {
+    const Tensor& tl = net.tensors[net.ops[e.op].in];
+    const int C = net.desc.num_classes;
+    if (c.dec == DEC_HEAD) {      // the head already holds log-softmax + the tiles' maxima: the decode's second half only
+        int rp, cp;
+        head32_decode_parts(tl.H, tl.W, &rp, &cp);
+        const float* parts = reinterpret_cast<const float*>(c.ws + tl.offset);        // the logits tensor's slot holds them
+        return launch_kp_finish(parts, rp, parts + (size_t)c.sb * (C - 1) * tl.H * rp, cp, C, c.sb, tl.H, tl.W, c.img_h, c.img_w, c.kpts, c.stream);
+    }
+    if (c.dec == DEC_TAIL)
+        return launch_logsoftmax_decode(reinterpret_cast<const float*>(c.ws + tl.offset), tl.C, C, c.sb, tl.H, tl.W, c.img_h, c.img_w, c.heat, c.kpts, c.stream);
+    return launch_softmax_nchw(reinterpret_cast<const float*>(c.ws + tl.offset), tl.C, C, (size_t)c.sb * tl.H * tl.W, (size_t)tl.H * tl.W,
+                               net.desc.head_softmax ? 0 : 1, c.heat, c.stream);
+}
+
+int run_decode(const sncal_hrnet& net, const Call& c) {
+    if (!c.kpts || c.dec != DEC_NONE) return SNCAL_OK;         // no keypoints wanted, or decoded already
+    const Tensor& th = net.tensors[net.t_heat];
+    return sncal_heatmap_decode(c.heat, c.sb, net.desc.num_classes, th.H, th.W, c.img_h, c.img_w, c.kpts, (void*)c.stream);
 }
 
 }  // namespace
@@ -1675,10 +2036,7 @@ extern "C" int sncal_hrnet_create(const sncal_hrnet_desc* desc, int dtype, sncal
     net->dtype = dtype;
     net->ge = dtype == SNCAL_BF16 ? 8 : 4;
     net->esize = dtype == SNCAL_BF16 ? 2 : 4;
-    // bf16x3 engine: the generic kernel too multiplies in split-bf16 arithmetic (x3_t, conv.hpp); SNCAL_X3_GENERIC=0 keeps its exact-fp32 variants
-    net->x3_res_twin = !(getenv("SNCAL_X3_RES_TWIN") && atoi(getenv("SNCAL_X3_RES_TWIN")) == 0);
-    net->x3_generic = net->x3 && !(getenv("SNCAL_X3_GENERIC") && atoi(getenv("SNCAL_X3_GENERIC")) == 0);
-    net->variants = dtype == SNCAL_BF16 ? conv_variants_bf16(&net->nvariants) : net->x3_generic ? conv_variants_x3(&net->nvariants) : conv_variants_f32(&net->nvariants);
+    net->variants = dtype == SNCAL_BF16 ? conv_variants_bf16(&net->nvariants) : net->x3 ? conv_variants_x3(&net->nvariants) : conv_variants_f32(&net->nvariants);
     if (const char* e = getenv("SNCAL_SUBBATCH")) { const int v = atoi(e); if (v > 0) net->subbatch = v; }
     if (const char* e = getenv("SNCAL_FUSED_HEAD")) net->fused_enabled = atoi(e) != 0;
     Builder b(*net);
@@ -1689,7 +2047,7 @@ extern "C" int sncal_hrnet_create(const sncal_hrnet_desc* desc, int dtype, sncal
 
 extern "C" void sncal_hrnet_destroy(sncal_hrnet* net) {
     if (!net) return;
-    for (auto& kv : net->tt_plans) { (void)hipFree(kv.second.items); (void)hipFree(kv.second.first); }
+    drop_layout(*net);
     for (ConvLayer& L : net->layers) { if (L.d_w) (void)hipFree(L.d_w); if (L.d_bias) (void)hipFree(L.d_bias); if (L.d_w_tt) (void)hipFree(L.d_w_tt); if (L.d_w8) (void)hipFree(L.d_w8); if (L.d_w_x3) (void)hipFree(L.d_w_x3); if (L.d_w_bbx) (void)hipFree(L.d_w_bbx); if (L.d_w_bnp) (void)hipFree(L.d_w_bnp); if (L.d_oscale) (void)hipFree(L.d_oscale); }
     for (hipEvent_t e : net->event_pool) (void)hipEventDestroy(e);
     if (net->d_tickets) (void)hipFree(net->d_tickets);
@@ -1915,6 +2273,12 @@ extern "C" int sncal_hrnet_finalize(sncal_hrnet* net) {
         if (rc) return rc;
         std::vector<float>().swap(L.w);
     }
+    if (!net->n_cus) {
+        int dev = 0, cus = 0;
+        SNCAL_CHECK_HIP(hipGetDevice(&dev));
+        SNCAL_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        net->n_cus = cus > 0 ? cus : 256;
+    }
     if (net->x3 && !net->d_range) {
         SNCAL_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->d_range), 2 * sizeof(unsigned)));
         SNCAL_CHECK_HIP(hipMemset(net->d_range, 0, 2 * sizeof(unsigned)));
@@ -1973,6 +2337,21 @@ hipEvent_t next_event(sncal_hrnet& net) {
     }
     return net.event_pool[net.events_used++];
 }
+
+// test instrumentation (sncal_hrnet_plan_tap): copies of the tensors tapped at the ops a launch covered, first sub-batch only, stream-ordered
+int run_taps(const sncal_hrnet& net, const Launch& e, const Call& c) {
+    if (net.taps.empty() || c.b0 != 0) return SNCAL_OK;
+    for (int oi = e.op; oi < e.op + e.n; ++oi)
+        for (const sncal_hrnet::Tap& tp : net.taps) {
+            if (tp.op != oi) continue;
+            const Tensor& tt = net.tensors[tp.tensor];
+            if (tt.first < 0) { set_error("sncal_hrnet_plan_tap: tensor %d is not allocated at this layout", tp.tensor); return SNCAL_ERR_STATE; }
+            const void* src = tt.external_heat ? (const void*)c.heat : (const void*)(c.ws + tt.offset);
+            const size_t nb = (size_t)c.sb * tt.H * tt.W * tt.C * (tt.f32 ? 4 : tt.fp8 ? 1 : net.esize);
+            SNCAL_CHECK_HIP(hipMemcpyAsync(tp.dst, src, nb, hipMemcpyDeviceToDevice, c.stream));
+        }
+    return SNCAL_OK;
+}
 }  // namespace
 
 static int forward_impl(sncal_hrnet* net, const float* d_x, const unsigned char* d_x8, int B, int H, int W, float* d_heat,
@@ -1998,7 +2377,7 @@ extern "C" int sncal_hrnet_set_fp8_layers(sncal_hrnet* net, const char* spec) {
     }
     net->fp8_stages = none ? (1u << 31) : stages;       // bit 31 matches no stage: nothing selected
     net->fp8_widths = widths;
-    net->lay_sb = -1;                                   // twins / lifetimes depend on the selection
+    drop_layout(*net);                                  // twins / lifetimes depend on the selection
     return SNCAL_OK;
 }
 
@@ -2012,9 +2391,9 @@ extern "C" int sncal_hrnet_calibrate_fp8(sncal_hrnet* net, const float* d_x, int
     // keypoints into the (unused) head of the workspace would alias activations: decode into a scratch buffer of our own
     float* d_kp = nullptr;
     SNCAL_CHECK_HIP(hipMalloc((void**)&d_kp, (size_t)B * (net->desc.num_classes - 1) * 3 * 4));
-    net->calibrating = true; net->lay_sb = -1;          // set only around the forward: every exit path below sees it cleared
+    net->calibrating = true; drop_layout(*net);         // set only around the forward: every exit path below sees it cleared
     const int rc = forward_impl(net, d_x, nullptr, B, H, W, nullptr, d_kp, H, W, d_ws, ws_bytes, stream_);
-    net->calibrating = false; net->lay_sb = -1;
+    net->calibrating = false; drop_layout(*net);
     if (rc) { (void)hipFree(d_kp); return rc; }
     std::vector<float> amax(nt);
     SNCAL_CHECK_HIP(hipStreamSynchronize(stream));
@@ -2091,7 +2470,7 @@ extern "C" int sncal_hrnet_plan_op(const sncal_hrnet* net, int idx, sncal_plan_o
         const ConvLayer& L = net->layers[op.conv];
         snprintf(out->name, sizeof(out->name), "%s", L.name.c_str());
         out->cin = L.cin; out->cout = L.cout; out->ksize = L.k; out->stride = L.stride; out->col_off = L.col_off;
-        out->fp8 = L.fp8_on ? 1 : L.x3_on ? 2 : (net->x3_generic && op.type == OP_CONV) ? 3 : 0;
+        out->fp8 = L.fp8_on ? 1 : L.x3_on ? 2 : (net->x3 && op.type == OP_CONV) ? 3 : 0;
     }
     out->res_twin = op.res_twin ? 1 : 0;
     if (idx < (int)net->op_label.size()) snprintf(out->kernel, sizeof(out->kernel), "%s", net->op_label[idx].c_str());
@@ -2126,8 +2505,7 @@ extern "C" int sncal_hrnet_plan_tap(sncal_hrnet* net, int op_idx, int tensor_id,
 // next forward a counter that skips or repeats work.  A network handle is single-stream: forwards of ONE handle issued on two streams
 // at once would share these words (include/sncal.h says so); use one handle per stream (the weights are small against 288 GB).
 static int rearm_tickets(sncal_hrnet* net, hipStream_t stream) {
-    const int rc = ensure_tickets(net, stream);
-    if (rc) return rc;
+    if (!net->d_tickets) SNCAL_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&net->d_tickets), TICKET_WORDS * sizeof(unsigned)));
     SNCAL_CHECK_HIP(hipMemsetAsync(net->d_tickets, 0, TICKET_WORDS * sizeof(unsigned), stream));
     return SNCAL_OK;
 }
@@ -2162,351 +2540,49 @@ static int forward_impl(sncal_hrnet* net, const float* d_x, const unsigned char*
     const int C = net->desc.num_classes;
     rc = rearm_tickets(net, stream);
     if (rc) return rc;
+    if (net->op_label.size() != net->ops.size()) net->op_label.assign(net->ops.size(), std::string());
     for (int b0 = 0; b0 < B; b0 += SB) {
         const int sb = std::min(SB, B - b0);
-        float* heat = d_heat ? d_heat + (size_t)b0 * C * th.H * th.W : reinterpret_cast<float*>(ws + th.offset);
-        bool skip_next = false, decoded = false;
-        bool head_decoded = false;       // the head kernel produced the decode's partial maxima instead of logits
-        int skip_group = 0;                                  // remaining members of a launch group that already ran
-        for (size_t oi = 0; oi < net->ops.size(); ++oi) {
-            const Op& op = net->ops[oi];
-            if (!op_active(*net, op)) continue;
-            auto run_taps = [&]() -> int {                       // test instrumentation: first sub-batch only, stream-ordered copies
-                if (net->taps.empty() || b0 != 0) return SNCAL_OK;
-                for (const sncal_hrnet::Tap& tp : net->taps) {
-                    if (tp.op != (int)oi) continue;
-                    const Tensor& tt = net->tensors[tp.tensor];
-                    if (tt.first < 0) { set_error("sncal_hrnet_plan_tap: tensor %d is not allocated at this layout", tp.tensor); return SNCAL_ERR_STATE; }
-                    const void* src = tt.external_heat ? (const void*)heat : (const void*)(ws + tt.offset);
-                    const size_t nb = (size_t)sb * tt.H * tt.W * tt.C * (tt.f32 ? 4 : tt.fp8 ? 1 : net->esize);
-                    SNCAL_CHECK_HIP(hipMemcpyAsync(tp.dst, src, nb, hipMemcpyDeviceToDevice, stream));
-                }
-                return SNCAL_OK;
-            };
-            if (skip_next) { skip_next = false; rc = run_taps(); if (rc) return rc; continue; }      // second conv of a fused BasicBlock
-            if (skip_group > 0) { --skip_group; rc = run_taps(); if (rc) return rc; continue; }
-            net->last_kernel.clear(); net->last_flops = 0; net->last_bytes = 0;
+        Schedule* s = nullptr;
+        rc = schedule_for(*net, sb, &s);
+        if (rc) return rc;
+        Call c;
+        c.b0 = b0; c.sb = sb; c.ws = ws; c.x = d_x; c.x8 = d_x8;
+        c.heat = d_heat ? d_heat + (size_t)b0 * C * th.H * th.W : reinterpret_cast<float*>(ws + th.offset);
+        c.kpts = d_kpts ? d_kpts + (size_t)b0 * (C - 1) * 3 : nullptr;
+        c.img_h = img_h; c.img_w = img_w;
+        c.dec = !d_heat && d_kpts ? s->dec : DEC_NONE;          // nobody wants the heatmap: the decode runs where the schedule fused it
+        c.stream = stream;
+        for (Launch& e : s->launches) {
             hipEvent_t ev0 = nullptr, ev1 = nullptr;
-            if (net->op_label.size() != net->ops.size()) net->op_label.assign(net->ops.size(), std::string());
-            if (net->profiling == 1 || (net->profiling == 2 && net->op_label[oi] == net->focus)) {
+            if (net->profiling == 1 || (net->profiling == 2 && net->op_label[e.op] == net->focus)) {
                 ev0 = next_event(*net); ev1 = next_event(*net); sncal::launch_events() = sncal::LaunchEvents{ev0, ev1};
             }
-            switch (op.type) {
-                case OP_INPUT:
-                    if (d_x8) rc = launch_u8hwc_to_nhwc(net->dtype, d_x8 + (size_t)b0 * 3 * H * W, ws + net->tensors[op.out].offset, sb, H, W, stream);
-                    else rc = launch_nchw_to_nhwc(net->dtype, d_x + (size_t)b0 * 3 * H * W, ws + net->tensors[op.out].offset, sb, 3, H, W, stream, net->d_range ? net->d_range + 1 : nullptr);
-                    break;
-                case OP_CONV: {
-                    if (op.launch_group >= 0) {              // same-depth convs of the parallel branches: one grouped launch
-                        int n = 1;
-                        while (oi + n < net->ops.size() && net->ops[oi + n].launch_group == op.launch_group && net->ops[oi + n].type == OP_CONV &&
-                               op_active(*net, net->ops[oi + n])) ++n;
-                        bool done = false;
-                        rc = run_conv_group(*net, &net->ops[oi], n, sb, ws, stream, &done);
-                        if (rc) return rc;
-                        if (done) { skip_group = n - 1; break; }
-                    }
-                    // BasicBlock of the 48-channel branch: conv1 + conv2 (+ residual) fused when the next active op
-                    // is its second convolution and both layers carry the (MI = 3, G = 3) packing
-                    const Op* op2 = nullptr;
-                    if (net->fuse_bblock && net->dtype == SNCAL_BF16 && op.relu && op.res < 0 && !op.out_f32 && oi + 1 < net->ops.size()) {
-                        const Op& nx = net->ops[oi + 1];
-                        if (nx.type == OP_CONV && op_active(*net, nx) && nx.in == op.out && nx.res == op.in && nx.relu && !nx.out_f32 &&
-                            nx.out_coff == 0 && op.out_coff == 0) {
-                            const ConvLayer& A = net->layers[op.conv]; const ConvLayer& Bl = net->layers[nx.conv];
-                            auto ok = [&](const ConvLayer& L) { return L.k == 3 && L.stride == 1 && L.cin == 48 && L.cout == 48 && L.cin_phys == 48 &&
-                                                                       L.mi == 3 && L.g == 3 && L.chunks == 2 && L.nblk == 1; };
-                            if (ok(A) && ok(Bl) && net->tensors[op.in].C == 48 && net->tensors[nx.out].C == 48) op2 = &nx;
-                        }
-                    }
-                    // ... and in the bf16x3 engine: conv1 -> mid tile in LDS as hi / lo planes -> conv2 + residual (bblockx3.hip); the mid tensor and
-                    // its twin are not written at all
-                    const Op* opx = nullptr;
-                    if (net->fuse_bbx3 && net->x3 && op.relu && op.res < 0 && !op.out_f32 && oi + 1 < net->ops.size() && net->layers[op.conv].x3_on &&
-                        net->layers[op.conv].d_w_bbx && tt_eligible(*net, op, sb)) {
-                        const Op& nx = net->ops[oi + 1];
-                        if (nx.type == OP_CONV && op_active(*net, nx) && nx.in == op.out && nx.res == op.in && nx.relu && !nx.out_f32 && op.out_coff == 0 &&
-                            net->layers[nx.conv].x3_on && net->layers[nx.conv].d_w_bbx && tt_eligible(*net, nx, sb) && net->tensors[op.in].C == 48 &&
-                            net->tensors[op.in].twin >= 0 && net->tensors[net->tensors[op.in].twin].first >= 0) opx = &nx;
-                    }
-                    // split engines, layer1: conv3 (+ residual, ReLU) of a Bottleneck and conv1 (+ ReLU) of the next one in one pass over the
-                    // pixels (bneckx3.hip): the 256-channel tensor between them is written once (the next residual) and not read back
-                    const Op* opn = nullptr;
-                    const Op* opd = nullptr;        // ... and block 0's tail: this op is the downsample branch, the next one the conv3 that adds it
-                    if ((net->fuse_bneck & 2) && net->x3 && !op.relu && op.res < 0 && !op.out_f32 && op.out_coff == 0 && oi + 1 < net->ops.size() &&
-                        net->layers[op.conv].d_w_bnp && net->layers[op.conv].cout == BNP_WIDE && !net->layers[op.conv].x3_on && op.launch_group < 0) {
-                        const Op& nx = net->ops[oi + 1];
-                        if (nx.type == OP_CONV && op_active(*net, nx) && nx.res == op.out && nx.relu && !nx.out_f32 && nx.out_coff == 0 && nx.launch_group < 0 &&
-                            net->layers[nx.conv].d_w_bnp && net->layers[nx.conv].cout == BNP_WIDE && !net->layers[nx.conv].x3_on &&
-                            net->tensors[op.in].C == BNP_MID && net->tensors[nx.in].C == BNP_MID && net->tensors[nx.out].C == BNP_WIDE &&
-                            net->tensors[op.in].H == net->tensors[nx.in].H && net->tensors[op.in].W == net->tensors[nx.in].W &&
-                            net->tensors[op.out].last_read == (int)oi + 1) {      // nobody else reads the downsample branch
-                            bool skip_a = false;
-                            if (!producer_twin(*net, nx.out, sb, ws, &skip_a)) opd = &nx;
-                        }
-                    }
-                    if ((net->fuse_bneck & 1) && net->x3 && op.relu && op.res >= 0 && !op.out_f32 && op.out_coff == 0 && oi + 1 < net->ops.size() &&
-                        net->layers[op.conv].d_w_bnp && net->layers[op.conv].cout == BNP_WIDE && !net->layers[op.conv].x3_on) {
-                        const Op& nx = net->ops[oi + 1];
-                        const Tensor& t_in = net->tensors[op.in];
-                        const Tensor& t_res = net->tensors[op.res];
-                        const Tensor& t_y = net->tensors[op.out];
-                        if (nx.type == OP_CONV && op_active(*net, nx) && nx.in == op.out && nx.res < 0 && nx.relu && !nx.out_f32 && nx.out_coff == 0 &&
-                            nx.launch_group < 0 && net->layers[nx.conv].d_w_bnp && net->layers[nx.conv].cout == BNP_MID && !net->layers[nx.conv].x3_on &&
-                            t_in.C == BNP_MID && t_res.C == BNP_WIDE && t_y.C == BNP_WIDE && net->tensors[nx.out].C == BNP_MID &&
-                            t_res.H == t_y.H && t_res.W == t_y.W) {
-                            bool skip_a = false, skip_b = false;         // neither output may owe somebody a split twin (they feed generic kernels)
-                            if (!producer_twin(*net, op.out, sb, ws, &skip_a) && !producer_twin(*net, nx.out, sb, ws, &skip_b)) opn = &nx;
-                        }
-                    }
-                    if (opd) {
-                        const Tensor& t_y = net->tensors[opd->out];
-                        BneckPairParams bp;
-                        memset(&bp, 0, sizeof(bp));
-                        bp.range = net->d_range;
-                        bp.h2 = reinterpret_cast<const float*>(ws + net->tensors[opd->in].offset);
-                        bp.x0 = reinterpret_cast<const float*>(ws + net->tensors[op.in].offset);
-                        bp.y = reinterpret_cast<float*>(ws + t_y.offset);
-                        bp.w3 = net->layers[opd->conv].d_w_bnp; bp.b3 = net->layers[opd->conv].d_bias;
-                        bp.wds = net->layers[op.conv].d_w_bnp; bp.bds = net->layers[op.conv].d_bias;
-                        bp.P = (long long)sb * t_y.H * t_y.W;
-                        if (!net->n_cus) {
-                            int dev = 0, cus = 0;
-                            SNCAL_CHECK_HIP(hipGetDevice(&dev));
-                            SNCAL_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-                            net->n_cus = cus > 0 ? cus : 256;
-                        }
-                        rc = ensure_tickets(net, stream);
-                        if (rc) return rc;
-                        bp.ticket = net->d_tickets;
-                        rc = launch_bneck_pair_x3(bp, net->n_cus, stream);
-                        if (net->profiling) {
-                            net->last_kernel = "bneck_tail_ds_x3";
-                            net->last_flops = 2.0 * 2.0 * (double)bp.P * BNP_MID * BNP_WIDE;
-                            net->last_bytes = (double)bp.P * 4.0 * (BNP_MID + BNP_MID + BNP_WIDE) + 2.0 * BNP_W_BYTES;
-                        }
-                        skip_next = true;
-                    } else if (opn) {
-                        const Tensor& t_y = net->tensors[op.out];
-                        BneckPairParams bp;
-                        memset(&bp, 0, sizeof(bp));
-                        bp.range = net->d_range;
-                        bp.h2 = reinterpret_cast<const float*>(ws + net->tensors[op.in].offset);
-                        bp.res = reinterpret_cast<const float*>(ws + net->tensors[op.res].offset);
-                        bp.y = reinterpret_cast<float*>(ws + t_y.offset);
-                        bp.h1 = reinterpret_cast<float*>(ws + net->tensors[opn->out].offset);
-                        bp.w3 = net->layers[op.conv].d_w_bnp; bp.b3 = net->layers[op.conv].d_bias;
-                        bp.w1 = net->layers[opn->conv].d_w_bnp; bp.b1 = net->layers[opn->conv].d_bias;
-                        bp.P = (long long)sb * t_y.H * t_y.W;
-                        if (!net->n_cus) {
-                            int dev = 0, cus = 0;
-                            SNCAL_CHECK_HIP(hipGetDevice(&dev));
-                            SNCAL_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-                            net->n_cus = cus > 0 ? cus : 256;
-                        }
-                        rc = ensure_tickets(net, stream);
-                        if (rc) return rc;
-                        bp.ticket = net->d_tickets;
-                        rc = launch_bneck_pair_x3(bp, net->n_cus, stream);
-                        if (net->profiling) {
-                            net->last_kernel = "bneck_seam_x3";
-                            net->last_flops = 2.0 * 2.0 * (double)bp.P * BNP_MID * BNP_WIDE;
-                            net->last_bytes = (double)bp.P * 4.0 * (BNP_MID + BNP_WIDE + BNP_WIDE + BNP_MID) + 2.0 * BNP_W_BYTES;
-                        }
-                        skip_next = true;
-                    } else if (opx) {
-                        const Tensor& ti = net->tensors[op.in];
-                        const Tensor& to = net->tensors[opx->out];
-                        const sncal::LaunchEvents armed = sncal::launch_events();
-                        sncal::launch_events() = sncal::LaunchEvents{};
-                        if (!twin_written_by_producer(*net, op.in, sb)) {         // the fp32 input's split twin, unless its producer wrote it
-                            rc = launch_split_f32(ws + ti.offset, ws + net->tensors[ti.twin].offset, (size_t)sb * ti.H * ti.W * ti.C, stream, net->d_range);
-                            if (rc) return rc;
-                        }
-                        sncal::launch_events() = armed;
-                        BBlockX3Params bp;
-                        memset(&bp, 0, sizeof(bp));
-                        bp.range = net->d_range;
-                        bp.x = ws + net->tensors[ti.twin].offset;
-                        const bool twin_out = to.twin >= 0 && net->tensors[to.twin].first >= 0 && twin_written_by_producer(*net, opx->out, sb);
-                        bp.out_twin = twin_out ? ws + net->tensors[to.twin].offset : nullptr;
-                        bp.out = (!twin_out || net->need_bf16[opx->out]) ? reinterpret_cast<float*>(ws + to.offset) : nullptr;
-                        bp.w1 = net->layers[op.conv].d_w_bbx; bp.b1 = net->layers[op.conv].d_bias;
-                        bp.w2 = net->layers[opx->conv].d_w_bbx; bp.b2 = net->layers[opx->conv].d_bias;
-                        bp.N = sb; bp.H = ti.H; bp.W = ti.W; bp.out_cstride = to.C; bp.out_coff = opx->out_coff;
-                        rc = ensure_tickets(net, stream);
-                        if (rc) return rc;
-                        bp.ticket = net->d_tickets + 16;
-                        rc = launch_bblockx3(bp, stream);
-                        if (net->profiling) {
-                            net->last_kernel = "bblockx3_fused";
-                            const double px = (double)sb * ti.H * ti.W;
-                            net->last_flops = 2.0 * 2.0 * px * 48 * 48 * 9;
-                            net->last_bytes = px * 48 * 4 * (1.0 + (bp.out_twin ? 1.0 : 0.0) + (bp.out ? 1.0 : 0.0)) + 2.0 * BBX_W_BYTES;
-                        }
-                        skip_next = true;
-                    } else if (op2) {
-                        const Tensor& ti = net->tensors[op.in];
-                        BBlockParams bp;
-                        bp.x = ws + ti.offset; bp.out = ws + net->tensors[op2->out].offset;
-                        bp.w1 = net->layers[op.conv].d_w; bp.b1 = net->layers[op.conv].d_bias;
-                        bp.w2 = net->layers[op2->conv].d_w; bp.b2 = net->layers[op2->conv].d_bias;
-                        bp.N = sb; bp.H = ti.H; bp.W = ti.W; bp.tiles_x = bp.tiles_y = 0; bp.trace = nullptr;
-                        rc = ensure_tickets(net, stream);
-                        if (rc) return rc;
-                        bp.ticket = net->d_tickets + 48;
-                        rc = launch_bblock48(bp, stream);
-                        if (net->profiling) {
-                            net->last_kernel = "bblock48_fused";
-                            const double px = (double)sb * ti.H * ti.W;
-                            net->last_flops = 2.0 * 2.0 * px * 48 * 48 * 9;
-                            net->last_bytes = 2.0 * px * 48 * 2 + 2.0 * 48 * 48 * 9 * 2;
-                        }
-                        skip_next = true;
-                    } else {
-                        rc = run_conv(*net, op, sb, ws, stream);
-                    }
-                    break;
-                }
-                case OP_UPADD: {
-                    const Tensor& to = net->tensors[op.out];
-                    UpsampleAddParams p;
-                    memset(&p, 0, sizeof(p));
-                    p.range = net->d_range;
-                    p.base = op.base >= 0 ? ws + net->tensors[op.base].offset : nullptr;
-                    p.nsrc = op.nsrc;
-                    int C0 = to.C;
-                    for (int s = 0; s < op.nsrc; ++s) {
-                        const Tensor& ts = net->tensors[op.srcs[s]];
-                        p.src[s] = ws + ts.offset; p.Hs[s] = ts.H; p.Ws[s] = ts.W;
-                        p.sy[s] = to.H > 1 ? (float)(ts.H - 1) / (float)(to.H - 1) : 0.f;
-                        p.sx[s] = to.W > 1 ? (float)(ts.W - 1) / (float)(to.W - 1) : 0.f;
-                        C0 = ts.C;
-                    }
-                    p.out = ws + to.offset; p.N = sb; p.H = to.H; p.W = to.W; p.C = C0;
-                    p.out_cstride = to.C; p.out_coff = op.out_coff; p.relu = op.relu ? 1 : 0;
-                    if (net->x3) {
-                        bool skip_f32 = false;
-                        p.out_twin = producer_twin(*net, op.out, sb, ws, &skip_f32);
-                        if (p.out_twin && skip_f32) p.out = nullptr;
-                    }
-                    rc = launch_upsample_add(net->dtype, p, stream);
-                    break;
-                }
-                case OP_SOFTMAX: {
-                    const Tensor& tl = net->tensors[op.in];
-                    // nobody wants the heatmap (predict() / the pipeline): log-softmax and the keypoint decode run fused and the
-                    // (B,C,h,w) tensor is never written; its workspace slot serves as the (much smaller) scratch
-                    static const bool fuse_decode = !(getenv("SNCAL_FUSE_DECODE") && atoi(getenv("SNCAL_FUSE_DECODE")) == 0);
-                    if (head_decoded) {        // head32.hip already holds log-softmax + the tiles' maxima: the decode's second half only
-                        int rp, cp;
-                        head32_decode_parts(tl.H, tl.W, &rp, &cp);
-                        const float* parts = reinterpret_cast<const float*>(ws + tl.offset);        // the logits tensor's slot holds them
-                        rc = launch_kp_finish(parts, rp, parts + (size_t)sb * (C - 1) * tl.H * rp, cp, C, sb, tl.H, tl.W, img_h, img_w,
-                                              d_kpts + (size_t)b0 * (C - 1) * 3, stream);
-                        decoded = true;
-                        if (net->profiling) { net->last_kernel = "kp_finish"; net->last_bytes = (double)head32_decode_scratch(sb, C, tl.H, tl.W); }
-                        break;
-                    }
-                    if (fuse_decode && !d_heat && d_kpts && !net->desc.head_softmax &&
-                        logsoftmax_decode_scratch(sb, C, tl.H, tl.W) <= (size_t)sb * C * th.H * th.W * sizeof(float)) {
-                        rc = launch_logsoftmax_decode(reinterpret_cast<const float*>(ws + tl.offset), tl.C, C, sb, tl.H, tl.W, img_h, img_w,
-                                                      heat, d_kpts + (size_t)b0 * (C - 1) * 3, stream);
-                        decoded = true;
-                        if (net->profiling) { net->last_kernel = "logsoftmax_decode_fused"; net->last_bytes = (double)sb * tl.H * tl.W * tl.C * 4; }
-                        break;
-                    }
-                    rc = launch_softmax_nchw(reinterpret_cast<const float*>(ws + tl.offset), tl.C, C, (size_t)sb * tl.H * tl.W,
-                                             (size_t)tl.H * tl.W, net->desc.head_softmax ? 0 : 1, heat, stream);
-                    break;
-                }
-                case OP_HEAD: {
-                    const Tensor& td = net->tensors[op.head_direct];
-                    const Tensor& to = net->tensors[op.out];
-                    HeadParams hp;
-                    memset(&hp, 0, sizeof(hp));
-                    hp.range = net->d_range;
-                    hp.direct = ws + td.offset; hp.Cd = td.C;
-                    hp.w0 = net->d_hw0; hp.bias0 = net->d_hb0; hp.w1 = net->d_hw1; hp.bias1 = net->d_hb1;
-                    hp.w0_32 = net->d_hw0_32; hp.w1_32 = net->d_hw1_32; hp.ks16 = net->head_ks16;
-                    hp.nsrc = op.head_nsrc;
-                    for (int s2 = 0; s2 < op.head_nsrc; ++s2) {
-                        const Tensor& ts = net->tensors[op.head_src[s2]];
-                        hp.src[s2] = ws + ts.offset; hp.Hs[s2] = ts.H; hp.Ws[s2] = ts.W;
-                        hp.sy[s2] = to.H > 1 ? (float)(ts.H - 1) / (float)(to.H - 1) : 0.f;
-                        hp.sx[s2] = to.W > 1 ? (float)(ts.W - 1) / (float)(to.W - 1) : 0.f;
-                    }
-                    hp.nfold = op.head_nfold; hp.ks1 = net->head_ks1;
-                    for (int s2 = 0; s2 < op.head_nfold; ++s2) {
-                        const Tensor& tf = net->tensors[op.head_fold[s2]];
-                        hp.fold[s2] = ws + tf.offset; hp.Cf[s2] = tf.C; hp.Hf[s2] = tf.H; hp.Wf[s2] = tf.W;
-                        hp.fsy[s2] = to.H > 1 ? (float)(tf.H - 1) / (float)(to.H - 1) : 0.f;
-                        hp.fsx[s2] = to.W > 1 ? (float)(tf.W - 1) / (float)(to.W - 1) : 0.f;
-                    }
-                    hp.logits = reinterpret_cast<float*>(ws + to.offset);
-                    hp.N = sb; hp.H = to.H; hp.W = to.W; hp.HP = net->head_hp; hp.NQ = net->head_hp / 32; hp.LC = to.C;
-                    {   // nobody wants the heatmap: log-softmax and the decode's maxima inside the head kernel (head32.hip), neither logits nor
-                        // log-probabilities are written; the logits tensor's own workspace slot (alive from here to the softmax op) holds the
-                        // partial maxima instead
-                        static const bool fuse_dec = !(getenv("SNCAL_FUSE_DECODE") && atoi(getenv("SNCAL_FUSE_DECODE")) == 0) &&
-                                                     !(getenv("SNCAL_HEAD_DECODE") && atoi(getenv("SNCAL_HEAD_DECODE")) == 0);
-                        head_decoded = false;
-                        hp.w0_32_lo = net->d_hw0_32l; hp.w1_32_lo = net->d_hw1_32l;
-                        if (fuse_dec && !d_heat && d_kpts && !net->desc.head_softmax && C > 32 && C <= 64 && (net->x3 ? headx3_applies(hp) : head32_applies(hp)) &&
-                            head32_decode_scratch(sb, C, to.H, to.W) <= to.bytes && th.H == to.H && th.W == to.W) {
-                            int rp, cp;
-                            head32_decode_parts(to.H, to.W, &rp, &cp);
-                            hp.dec_row = hp.logits; hp.dec_col = hp.logits + (size_t)sb * (C - 1) * to.H * rp; hp.dec_C = C;
-                            head_decoded = true;
-                        }
-                    }
-                    if (net->x3) {
-                        hp.w0_32_lo = net->d_hw0_32l; hp.w1_32_lo = net->d_hw1_32l;
-                        if (!launch_headx3(hp, stream)) { set_error("bf16x3 head: configuration not served by headx3 (set SNCAL_HEADX3=0)"); return SNCAL_ERR_STATE; }
-                        SNCAL_CHECK_LAUNCH();
-                        rc = SNCAL_OK;
-                    } else
-                    rc = launch_head_fused(hp, net->head_m2, stream);
-                    if (net->profiling) {
-                        net->last_kernel = net->x3 ? "headx3_fused" : "head_fused";
-                        const double px = (double)sb * to.H * to.W;
-                        net->last_flops = 2.0 * px * net->head_hp * (net->head_k + net->head_m2 * 16);
-                        net->last_bytes = px * (td.C * 2 + to.C * 4);
-                        for (int s2 = 0; s2 < op.head_nsrc; ++s2) { const Tensor& ts = net->tensors[op.head_src[s2]]; net->last_bytes += (double)sb * ts.H * ts.W * ts.C * 2; }
-                        for (int s2 = 0; s2 < op.head_nfold; ++s2) { const Tensor& tf = net->tensors[op.head_fold[s2]]; net->last_bytes += (double)sb * tf.H * tf.W * tf.C * 2; }
-                    }
-                    break;
-                }
-                case OP_DECODE:
-                    if (d_kpts && !decoded) rc = sncal_heatmap_decode(heat, sb, C, th.H, th.W, img_h, img_w, d_kpts + (size_t)b0 * (C - 1) * 3, stream_);
-                    break;
+            switch (e.kind) {
+                case LK_INPUT: rc = run_input(*net, e, c); break;
+                case LK_CONV: rc = run_conv(*net, e, c); break;
+                case LK_TT: rc = run_tt(*net, e, c); break;
+                case LK_GROUP: rc = run_group(*net, e, c); break;
+                case LK_SHARED_S2: rc = run_shared_s2(*net, e, c); break;
+                case LK_BNECK_TAIL: case LK_BNECK_SEAM: rc = run_bneck(*net, e, c); break;
+                case LK_BBLOCKX3: rc = run_bblockx3(*net, e, c); break;
+                case LK_BBLOCK48: rc = run_bblock48(*net, e, c); break;
+                case LK_UPADD: rc = run_upadd(*net, e, c); break;
+                case LK_HEAD: rc = run_head(*net, e, c); break;
+                case LK_TAIL: rc = run_tail(*net, e, c); break;
+                case LK_DECODE: rc = run_decode(*net, c); break;
             }
             if (rc) return rc;
-            rc = run_taps();
+            rc = run_taps(*net, e, c);
             if (rc) return rc;
             if (net->profiling) {
                 sncal::LaunchEvents& le = sncal::launch_events();
-                const bool launched = !le.start && !le.stop;          // the op's launch consumed the pair
+                const bool launched = !le.start && !le.stop;          // the launch consumed the pair
                 le = sncal::LaunchEvents{};
                 if (!launched || !ev0 || !ev1) continue;
-                if (net->last_kernel.empty()) {
-                    const char* names[] = {"nchw_to_nhwc", "conv", "upsample_add", "softmax_nchw", "kp_decode", "head_fused"};
-                    net->last_kernel = names[op.type];
-                    if (op.type == OP_UPADD) {
-                        const Tensor& to = net->tensors[op.out];
-                        double b = 0;
-                        for (int s2 = 0; s2 < op.nsrc; ++s2) { const Tensor& ts = net->tensors[op.srcs[s2]]; b += (double)sb * ts.H * ts.W * ts.C * net->esize; }
-                        const int C0 = op.nsrc ? net->tensors[op.srcs[0]].C : to.C;
-                        net->last_bytes = b + (double)sb * to.H * to.W * C0 * net->esize * (op.base >= 0 ? 2 : 1);
-                    } else if (op.type == OP_SOFTMAX || op.type == OP_DECODE) {
-                        net->last_bytes = (double)sb * C * th.H * th.W * 4 * (op.type == OP_SOFTMAX ? 2 : 1);
-                    } else if (op.type == OP_INPUT) {
-                        net->last_bytes = (double)sb * H * W * (3 * 4 + net->ge * net->esize);
-                    }
-                }
-                if (op.type == OP_DECODE && (!d_kpts || decoded)) continue;
-                if (net->profiling == 1) net->op_label[oi] = net->last_kernel;
-                net->intervals.push_back({ev0, ev1, net->last_kernel, net->last_flops, net->last_bytes});
+                const Prof& pr = e.kind == LK_TAIL && c.dec != DEC_NONE ? e.prof_kp : e.prof;
+                if (net->profiling == 1) net->op_label[e.op] = pr.kernel;
+                net->intervals.push_back({ev0, ev1, pr.kernel, pr.flops, pr.bytes});
             }
         }
     }

@@ -213,8 +213,9 @@ static inline int grid_for(size_t items) {
     return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
-int launch_nchw_to_nhwc(int dtype, const float* x, void* y, int N, int C, int H, int W, hipStream_t s, unsigned* nonfinite) {
+int launch_nchw_to_nhwc(int dtype, const float* x, void* y, int N, int C, int H, int W, hipStream_t s, unsigned* range) {
     const size_t total = (size_t)N * H * W;
+    unsigned* nonfinite = range ? range + 1 : nullptr;      // (the kernel counts into nonfinite[0] and the overflow word nonfinite[-1])
     if (dtype == SNCAL_BF16)
         SNCAL_LAUNCH(nchw_to_nhwc_kernel<__bf16>, dim3(grid_for((size_t)H * W), N), dim3(256), 0, s, x, (__bf16*)y, N, C, H, W, nonfinite);
     else

@@ -23,7 +23,8 @@ struct UpsampleAddParams {
                              // out may then be null
 };
 
-int launch_nchw_to_nhwc(int dtype, const float* x, void* y, int N, int C, int H, int W, hipStream_t s, unsigned* nonfinite = nullptr);   // nonfinite: counter of NaN / inf inputs, or null
+// range: the network's range flag (hrnet.cpp d_range) -- [0] counts frame values beyond fp16's 65504, [1] NaN / infinite ones -- or null
+int launch_nchw_to_nhwc(int dtype, const float* x, void* y, int N, int C, int H, int W, hipStream_t s, unsigned* range = nullptr);
 int launch_u8hwc_to_nhwc(int dtype, const unsigned char* x, void* y, int N, int H, int W, hipStream_t s);
 int launch_upsample_add(int dtype, const UpsampleAddParams& p, hipStream_t s);
 int launch_softmax_nchw(const float* logits, int cstride, int C, size_t npix_total, size_t hw, int log_mode,

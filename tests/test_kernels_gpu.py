@@ -391,7 +391,7 @@ def _split_twin_value(raw):
 
 
 def _producer_twin(net, op, taps):
-    """fp16x3: does this generic convolution / fuse sum write the split twin of its (dense) output?  (hrnet.cpp producer_twin)"""
+    """fp16x3: does this generic convolution / fuse sum write the split twin of its (dense) output?  (hrnet.cpp writes_twin)"""
     to = net.plan_tensor(op['out'])
     if to['twin'] < 0 or not net.plan_tensor(to['twin'])['alive'] or (op['idx'], to['twin']) not in taps:
         return False
@@ -549,7 +549,7 @@ def test_every_launch_of_the_fp16x3_engine_w48_540p(sncal, cuda, monkeypatch, sm
     branch as fused BasicBlocks, bblockx3.hip) in split-fp16 arithmetic -- each against torch fp32 on the
     split twin it reads (hi + lo; written by the producing convolution's epilogue or by split_f32_kernel), its fp32 output and the
     split twin it hands on.  Twice: three frames are a SMALL launch and take the two-team kernel's 96 x 4 x 32 tile by default
-    (SNCAL_TT_SMALL_ITEMS = 2 items per team, hrnet.cpp run_conv_tt); 0 forces the 96 x 8 x 32 tile of the large batches."""
+    (SNCAL_TT_SMALL_ITEMS = 2 items per team, hrnet.cpp tt_cfg); 0 forces the 96 x 8 x 32 tile of the large batches."""
     monkeypatch.setenv('SNCAL_TT_SMALL_ITEMS', small_items)
     sd = _weights('hrnet_w48')
     stats = verify_plan(sncal, cuda, 'hrnet_w48', sd, _frames(3, 540, 960, 18, cuda), 'fp16x3', tag='w48 540p fp16x3 small tile ' + small_items)
@@ -561,17 +561,6 @@ def test_every_launch_of_the_fp16x3_engine_w48_540p(sncal, cuda, monkeypatch, sm
     # layer1 (bneckx3.hip): block 0's conv3 with its downsample branch inside, and the seams conv3 + next conv1 of blocks 1 | 2 and 2 | 3
     # (two checks each: the 256-channel block output and the next block's 64-channel conv1 output)
     assert n('bneck_tail_ds_x3') == 1 and n('bneck_seam_x3') == 4, {k: v.get('ops') for k, v in stats.items()}
-
-
-def test_every_launch_of_the_fp16x3_engine_with_the_pipelined_stride2_kernel(sncal, cuda, monkeypatch):
-    """SNCAL_S2P=1: the 3x3 stride-2 convolutions (transitions and fuse-down chains, hrnet.py:183-214, 357-391) on the pipelined
-    persistent kernel (conv_s2p.hip; parked: measured slower than the generic kernel, off by default) -- every launch against torch fp32
-    like the default path, at W48 540p (96- and 48-channel n-blocks, shared launches) and W32 270p."""
-    monkeypatch.setenv('SNCAL_S2P', '1')
-    stats = verify_plan(sncal, cuda, 'hrnet_w48', _weights('hrnet_w48'), _frames(3, 540, 960, 18, cuda), 'fp16x3', tag='w48 540p fp16x3 s2p')
-    n = lambda key: sum(v.get('ops', 0) for k, v in stats.items() if k.startswith(key))
-    assert n('conv_s2p<') >= 20 and n('conv_s2p_shared<') >= 8, {k: v.get('ops') for k, v in stats.items()}      # (members of a shared launch carry the first member's label)
-    verify_plan(sncal, cuda, 'hrnet_w32', _weights('hrnet_w32'), _frames(2, 270, 480, 19, cuda), 'fp16x3', tag='w32 270p fp16x3 s2p')     # (whichever of its stride-2 layers pack at G = 3)
 
 
 def test_every_launch_of_the_fp16x3_engine_w32_270p(sncal, cuda):
