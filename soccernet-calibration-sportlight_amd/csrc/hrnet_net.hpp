@@ -1,0 +1,241 @@
+// Internal header of the HRNet host side: the plan's data (layers, ops, tensors, launch schedule, struct sncal_hrnet) and the functions
+// with which its stages call each other (below; hrnet.cpp, the executor and C ABI, calls them).  Included by the hrnet*.cpp units only.
+#pragma once
+#include "common.hpp"
+#include "conv.hpp"
+#include "ops.hpp"
+#include "head.hpp"
+#include "bblock.hpp"
+#include "bblockx3.hpp"
+#include "bneckx3.hpp"
+#include "x3.hpp"
+#include "conv_tt.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+namespace sncal {
+
+struct ConvLayer {
+    std::string name, bn;
+    int cin, cout, k, stride;
+    bool bias;
+    // host weights (BN folded on set)
+    std::vector<float> w, scale, shift;
+    bool is_set = false;
+    // packing / dispatch
+    int cin_phys = 0, mi = 0, g = 0, chunks = 0, nblk = 0, cout_frags = 0;
+    void* d_w = nullptr;
+    float* d_bias = nullptr;
+    void* d_w_tt = nullptr;     // second packing, for the two-team kernel (conv_tt.hip): 32 x 32 x 16 MFMA fragment order
+    // C5 path: e4m3 weights of the same layer for conv_tt_kernel<true> (one scale per output channel), the scales, and
+    // oscale = (calibrated scale of the layer's input tensor) x (weight scale of the channel)
+    void* d_w8 = nullptr;
+    std::vector<float> wscale;
+    float* d_oscale = nullptr;
+    int stage = 0;              // 2..4 for model.stageN.* layers, 0 otherwise
+    bool fp8_on = false;
+    void* d_w_x3 = nullptr;     // bf16x3 engine: hi / lo split weights in the two-team kernel's fragment order (16-channel stages)
+    int x3_blk = TT_COUT;       // ... packed in output-channel blocks of 96 (tile 96 x 8 x 32) or, for widths that are no multiple of 96, 64 (64 x 12 x 32)
+    bool x3_on = false;
+    void* d_w_bbx = nullptr;    // bf16x3 engine, 48 -> 48 3x3 layers: pair-step packing of the fused BasicBlock (bblockx3.hip)
+    void* d_w_bnp = nullptr;    // split engines, layer1's 1x1 layers (64 -> 256, 256 -> 64): A fragments of the fused Bottleneck seam (bneckx3.hip)
+    // internal layers of the fused head: t_i = W0[:, col_off : col_off + cin] . branch_i  (derived at finalize)
+    bool derived = false;
+    int col_off = 0;
+    bool derived_shift = false;     // the slice that also carries last_layer.0's folded-BN shift (split head: the direct tensor's)
+};
+
+enum OpType { OP_INPUT, OP_CONV, OP_UPADD, OP_SOFTMAX, OP_DECODE, OP_HEAD };
+enum OpGroup { GRP_ALL = 0, GRP_UNFUSED = 1, GRP_FUSED = 2, GRP_SPLIT = 3 };   // head variants living side by side in the plan
+
+struct Op {
+    OpType type;
+    int conv = -1;
+    int in = -1, out = -1, res = -1;
+    bool relu = false;
+    int out_coff = 0;
+    bool out_f32 = false;
+    bool res_twin = false;       // bf16x3: the residual is read from res's split twin (set by layout())
+    int base = -1, srcs[4] = {-1, -1, -1, -1}, nsrc = 0;
+    int dims_from = -1, dims_mul = 1;     // UPADD without base: out dims = dims(dims_from) * dims_mul
+    int group = GRP_ALL;
+    int launch_group = -1;                // >= 0: independent convs that may share one grouped launch (consecutive ops)
+    bool shared_in = false;               // ... and all members read the SAME input tensor with stride 2 (conv_shared_s2_kernel)
+    int head_direct = -1, head_src[HEAD_MAX_SRC] = {-1, -1, -1, -1, -1}, head_nsrc = 0;   // OP_HEAD
+    int head_fold[HEAD_MAX_FOLD] = {-1, -1}, head_nfold = 0;                              // OP_HEAD: branches folded into stage-1 K
+};
+
+struct Tensor {
+    int C = 0;
+    bool f32 = false;         // fp32 storage regardless of the net dtype (logits / heat)
+    bool external_heat = false;
+    bool fp8 = false;            // e4m3 twin (1 byte per element) of a bf16 tensor, input of an fp8 convolution
+    bool split = false;          // bf16x3 engine: split twin ([16 hi | 16 lo] bf16 per 16-channel group = 4 bytes per element) of an fp32 tensor
+    int twin = -1;               // index of this tensor's fp8 twin, if any
+    float scale = 0.f;           // calibrated per-tensor scale of the twin: amax / 448
+    int first = -1, last = -1;   // producing / last consuming op, as the allocator sees them (extended over launch groups and fusable pairs)
+    int last_read = -1;          // the op that really reads the tensor last (what a fusion's "nobody else reads it" test asks)
+    // per-run
+    int H = 0, W = 0;
+    size_t offset = 0, bytes = 0;
+};
+
+// ---- launch schedule: which kernel runs which ops, decided once per (layout, sub-batch size) -------------------------
+enum LaunchKind {
+    LK_INPUT,        // NCHW fp32 / HWC u8 frames -> NHWC
+    LK_CONV,         // one convolution on the generic kernel (conv.hpp)
+    LK_TT,           // one to three independent convolutions on the two-team kernel (conv_tt.hip)
+    LK_GROUP,        // two or three independent convolutions as one grouped launch of the generic kernel
+    LK_SHARED_S2,    // the chain-starting stride-2 convolutions of one input tensor as one launch (conv_shared_s2_kernel)
+    LK_BNECK_TAIL,   // layer1 block 0: downsample branch + conv3 (bneckx3.hip)
+    LK_BNECK_SEAM,   // layer1: conv3 of a Bottleneck + conv1 of the next (bneckx3.hip)
+    LK_BBLOCKX3,     // 48-channel BasicBlock in split arithmetic (bblockx3.hip)
+    LK_BBLOCK48,     // 48-channel BasicBlock, bf16 (bblock.hip)
+    LK_UPADD,        // upsample + add (ops.hip)
+    LK_HEAD,         // fused head (head.hip / head32.hip / headx3.hip)
+    LK_TAIL,         // softmax, or the part of the keypoint decode fused with it
+    LK_DECODE,       // keypoint decode (decode.hip)
+};
+enum DecodeAt { DEC_NONE, DEC_HEAD, DEC_TAIL };    // where the keypoint decode runs when a call wants keypoints only
+
+struct Member {                     // what the schedule resolved for one op a launch covers
+    const ConvVariant* v = nullptr; // generic kernel: variant, tile width factor, tiles, dynamic LDS bytes, LDS-transposed epilogue
+    int twf = 1, tiles_x = 0, tiles_y = 0;
+    size_t lds = 0;
+    bool epi_lds = false;
+    bool twin = false, f32 = true;  // the launch writes the output's split twin / the output itself
+};
+struct TTPlanDev { TTItem* items = nullptr; uint32_t* first = nullptr; int n_wgs = 0; int lazy = 0; int cfg = 0; };
+struct Prof { std::string kernel; double flops = 0, bytes = 0; };
+struct Launch {
+    LaunchKind kind = LK_CONV;
+    int op = 0, n = 1;              // covers the ops [op, op + n), all active
+    Member m[3];
+    bool split_in = false;          // LK_BBLOCKX3: the input's split twin is made in front of the launch
+    TTPlanDev plan;                 // LK_TT: work lists (cfg set by the schedule, uploaded by the first launch)
+    Prof prof, prof_kp;             // profile row; LK_TAIL: prof_kp when the call wants keypoints only
+};
+struct Schedule { int sb = 0; DecodeAt dec = DEC_NONE; std::vector<Launch> launches; };
+
+}  // namespace sncal
+
+struct sncal_hrnet {
+    sncal_hrnet_desc desc;
+    int dtype;
+    int ge;          // elements per 16-byte k-group
+    int esize;
+    std::vector<sncal::ConvLayer> layers;
+    std::map<std::string, int> layer_by_name;
+    std::vector<sncal::Op> ops;
+    std::vector<sncal::Tensor> tensors;
+    int t_heat = -1, t_kpts_src = -1;
+    int n_public = 0;                 // layers [0, n_public) are the reference's convs; the rest are internal
+    int t_stem = -1, t_branch0 = -1;  // tensors whose dims decide whether the fused head applies
+    int l_head0 = -1, l_head1 = -1;   // last_layer.0 / last_layer.3
+    int head_direct_coff = 0, head_direct_c = 0, head_hp = 0, head_m2 = 0;
+    int head_k = 0, head_ks1 = 2;     // stage-1 K of the fused head (direct + folded branch channels), its k-steps
+    bool fused_enabled = true, use_fused = false;
+    // exact-fp32 engine: the head in its restructured form (per-source 1x1 products at native resolution, one bilinear sum) on the
+    // generic fp32 kernels -- the 784 -> 784 product at 270x480 (31 % of the reference's MACs) shrinks ninefold
+    bool has_split = false, use_split = false;
+    // wide 3x3 stride-1 convolutions (96 / 192 / 384 channels) on the two-team persistent kernel (conv_tt.hip), bf16 path
+    bool use_conv_tt = getenv("SNCAL_CONV_TT") ? atoi(getenv("SNCAL_CONV_TT")) != 0 : true;
+    std::vector<sncal::Schedule> schedules;      // per sub-batch size at the current layout (SB and the last sub-batch's), dropped with the layout
+    int n_cus = 0;                        // compute units of the device (queried at finalize)
+    // C5: fp8 (OCP e4m3) arithmetic for the wide 3x3 stride-1 convolutions, everything else as the bf16 engine
+    bool fp8 = false, fp8_calibrated = false, calibrating = false;
+    // SNCAL_BF16X3: the fp32 engine with split-bf16 arithmetic in the 3x3 stride-1 convolutions of stages 2-4 and in the generic
+    // convolutions (x3_t variants: packed weights [4 hi | 4 lo] per k-group); residuals of the two-team convolutions come from split twins
+    bool x3 = false;
+    unsigned fp8_stages = 0;                  // bit s: stage s selected (0 = all stages)
+    std::vector<int> fp8_widths;              // selected channel widths (empty = all)
+    unsigned* d_amax = nullptr;               // calibration: per-tensor max |x| (float bit patterns)
+    std::vector<char> need_bf16;              // per tensor: some active consumer reads the bf16 tensor
+    std::vector<int> producer;                // per tensor: active op that writes it
+    bool fuse_bblock = getenv("SNCAL_FUSE_BBLOCK") ? atoi(getenv("SNCAL_FUSE_BBLOCK")) != 0 : true;   // 48-channel BasicBlocks as one kernel (bblock.hip), bf16 path
+    // split engines, layer1 (bneckx3.hip): bit 0 = conv3 of a Bottleneck + conv1 of the next as one pass, bit 1 = block 0's downsample branch inside its conv3
+    int fuse_bneck = getenv("SNCAL_FUSE_BNECK") ? atoi(getenv("SNCAL_FUSE_BNECK")) : 3;
+    void *d_hw0 = nullptr, *d_hw1 = nullptr;
+    void *d_hw0_32 = nullptr, *d_hw1_32 = nullptr;      // head32.hip packing (null when K1 is not a multiple of 16)
+    void *d_hw0_32l = nullptr, *d_hw1_32l = nullptr;    // bf16x3 engine (headx3.hip): lo parts of the split weights; d_hw0_32 / d_hw1_32 then hold the hi parts
+    int head_ks16 = 0;
+    float *d_hb0 = nullptr, *d_hb1 = nullptr;
+    int cur_group = sncal::GRP_ALL;
+    bool finalized = false;
+    bool equalize = true;        // fp16x3: rebalance block-internal channels by powers of two at finalize (equalize_blocks)
+    bool equalize_done = false;  // ... already applied to the weights held now (re-armed by sncal_hrnet_set_conv)
+    int equalized = 0;           // channels moved by the last equalize_blocks
+    int subbatch = 64;
+    const sncal::ConvVariant* variants = nullptr;
+    int nvariants = 0;
+    // cached per-(sb,H,W) layout
+    int lay_sb = -1, lay_h = -1, lay_w = -1;
+    size_t lay_bytes = 0;
+    // profiling (sncal_hrnet_set_profiling): events recorded between launches + what each interval ran
+    int profiling = 0;                    // 0 off, 1 every launch, 2 only the launches of `focus` (labels cached per op by a mode-1 run)
+    std::string focus;
+    int n_launch_groups = 0;
+    std::vector<std::string> op_label;
+    struct Interval { hipEvent_t e0, e1; std::string kernel; double flops, bytes; };
+    std::vector<Interval> intervals;
+    std::vector<hipEvent_t> event_pool;
+    size_t events_used = 0;
+    // work tickets of the persistent kernels that deal their work dynamically (TICKET_*): zeroed words, re-armed by the kernels
+    // themselves; launches of one network are ordered on its stream, so they share the words
+    unsigned* d_tickets = nullptr;
+    // range flag of the split-fp16 engine (x3.hpp x3_report): [0] wavefronts that split a value beyond +-65504, [1] workgroups of the
+    // layout kernel that met a NaN / infinite input value.  Sticky until sncal_hrnet_range_status(clear = 1); allocated at finalize
+    unsigned* d_range = nullptr;
+    // test instrumentation (sncal_hrnet_plan_tap): copies of plan tensors taken while the executor passes an op
+    struct Tap { int op, tensor; void* dst; };
+    std::vector<Tap> taps;
+};
+
+namespace sncal {
+
+inline std::string fmt(const char* f, ...) {
+    char buf[256];
+    va_list ap;
+    va_start(ap, f);
+    vsnprintf(buf, sizeof(buf), f, ap);
+    va_end(ap);
+    return buf;
+}
+
+// ticket words of a network: the first word of each kernel's own range
+constexpr int TICKET_SEAM = 0;       // layer1's seams and block 0's tail (bneckx3.hip)
+constexpr int TICKET_BBX3 = 16;      // fused BasicBlock, split arithmetic (bblockx3.hip)
+constexpr int TICKET_TT = 32;        // two-team kernel (conv_tt.hip)
+constexpr int TICKET_BB48 = 48;      // fused BasicBlock, bf16 (bblock.hip)
+constexpr int TICKET_WORDS = 96;
+
+// the head variants live side by side in the plan: is this op part of the variant the current layout chose?
+inline bool op_active(const sncal_hrnet& net, const Op& op) {
+    const int head = net.use_fused ? GRP_FUSED : net.use_split ? GRP_SPLIT : GRP_UNFUSED;
+    return op.group == GRP_ALL || op.group == head;
+}
+
+// ---- the stages: one unit each, what the others call of it, when it runs --------------------------------------------
+// hrnet_graph.cpp: the op graph of a network (sncal_hrnet_create)
+bool build_graph(sncal_hrnet& net);
+// hrnet_weights.cpp: balance, packing and upload of the weights (sncal_hrnet_finalize), release of the packed buffers
+int equalize_blocks(sncal_hrnet& net);
+int pack_weights(sncal_hrnet& net);
+void release_weights(sncal_hrnet& net);
+// hrnet_layout.cpp: head variant, shapes, lifetimes, workspace offsets (per sub-batch, H, W)
+int layout(sncal_hrnet& net, int sb, int H, int W);
+void drop_layout(sncal_hrnet& net);
+// hrnet_schedule.cpp: which kernel runs which ops (per layout and sub-batch size), and the predicates layout and launches share
+bool tt_eligible(const sncal_hrnet& net, const Op& op, int sb);
+bool twin_written_by_producer(const sncal_hrnet& net, int t, int sb);
+void tt_outputs(const sncal_hrnet& net, const Op& op, int sb, bool* out, bool* twin);
+void head_params(const sncal_hrnet& net, const Op& op, int sb, HeadParams& hp);
+int schedule_for(sncal_hrnet& net, int sb, Schedule** out);
+
+}  // namespace sncal

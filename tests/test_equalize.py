@@ -1,4 +1,4 @@
-"""CPU: the fp16x3 engine's load-time rebalancing of block-internal channels (sncal_hrnet_equalize, csrc/hrnet.cpp equalize_blocks)
+"""CPU: the fp16x3 engine's load-time rebalancing of block-internal channels (sncal_hrnet_equalize, csrc/hrnet_weights.cpp equalize_blocks)
 against a numpy restatement of its rule, through the C ABI without a GPU (sncal_hrnet_create / set_conv / equalize / get_conv are host
 only).  No reference counterpart: the reference's predict() is fp32 (src/models/hrnet/metamodel.py:127-134); what the step must
 preserve is the reference's FUNCTION -- producer row c x 2^-l and consumer column c x 2^l is the same fp32 network bit for bit

@@ -391,7 +391,7 @@ def _split_twin_value(raw):
 
 
 def _producer_twin(net, op, taps):
-    """fp16x3: does this generic convolution / fuse sum write the split twin of its (dense) output?  (hrnet.cpp writes_twin)"""
+    """fp16x3: does this generic convolution / fuse sum write the split twin of its (dense) output?  (hrnet_schedule.cpp writes_twin)"""
     to = net.plan_tensor(op['out'])
     if to['twin'] < 0 or not net.plan_tensor(to['twin'])['alive'] or (op['idx'], to['twin']) not in taps:
         return False
@@ -549,7 +549,7 @@ def test_every_launch_of_the_fp16x3_engine_w48_540p(sncal, cuda, monkeypatch, sm
     branch as fused BasicBlocks, bblockx3.hip) in split-fp16 arithmetic -- each against torch fp32 on the
     split twin it reads (hi + lo; written by the producing convolution's epilogue or by split_f32_kernel), its fp32 output and the
     split twin it hands on.  Twice: three frames are a SMALL launch and take the two-team kernel's 96 x 4 x 32 tile by default
-    (SNCAL_TT_SMALL_ITEMS = 2 items per team, hrnet.cpp tt_cfg); 0 forces the 96 x 8 x 32 tile of the large batches."""
+    (SNCAL_TT_SMALL_ITEMS = 2 items per team, hrnet_schedule.cpp tt_cfg); 0 forces the 96 x 8 x 32 tile of the large batches."""
     monkeypatch.setenv('SNCAL_TT_SMALL_ITEMS', small_items)
     sd = _weights('hrnet_w48')
     stats = verify_plan(sncal, cuda, 'hrnet_w48', sd, _frames(3, 540, 960, 18, cuda), 'fp16x3', tag='w48 540p fp16x3 small tile ' + small_items)
