@@ -406,6 +406,26 @@ int sncal_jpeg_decode(sncal_jpeg* dec, const unsigned char* const* data, const s
 int sncal_create_target(const float* d_kpts, int B, int N, float sigma, int h, int w, float* d_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Validation loss, fused: one read of the heatmap, the target rebuilt on the fly (never written)
+ * replaces HRNetLoss.forward for num_refinement_stages = 0        src/models/hrnet/loss.py:89-119, 129-144
+ *   d_logp (B,N+1,h,w) fp32 log-probabilities (the forward's heat output)
+ *   d_kpts (B,N,3) fp32 [x, y, flag] in IMAGE pixels, as the dataset yields them: x and y are divided by `stride` in fp32 here
+ *          (loss.py:92) and the visibility test any(keypoints == 1) runs on the divided values
+ *   d_mask (B,N+1) fp32 or NULL; multiplied into prediction and target (loss.py:94-103): a channel with mask 0 has exp(0) = 1
+ *          against target 0
+ *   terms  bit0 MSE sum of (exp(p) - t)^2, bit1 KL sum of xlogy(t, t) - t*p, bit2 adaptive wing (alpha 2.1, omega 14, epsilon 1,
+ *          theta 0.5); terms whose bit is clear are not computed and come back 0
+ *   d_out  (B,3) fp64: per-frame SUMS over (N+1)*h*w of the three terms.  The caller weighs and divides:
+ *          l2_w * S_mse / (B*(N+1)*h*w) + kldiv_w * S_kl / B + awing_w * S_awing / (B*(N+1)*h*w)
+ *   d_ws   caller-owned scratch of sncal_heatmap_loss_workspace bytes, 16-byte aligned (SNCAL_ERR_WORKSPACE when short)
+ * N <= 64.  Deterministic: no atomics, partial sums are folded in a fixed order, two runs give the same bits.  Asynchronous on
+ * `stream`; the library allocates nothing.
+ * ---------------------------------------------------------------------------------------------- */
+int sncal_heatmap_loss_workspace(int B, int N, int h, int w, size_t* bytes);
+int sncal_heatmap_loss(const float* d_logp, const float* d_kpts, const float* d_mask, int B, int N, int h, int w, float sigma,
+                       float stride, int terms, double* d_out, void* d_ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pipeline plumbing: a stream confined to `cus_per_xcd` compute units of each XCD (for the camera solves)
  * replaces the 16-process CPU pool of make_submit.py:25,53-54,69 (ProcessPoolExecutor workers beside the GPU loop): the solves of
  * up to four batches run beside the network on these streams; what they may occupy is bounded by the mask instead of by a process

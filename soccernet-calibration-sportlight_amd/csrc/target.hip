@@ -10,17 +10,16 @@
 // N*(w + h) per frame instead of N*w*h, and every store instruction writes 1 KB of one channel row.
 // The arithmetic is fp32 step by step as torch evaluates it; exp is float32(exp(float64)), i.e. correctly rounded
 // (torch's CPU exp is within 1 ulp of that: tests/test_target_gpu.py).
+// gauss1 and the visibility test live in gauss.hpp, shared with the fused loss (loss.hip) so the two cannot drift.
 #include "common.hpp"
+#include "gauss.hpp"
 #include "../../include/sncal.h"
 
 namespace {
 
-constexpr int TG_ROWS = 32, TG_MAXN = 64;
+using sncal::gauss1;
 
-__device__ __forceinline__ float gauss1(float x, float mu, float sigma) {
-    const float d = (x - mu) / sigma;                 // torch.div(x - mu, sigma)
-    return (float)exp((double)(-(d * d) / 2.0f));     // exp(-(d ** 2) / 2.0)
-}
+constexpr int TG_ROWS = 32, TG_MAXN = 64;
 
 __global__ __launch_bounds__(256) void create_target_kernel(const float* __restrict__ kp, int N, float sigma, int h, int w,
                                                             float* __restrict__ out) {
@@ -31,7 +30,7 @@ __global__ __launch_bounds__(256) void create_target_kernel(const float* __restr
     const int rows = min(TG_ROWS, h - y0);
     for (int i = t; i < N * 3; i += 256) s_kp[i / 3][i % 3] = kp[((size_t)b * N) * 3 + i];
     __syncthreads();
-    for (int i = t; i < N; i += 256) s_vis[i] = (s_kp[i][0] == 1.0f) | (s_kp[i][1] == 1.0f) | (s_kp[i][2] == 1.0f);
+    for (int i = t; i < N; i += 256) s_vis[i] = sncal::kp_visible(s_kp[i][0], s_kp[i][1], s_kp[i][2]);
     for (int i = t; i < N * TG_ROWS; i += 256) {
         const int n = i / TG_ROWS, r = i - n * TG_ROWS;
         s_gy[n][r] = gauss1((float)(y0 + r), s_kp[n][1], sigma);

@@ -1,6 +1,6 @@
-"""Model surface: ``load_model(path, device=...)`` -> object with ``.predict(x)``, ``.nn_module``, ``.device``.
+"""Model surface: ``load_model(path, device=...)`` -> object with ``.predict(x)``, ``.val_step(batch)``, ``.nn_module``, ``.device``.
 
-Mirrors argus.load_model + HRNetMetaModel.predict  (/root/reference/src/models/hrnet/metamodel.py:127-134,
+Mirrors argus.load_model + HRNetMetaModel.predict / val_step  (/root/reference/src/models/hrnet/metamodel.py:127-134, :59-86,
 checkpoint schema :108-124; callers: /root/reference/src/utils/make_submit.py:51,68 and
 /root/reference/src/utils/export_line_result.py:168,181).  pytorch-argus itself is not a dependency: the
 checkpoint is the plain ``torch.save`` dict {'model_name', 'params', 'nn_state_dict'}.
@@ -9,6 +9,7 @@ import torch
 
 from . import _lib
 from .hrnet import HRNetHeatmap, _plain
+from .loss import HRNetLoss
 from .transforms import HRNetPredictionTransform, EHMPredictionTransform
 
 
@@ -31,6 +32,7 @@ class HRNetMetaModel:
                                       head=self.head, upscale=self.upscale)
         pt = _plain(params.get('prediction_transform', {}) or {})
         self.prediction_transform = self.prediction_transform_cls(**pt) if pt else None
+        self.loss = None                 # built from params['loss'] by the first val_step(), or set by the caller / load_model(loss=...)
 
     def predict(self, x: torch.Tensor, check_range: bool = True) -> torch.Tensor:
         """x (B,3,H,W) float32 BGR in [0,1] (any device) -> prediction_transform(net(x)[-1]) on `device`.
@@ -49,6 +51,41 @@ class HRNetMetaModel:
         if check_range:
             self.check_range()
         return out
+
+    def _loss(self):
+        """The loss object of val_step: the one the caller set, else HRNetLoss(**params['loss']) (built on first use, so a checkpoint
+        whose loss this build does not cover -- refinement stages -- still loads and predicts)."""
+        if self.loss is None:
+            lp = _plain(self.params.get('loss', None) or {})
+            if not lp:
+                raise _lib.SncalError("val_step(): params hold no 'loss' section; set model.loss = HRNetLoss(...) "
+                                      'or pass load_model(..., loss=HRNetLoss(...))')
+            self.loss = HRNetLoss(**lp)
+        return self.loss
+
+    def val_step(self, batch: dict, state=None, sync: bool = False) -> dict:
+        """metamodel.py:59-86: batch {'image', 'keypoints', 'mask', 'raw_annot', 'img_name'} as the reference's loader collates it
+        ('image' (B,3,H,W) float32 BGR in [0,1], or (B,H,W,3) uint8 frames) -> {'prediction' (B,57,3), 'target', 'loss',
+        'raw_annots', 'img_name'}.  ONE forward gives the heatmap (for the loss) and the decoded keypoints (want_heat=True with
+        decode_size).  'loss' stays a 0-dim device tensor and nothing waits for the GPU unless sync=True, which returns it as a
+        float (the reference's loss.item()) and checks the split-fp16 engine's range flag as predict() does; with sync=False the
+        caller owes a check_range() before trusting the results.  The batch dict is not modified."""
+        if not isinstance(self.prediction_transform, HRNetPredictionTransform):
+            raise _lib.SncalError('val_step(): only the keypoint model (HRNetPredictionTransform) has a validation step')
+        loss_fn = self._loss()
+        image = batch['image'].to(self.device, non_blocking=True)
+        keypoints = batch['keypoints'].to(self.device, non_blocking=True)
+        mask = batch.get('mask')
+        if mask is not None:
+            mask = mask.to(self.device, non_blocking=True)
+        pt = self.prediction_transform
+        heat, prediction = self.nn_module.forward(image.contiguous(), want_heat=True, decode_size=(pt.H, pt.W))
+        loss = loss_fn([heat], keypoints, mask)
+        if sync:
+            self.check_range()
+            loss = loss.item()
+        return {'prediction': prediction, 'target': keypoints.detach(), 'loss': loss,
+                'raw_annots': batch['raw_annot'], 'img_name': batch['img_name']}
 
     def check_range(self):
         """Raise SncalRangeError if a forward since the last check left the split-fp16 engine's range (HRNetHeatmap.range_status):
@@ -73,6 +110,8 @@ _MODELS = {'HRNetMetaModel': HRNetMetaModel, 'EHMMetaModel': EHMMetaModel}
 
 def load_model(file_path, loss=None, optimizer=None, device='cuda:0', dtype: str = None, **_ignored):
     """argus.load_model(path, loss=None, optimizer=None, device=...) for the two inference models.
+    loss: None (default) leaves val_step() to build HRNetLoss from the checkpoint's params['loss']; an HRNetLoss instance or a dict of
+    its arguments replaces that.
     dtype: None (default) = 'fp16x3' WITH a fall-back to 'fp32' when the checkpoint's folded weights do not fit the split-fp16 range
     (SNCAL_ERR_RANGE at finalize; a warning names the layer).  'fp16x3' is the fp32-class engine bench.py measures (fp32 tensors, split-fp16 products, fp32 accumulation):
     on 2048 deep-path frames it reproduced the exact engine's keypoint indices on every usable row and its camera on every frame
@@ -101,4 +140,6 @@ def load_model(file_path, loss=None, optimizer=None, device='cuda:0', dtype: str
         warnings.warn(f'{file_path}: {e}; falling back to the exact-fp32 engine (dtype=\'fp32\', about 3x slower)')
         model = cls(params, dtype='fp32')
         model.nn_module.load_state_dict(state['nn_state_dict'])
+    if loss is not None:
+        model.loss = HRNetLoss(**_plain(loss)) if not isinstance(loss, HRNetLoss) else loss
     return model

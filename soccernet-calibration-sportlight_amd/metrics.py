@@ -1,0 +1,170 @@
+"""Validation metrics with device-side accumulators: L2metric and EvalAImetric of
+/root/reference/src/models/hrnet/metrics.py:14-94, 142-229 -- same names, constructor arguments, methods
+(reset / update(step_output) / compute / epoch_complete(state)) and dictionary keys.
+
+`state` is any object with `.phase` and `.metrics` (pytorch-argus is not a dependency).  update() queues device work only; the host
+reads the accumulators once, in compute() / epoch_complete().  The per-class confusion matrices the reference also sums
+(metrics.py:198-199) are never reported by it and are not kept here (CameraEvaluator.class_report gives them).  EvalAImetric sends the whole batch through the batched solve
+(CameraCreator.solve_device) and the batched evaluation (CameraEvaluator.evaluate) instead of a 16-process pool over frames.
+
+Mirrored, not fixed (the reference's behaviour is the definition):
+  * L2metric.n_fp / n_fn are ASSIGNED by each update, not accumulated (metrics.py:67-68): precision and recall relate the
+    matched points of the whole epoch to the false positives / negatives of the LAST batch;
+  * pckhs counts count_nonzero(l2[l2 < t]) (metrics.py:70): a matched point at distance exactly 0 is not counted;
+  * compute() is inf when no point matched.
+"""
+from typing import Callable, List, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from .evaluate import CameraEvaluator
+
+
+def _prefix(state) -> str:
+    return f'{state.phase}_' if getattr(state, 'phase', None) else ''
+
+
+class L2metric:
+    name = 'l2'
+    better = 'min'
+
+    def __init__(self, num_keypoints: int = 30, conf_threshold: float = 0.5, pckhs_thres: Sequence[float] = (2.0, 5.0, 10.0, 50.0)):
+        self.num_keypoints = num_keypoints
+        self.conf_threshold = conf_threshold
+        self.pckhs_thres = list(pckhs_thres)
+        self.reset()
+
+    def reset(self):
+        self._acc = None            # fp64 device vector [sum, num_el, gt_points, pred_points, pckhs...]: exact for the counts
+        self._last = None           # int64 device vector [n_fp, n_fn] of the last update
+
+    def update(self, step_output: dict):
+        preds = step_output['prediction']
+        kpts = step_output['target'].to(preds.device).reshape(-1, self.num_keypoints, 3)
+        l2 = torch.linalg.vector_norm(preds[:, :, :2] - kpts[:, :, :2], dim=-1)
+        gt_valid = kpts[:, :, 0] != -1
+        pred_valid = preds[:, :, 2] > self.conf_threshold
+        mask = gt_valid & pred_valid
+        # sums over l2[mask] without the host round trip of boolean indexing
+        parts = [torch.where(mask, l2, torch.zeros_like(l2)).sum(dtype=torch.float64), mask.sum(), gt_valid.sum(), pred_valid.sum()]
+        parts += [(mask & (l2 < t) & (l2 != 0)).sum() for t in self.pckhs_thres]
+        acc = torch.stack([p.to(torch.float64) for p in parts])
+        self._acc = acc if self._acc is None else self._acc + acc
+        self._last = torch.stack([(~gt_valid & pred_valid).sum(), (~pred_valid & gt_valid).sum()])
+
+    def _read(self):
+        n = 4 + len(self.pckhs_thres)
+        if self._acc is None:
+            return [0.0] + [0] * (n - 1), [0, 0]
+        acc = self._acc.cpu().numpy()
+        return [float(acc[0])] + [int(round(v)) for v in acc[1:]], [int(v) for v in self._last.cpu().numpy()]
+
+    def compute(self) -> float:
+        acc, _ = self._read()
+        return acc[0] / acc[1] if acc[1] > 0 else float('inf')
+
+    def epoch_complete(self, state):
+        acc, (n_fp, n_fn) = self._read()
+        total, num_el, gt_points = acc[0], acc[1], acc[2]
+        precision, recall = 0.0, 0.0
+        if num_el > 0:
+            precision = num_el / (num_el + n_fp)
+            recall = num_el / (num_el + n_fn)
+        p = _prefix(state)
+        state.metrics[f'{p}precision'] = precision
+        state.metrics[f'{p}recall'] = recall
+        for i, t in enumerate(self.pckhs_thres):
+            state.metrics[f'{p}pcks-{t}'] = acc[4 + i] / gt_points if gt_points > 0 else 0.0
+        state.metrics[f'{p}{self.name}'] = total / num_el if num_el > 0 else float('inf')
+
+
+class EvalAImetric:
+    """pred2cam: a CameraCreator (its batched solve_device is what runs); threshold in pixels; img_size (W, H)."""
+    name = 'evalai'
+    better = 'max'
+
+    def __init__(self, pred2cam: Callable, threshold: int = 5, img_size: Tuple[int, int] = (960, 540), max_workers: int = 16):
+        self.pred2cam = pred2cam
+        self.threshold = threshold
+        self.img_size = tuple(int(v) for v in img_size)
+        self._evaluator = None       # built on the first update, on the predictions' device (max_workers: no pool here, ignored)
+        self.reset()
+
+    def reset(self):
+        self.total_frames = 0
+        self._skipped = 0            # frames that never reached the network: missed without a solve
+        self._acc = None             # fp64 [missed, accuracy, n_accuracy, tp, n_precision, n_recall, l2_proj_sum, n_l2_proj]
+
+    def add_missed(self, n: int):
+        """Frames without a prediction (e.g. images the decoder refused): counted in total_frames and as missed."""
+        self.total_frames += int(n)
+        self._skipped += int(n)
+
+    def evaluator(self, device) -> CameraEvaluator:
+        if self._evaluator is None or self._evaluator.device != torch.device(device):
+            self._evaluator = CameraEvaluator(device, self.img_size[0], self.img_size[1], float(self.threshold))
+        return self._evaluator
+
+    def update(self, step_output: dict):
+        preds = step_output['prediction']
+        d_lp = None
+        lp = self.pred2cam.line_points_array(step_output.get('img_name'))
+        if lp is not None:
+            d_lp = torch.from_numpy(lp).to(preds.device)
+        records = self.pred2cam.solve_device(preds.contiguous().float(), d_lp)
+        self.update_records(records, step_output['raw_annots'])
+
+    def update_records(self, records: torch.Tensor, raw_annots: List[dict]):
+        """The aggregation of metrics.py:185-207 for a batch whose cameras are already solved: records (B, sizeof(sncal_camera))
+        uint8 on the device, status 0 = no camera."""
+        B = records.shape[0]
+        self.total_frames += B
+        if B == 0:
+            return
+        out, err, cls = self.evaluator(records.device).evaluate(records, raw_annots, detail=True)
+        done = out[:, 11] > 0
+        plain = out[:, 10] == 1                                           # the kept pass: plain labels only when strictly better
+        acc = torch.where(plain, out[:, 8], out[:, 9]).to(torch.float64)
+        conf = torch.where(plain[:, None], out[:, 0:4], out[:, 4:8]).to(torch.float64)      # [0,0] [0,1] [1,0] [1,1]
+        sel = torch.where(plain, 0, 1)
+        idx = torch.arange(B, device=out.device)
+        q = cls[idx, sel].to(torch.float64)                               # (B,C,4) [below, beyond, missed, fp_flag]
+        e = err[idx, sel]                                                 # (B,C,max_gt)
+        common = (q[..., 3] == 0) & (q[..., 2] == 0) & (q[..., 0] + q[..., 1] > 0) & done[:, None]
+        n_pts = torch.where(common, q[..., 0] + q[..., 1], torch.zeros_like(q[..., 0]))
+        k = torch.arange(e.shape[2], device=e.device)
+        used = k[None, None, :] < n_pts[..., None]
+        zero = torch.zeros((), dtype=torch.float64, device=out.device)
+        d = done.to(torch.float64)
+        parts = [(1.0 - d).sum(), torch.where(done, acc, zero).sum(), d.sum(),
+                 torch.where(done, conf[:, 0], zero).sum(), torch.where(done, conf[:, 0] + conf[:, 1], zero).sum(),
+                 torch.where(done, conf[:, 0] + conf[:, 2], zero).sum(),
+                 torch.where(used, e, zero).sum(), n_pts.sum()]            # non-finite errors propagate, as sum() does in the reference
+        a = torch.stack(parts)
+        self._acc = a if self._acc is None else self._acc + a
+
+    def _read(self):
+        if self._acc is None:
+            return np.zeros(8)
+        return self._acc.cpu().numpy()
+
+    def compute(self) -> float:
+        missed = float(self._read()[0]) + self._skipped
+        return (self.total_frames - missed) / self.total_frames if self.total_frames > 0 else 0.0
+
+    def epoch_complete(self, state):
+        a = self._read()
+        missed = float(a[0]) + self._skipped
+        completeness = (self.total_frames - missed) / self.total_frames if self.total_frames > 0 else 0.0
+        accuracy = a[1] / a[2] if a[2] > 0 else 0.0
+        precision = a[3] / a[4] if a[4] > 0 else 0.0
+        recall = a[3] / a[5] if a[5] > 0 else 0.0
+        l2_reproj = a[6] / a[7] if a[7] > 0 else float('inf')
+        p = _prefix(state)
+        state.metrics[f'{p}l2_reprojection'] = float(l2_reproj)
+        state.metrics[f'{p}completeness'] = float(completeness)
+        state.metrics[f'{p}eval_precision'] = float(precision)
+        state.metrics[f'{p}eval_recall'] = float(recall)
+        state.metrics[f'{p}eval_accuracy'] = float(accuracy)
+        state.metrics[f'{p}{self.name}'] = float(completeness * accuracy)

@@ -1,0 +1,212 @@
+"""Score a checkpoint: counterpart of /root/reference/src/models/hrnet/validate.py (val_config.yaml, optimize_valid.yaml) with
+every stage on the GPU path.
+
+    reference (argus Model.validate over get_loader)              here
+    cv2.imread + ToTensor, get_intersections   dataset.py:52-87   JpegDecoder -> uint8 BGR frames; annotations.get_intersections
+    model.val_step: forward, HRNetLoss, decode metamodel.py:59-86 HRNetMetaModel.val_step: one forward (heatmap + keypoints), fused loss
+    L2metric                                   metrics.py:14-94   metrics.L2metric, accumulators on the device
+    EvalAImetric: 16-process pool per frame    metrics.py:97-229  metrics.EvalAImetric: batched solve + batched evaluation
+    Loss metric (argus)                                           mean of the step losses weighted by step size (see validate())
+
+    python -m sncal_amd.validate --data DIR --model model.pth [--lines-file lines.pkl] [--batch-size 16]
+"""
+import argparse
+import json
+import os
+import warnings
+from typing import Dict, Iterable, Iterator, List, Sequence, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+from .annotations import get_intersections
+from .evaluate import scale_points
+from .jpeg import JpegDecoder, probe
+from .metrics import EvalAImetric, L2metric
+from .prediction import CameraCreator
+
+
+class _State:
+    def __init__(self, phase='val'):
+        self.phase = phase
+        self.metrics = {}
+
+
+class ValidationResult(dict):
+    """The metrics dict; .frames = frames seen, .skipped = names of the frames that could not be decoded (counted as missed)."""
+    frames = 0
+    skipped: List[str] = []
+
+
+def annot_to_keypoints(annot: dict, num_keypoints: int = 57, margin: float = 0.0):
+    """HRNetDataset._annot2keypoints (dataset.py:73-87): SoccerNet annotation {class: [{'x', 'y'}, ...]} (normalised) ->
+    (keypoints (3*num_keypoints,) float32 [x, y, 1] or [-1, -1, 0], mask (num_keypoints + 1,) int64)."""
+    points = {cls: [(p['x'], p['y']) for p in pts] for cls, pts in annot.items()}           # reader.decode_annot
+    kpts, missing = get_intersections(points, margin=margin)
+    keypoints = np.ones(num_keypoints * 3, dtype=np.float32) * -1
+    for i in range(num_keypoints):
+        if kpts[i] is not None:
+            keypoints[i * 3], keypoints[i * 3 + 1], keypoints[i * 3 + 2] = kpts[i][0], kpts[i][1], 1
+        else:
+            keypoints[i * 3 + 2] = 0
+    mask = np.ones(num_keypoints + 1, dtype=np.int64)
+    for i in missing:
+        mask[i] = 0
+    return keypoints, mask
+
+
+def list_split(folder: str):
+    """dataset.py:41-50: (image names, annotation dicts) of a SoccerNet split folder, sorted; names containing 'info' skipped."""
+    names, annots = [], []
+    for fname in sorted(os.listdir(folder)):
+        if 'info' in fname or not fname.endswith('.json'):
+            continue
+        img = fname.replace('.json', '.jpg')
+        if os.path.exists(os.path.join(folder, img)):
+            with open(os.path.join(folder, fname), 'r') as f:
+                annots.append(json.load(f))
+            names.append(img)
+    return names, annots
+
+
+def folder_batches(folder: str, batch_size: int, device, num_keypoints: int, margin: float, img_size, decoder_threads: int,
+                   skipped: List[str]) -> Iterator[dict]:
+    """The batch dicts of a split folder, frames decoded on the device as uint8 BGR.  A file the decoder cannot take is left out
+    of its batch and named in `skipped`."""
+    names, annots = list_split(folder)
+    dec, size = None, None
+
+    def skip(name, why):
+        warnings.warn(f'{name}: skipped ({why})')
+        skipped.append(name)
+
+    try:
+        for i in range(0, len(names), batch_size):
+            keep, blobs = [], []
+            for j in range(i, min(i + batch_size, len(names))):
+                try:
+                    with open(os.path.join(folder, names[j]), 'rb') as f:
+                        blob = f.read()
+                    fi = probe(blob)
+                    if size is None:
+                        size = (fi['height'], fi['width'])
+                        dec = JpegDecoder(size[0], size[1], max_batch=batch_size, threads=decoder_threads, device=device)
+                    if (fi['height'], fi['width']) != size:
+                        raise _lib.SncalError(f"{fi['width']}x{fi['height']} where the run's frames are {size[1]}x{size[0]}")
+                except (_lib.SncalError, OSError) as e:
+                    skip(names[j], e)
+                    continue
+                keep.append(j)
+                blobs.append(blob)
+            if not keep:
+                continue
+            try:
+                image = dec.decode(blobs)
+            except _lib.SncalError:                         # a stream damaged behind its headers: find it, drop it, decode the rest
+                good = []
+                for j, blob in zip(keep, blobs):
+                    try:
+                        dec.decode([blob])
+                        good.append((j, blob))
+                    except _lib.SncalError as e:
+                        skip(names[j], e)
+                if not good:
+                    continue
+                keep, blobs = [j for j, _ in good], [b for _, b in good]
+                image = dec.decode(blobs)
+            pairs = [annot_to_keypoints(annots[j], num_keypoints, margin) for j in keep]
+            yield {'image': image,
+                   'keypoints': torch.from_numpy(np.stack([p[0] for p in pairs])),
+                   'mask': torch.from_numpy(np.stack([p[1] for p in pairs])),
+                   'raw_annot': [scale_points(annots[j], img_size[0], img_size[1]) for j in keep],
+                   'img_name': [names[j] for j in keep]}
+    finally:                                            # also when the consumer stops early or raises: generator.close() lands here
+        if dec is not None:
+            dec.close()
+
+
+def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreator, Sequence[CameraCreator]], batch_size: int = 16,
+             loss=None, decoder_threads: int = 0, conf_threshold: float = 0.5, pckhs_thres: Sequence[float] = (2.0, 5.0, 10.0, 50.0),
+             threshold: int = 5, img_size=(960, 540)):
+    """-> {'val_loss', 'val_l2', 'val_precision', 'val_recall', 'val_pcks-2.0', ..., 'val_l2_reprojection', 'val_completeness',
+    'val_eval_precision', 'val_eval_recall', 'val_eval_accuracy', 'val_evalai'} as floats (a ValidationResult).
+
+    data    a SoccerNet split folder (NNNNN.jpg + NNNNN.json) or any iterable of the batch dicts the reference's loader yields
+            ({'image', 'keypoints', 'mask', 'raw_annot', 'img_name'}; batch_size then is whatever the iterable delivers)
+    camera  a CameraCreator, or a LIST of them: the network, the loss and L2metric run once per batch, only solve + evaluation run
+            per calibrator, and a list of results comes back, one per calibrator -- the trials of optimize_valid.yaml without
+            running the network once per trial
+    loss    an HRNetLoss; default: the model's own (params['loss'] of the checkpoint)
+
+    val_loss is the mean of the step losses weighted by step size.  This is the one definition here NOT taken from the reference:
+    it is computed by pytorch-argus' Loss metric there, whose source is not part of the reference tree.
+    A frame the decoder refuses (folder form) gets no prediction: it is left out of val_loss and the keypoint metrics and counted
+    as a missed frame by the camera metrics, as a frame without a camera is.  The host waits for the GPU once, at the end."""
+    cams = list(camera) if isinstance(camera, (list, tuple)) else [camera]
+    own_loss = model.loss
+    if loss is not None:
+        model.loss = loss                      # for this call only: restored below
+    batches = None
+    try:
+        loss_fn = model._loss()
+        nk = loss_fn.num_keypoints
+        l2 = L2metric(num_keypoints=nk, conf_threshold=conf_threshold, pckhs_thres=pckhs_thres)
+        evals = [EvalAImetric(c, threshold=threshold, img_size=img_size) for c in cams]
+        skipped: List[str] = []
+        if isinstance(data, (str, os.PathLike)):
+            batches = folder_batches(os.fspath(data), batch_size, model.device, nk, float(loss_fn.sigma), img_size, decoder_threads, skipped)
+        loss_sum = torch.zeros((), dtype=torch.float64, device=model.device)
+        frames = 0
+        for batch in (batches if batches is not None else data):
+            out = model.val_step(batch)
+            B = out['prediction'].shape[0]
+            frames += B
+            loss_sum = loss_sum + out['loss'].to(torch.float64) * B
+            l2.update(out)
+            for ev in evals:
+                ev.update(out)
+        model.check_range()
+    finally:
+        if batches is not None:
+            batches.close()                    # ends the generator: its finally closes the decoder, also after an exception mid-epoch
+        if loss is not None:
+            model.loss = own_loss
+    val_loss = float(loss_sum.item()) / frames if frames else float('nan')
+    results = []
+    for ev in evals:
+        ev.add_missed(len(skipped))
+        state = _State('val')
+        state.metrics['val_loss'] = val_loss
+        l2.epoch_complete(state)
+        ev.epoch_complete(state)
+        res = ValidationResult({k: float(v) for k, v in state.metrics.items()})
+        res.frames, res.skipped = ev.total_frames, list(skipped)          # the camera metric's own count: scored + skipped
+        results.append(res)
+    return results if isinstance(camera, (list, tuple)) else results[0]
+
+
+def main(argv=None):
+    from .metamodel import load_model
+    from .submit import default_calibrator
+    ap = argparse.ArgumentParser(description='Validate a keypoint checkpoint on a SoccerNet split (validate.py counterpart)')
+    ap.add_argument('--data', required=True, help='split folder: NNNNN.jpg + NNNNN.json')
+    ap.add_argument('--model', required=True, help='argus checkpoint of the keypoint model (model_name/params/nn_state_dict)')
+    ap.add_argument('--lines-file', default=None, help='lines pickle of export_line_result.py (optional)')
+    ap.add_argument('--batch-size', type=int, default=16)
+    ap.add_argument('--device', default='cuda:0')
+    ap.add_argument('--dtype', default=None, choices=['fp16x3', 'bf16x3', 'fp32', 'bf16', 'fp8'])
+    a = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise _lib.SncalError('no GPU visible: this package has no CPU path')
+    model = load_model(a.model, device=a.device, dtype=a.dtype)
+    res = validate(model, a.data, default_calibrator(a.lines_file), batch_size=a.batch_size)
+    for k, v in res.items():
+        print(f'{k}: {v:.6f}')
+    if res.skipped:
+        print(f'skipped: {len(res.skipped)} of {res.frames} frames')
+    return res
+
+
+if __name__ == '__main__':
+    main()
