@@ -426,6 +426,42 @@ int sncal_heatmap_loss(const float* d_logp, const float* d_kpts, const float* d_
                        float stride, int terms, double* d_out, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Line model, validation tail: target maps, fused loss, accuracy counts
+ *
+ * sncal_line_target replaces EHMDataset._generate_keypoint_maps / _add_gaussian      src/models/line/dataset.py:107-178
+ *   d_kpts (B,C,2,3) fp32 rows [x, y, flag] in IMAGE pixels, as the dataset yields them; a row with flag == 1 is drawn
+ *   d_out  (B,C,h,w) fp32.  Per drawn point mu = (min(w-1, rint(x/stride)), min(h-1, rint(y/stride))): fp32 division, ties to
+ *          even, no lower clamp (mu may be negative); exp(-((X-mu_x)^2 + (Y-mu_y)^2) / (2 sigma^2)) divided by its maximum over
+ *          the grid (1 unless mu is off the grid); a channel is the sum of its Gaussians, first point first
+ *
+ * sncal_line_loss replaces EHMLoss.forward for num_refinement_stages = 0              src/models/line/loss.py:34-108
+ *   d_pred   (B,C,h,w) fp32, the softmax output of the line head; read once
+ *   d_target (B,C,h,w) fp32 maps as a loader delivers them, or NULL
+ *   d_kpts   (B,C,2,3) as above, or NULL: the target is rebuilt in registers with target_sigma / stride and never written; the
+ *            values and their order are exactly those sncal_line_target writes.  Exactly one of d_target, d_kpts is non-NULL.
+ *   terms    bit0 GMSE sum of d^2 * exp(-d^2 / (2 gmse_sigma^2)), d = pred - target; bit1 adaptive wing (alpha 2.1, omega 14,
+ *            epsilon 1, theta 0.5); a term whose bit is clear is not computed and comes back 0
+ *   d_out    (B,2) fp64: per-frame SUMS over C*h*w.  The caller weighs and divides:
+ *            gmse_w * S_gmse / (B*C*h*w) + awing_w * S_awing / (B*C*h*w)
+ *   d_ws     caller-owned scratch of sncal_line_loss_workspace bytes, 16-byte aligned (SNCAL_ERR_WORKSPACE when short)
+ * C <= 64.  Deterministic: no atomics, partial sums are folded in a fixed order.
+ *
+ * sncal_line_acc_counts replaces AccMetric.a_t_score's counting                       src/models/line/metrics.py:53-103
+ *   d_gt, d_pred (B,C,2,3) fp32; ts: n_t <= 8 distance thresholds, a HOST array read inside the call
+ *   d_out (n_t,3) int64 [tp, fp, fn] over the whole batch.  Per (b, c) and slot i: gt_exists = gt[i,2] == 1,
+ *   pred_exists = pred[i,2] >= p_threshold, within = min_j |gt[i,:2] - pred[j,:2]| <= t over BOTH predicted points;
+ *   tp += gt & pred & within, fn += gt & ~pred, fp += pred & ~gt, fp += gt & pred & ~within (the reference's pairing by slot)
+ *
+ * All three are asynchronous on `stream`; the library allocates nothing.
+ * ---------------------------------------------------------------------------------------------- */
+int sncal_line_target(const float* d_kpts, int B, int C, float sigma, float stride, int h, int w, float* d_out, void* stream);
+int sncal_line_loss_workspace(int B, int C, int h, int w, size_t* bytes);
+int sncal_line_loss(const float* d_pred, const float* d_target, const float* d_kpts, int B, int C, int h, int w, float target_sigma,
+                    float stride, float gmse_sigma, int terms, double* d_out, void* d_ws, size_t ws_bytes, void* stream);
+int sncal_line_acc_counts(const float* d_gt, const float* d_pred, int B, int C, float p_threshold, const float* ts, int n_t,
+                          long long* d_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pipeline plumbing: a stream confined to `cus_per_xcd` compute units of each XCD (for the camera solves)
  * replaces the 16-process CPU pool of make_submit.py:25,53-54,69 (ProcessPoolExecutor workers beside the GPU loop): the solves of
  * up to four batches run beside the network on these streams; what they may occupy is bounded by the mask instead of by a process

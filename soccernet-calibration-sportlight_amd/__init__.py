@@ -14,9 +14,9 @@ from . import lines, pitch, prediction, camera, synth, dist, pipeline, interop, 
 from .evaluate import CameraEvaluator  # noqa: F401
 from .jpeg import JpegDecoder  # noqa: F401
 from .pipeline import CalibrationPipeline  # noqa: F401
-from .loss import HRNetLoss  # noqa: F401
-from .metrics import L2metric, EvalAImetric  # noqa: F401
+from .loss import HRNetLoss, EHMLoss  # noqa: F401
+from .metrics import L2metric, EvalAImetric, AccMetric  # noqa: F401
 
 __all__ = ['HRNetPredictionTransform', 'EHMPredictionTransform', 'HRNetHeatmap', 'load_config',
            'HRNetMetaModel', 'EHMMetaModel', 'load_model', 'Camera', 'CameraCreator', 'PITCH_POINTS',
-           'INTERSECTON_TO_PITCH_POINTS', 'HRNetLoss', 'L2metric', 'EvalAImetric']
+           'INTERSECTON_TO_PITCH_POINTS', 'HRNetLoss', 'EHMLoss', 'L2metric', 'EvalAImetric', 'AccMetric']

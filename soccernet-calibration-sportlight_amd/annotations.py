@@ -19,12 +19,16 @@ The arithmetic is this build's own:
   * the missing circle points come from a RANSAC homography pitch -> image (normalised DLT, deterministic sampling).
 No OpenCV, no lsq-ellipse.  Pinned by tests/golden/annotations.json: the imported reference functions (numpy-only parts) run on
 synthetic annotations with the two third-party calls replaced by the fit / homography of this file (tools/make_golden.py).
+
+The line model's labels (sort_anno, sort_points_on_line, get_extreme_points: /root/reference/src/datatools/line.py:82-220) are at
+the end of this file: polylines -> the two extreme points and (slope, intercept) of each of the 23 LINE_CLS lines.  Pinned by
+tests/golden/validate_line.npz (tools/make_golden_validate_line.py).
 """
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .lines import LINE_INTERSECTIONS
+from .lines import LINE_CLS, LINE_INTERSECTIONS
 from .pitch import INTERSECTON_TO_PITCH_POINTS, PITCH_POINTS
 
 NOT_ON_PLANE = (0, 1, 24, 25)
@@ -341,3 +345,79 @@ def get_intersections(points: Dict[str, List[Tuple[float, float]]], img_size: Tu
                                                  np.asarray(points[n2], dtype=np.float64) * size), img_size, within_image, margin)
     labels, mask = add_conic_points(points, labels, img_size)
     return {i: inside(p, img_size, True, margin) for i, p in labels.items()}, mask
+
+
+# ---- line-model labels -------------------------------------------------------------------------------------------
+
+NO_LINE = ('Circle left', 'Circle right', 'Circle central', 'Line unknown')
+
+
+def sort_points_on_line(points: List[Tuple[float, float]], input_size=(960, 540)):
+    """line.py:176-220: order a polyline (normalised coordinates) along its least-squares line y = slope * x + intercept, fitted in
+    PIXELS over the finite points -> (points, slope, intercept); (points as given, None, None) when fewer than two finite points
+    remain or they do not vary in x or in y.
+    Mirrored, not fixed: the projection takes the NORMALISED points against the PIXEL-space line (origin (0, intercept), direction
+    (1, slope) / (its norm + 1e-5)); equal projections fall through to comparing the points themselves; non-finite points stay in
+    the list and are sorted with their nan projections; no finite point at all raises ValueError, as the reference's unzip does."""
+    w, h = input_size
+    px = np.array([p[0] for p in points]) * w
+    py = np.array([p[1] for p in points]) * h
+    ok = np.isfinite(px) & np.isfinite(py)
+    if not ok.any():
+        raise ValueError('not enough values to unpack (expected 2, got 0)')
+    px, py = px[ok], py[ok]
+    if px.size < 2 or np.std(px) == 0 or np.std(py) == 0:
+        return points, None, None
+    slope, intercept = np.polyfit(px, py, deg=1)
+    origin = np.array([0, intercept])
+    direction = np.array([1, slope])
+    direction = direction / (np.linalg.norm(direction) + 0.00001)
+    along = [np.dot(np.array(p) - origin, direction) for p in points]
+    return [p for _, p in sorted(zip(along, points))], slope, intercept
+
+
+def sort_anno(annos: Dict[str, List[Tuple[float, float]]], img_size=(960, 540)):
+    """line.py:114-148: {class: polyline} -> ({class: (sorted polyline, (slope, intercept))}, usable).  Circles and 'Line unknown'
+    are ignored.  A line with fewer than two points, or whose fit failed, makes the whole frame unusable -- and so does a slope or
+    an intercept of exactly 0 (`if slope and intercept`, mirrored)."""
+    out, usable = {}, True
+    for name, pts in annos.items():
+        if name in NO_LINE:
+            continue
+        if len(pts) < 2:
+            usable = False
+            continue
+        pts, slope, intercept = sort_points_on_line(pts, input_size=img_size)
+        if slope and intercept:
+            out[name] = pts, (slope, intercept)
+        else:
+            usable = False
+    return out, usable
+
+
+def get_extreme_points(points_data: Dict[str, tuple], img_size=(960, 540)):
+    """line.py:82-111: sort_anno's dict -> {line id 0..22: ((first point, last point) in pixels, (slope, intercept)) or None}."""
+    res = {}
+    for i, name in LINE_CLS.items():
+        res[i] = None
+        if name in points_data:
+            pts, param = points_data[name][0], points_data[name][1]
+            if len(pts) > 1:
+                res[i] = (np.array(pts[0]) * img_size, np.array(pts[-1]) * img_size), param
+    return res
+
+
+def line_keypoints(labels: Dict[int, Optional[tuple]], num_keypoint_pairs: int = 23):
+    """EHMDataset.__getitem__ (line/dataset.py:74-92): get_extreme_points' dict -> (keypoints (num_keypoint_pairs * 6,) float32
+    rows [x, y, 1] or [-1, -1, 0], line_para [(slope, intercept) or (nan, nan)])."""
+    kp = np.ones(num_keypoint_pairs * 6, dtype=np.float32) * -1
+    paras = []
+    for i in range(num_keypoint_pairs):
+        if labels[i] is not None:
+            (p0, p1), para = labels[i]
+            kp[i * 6:i * 6 + 6] = (p0[0], p0[1], 1, p1[0], p1[1], 1)
+            paras.append(para)
+        else:
+            kp[i * 6 + 2] = kp[i * 6 + 5] = 0
+            paras.append((np.nan, np.nan))
+    return kp, paras

@@ -23,13 +23,18 @@
 // or VALU issue bounds each variant is a question for measurement, not for this header: profiles/validate_loss.md holds what was
 // measured (kernel times from a trace, algorithmic bytes over time against the HBM rate) and says so where nothing was.
 #include "common.hpp"
+#include "awing.hpp"
+#include "tile.hpp"
 #include "gauss.hpp"
 #include "../../include/sncal.h"
 
 namespace {
 
+using sncal::Vec;
+using sncal::lane_of;
+using sncal::wave_sum;
+
 constexpr int LS_MAXN = 64, LS_R = 4, LS_WAVES = 4, LS_ROWS = LS_R * LS_WAVES;
-constexpr float AW_ALPHA = 2.1f, AW_OMEGA = 14.0f, AW_THETA = 0.5f;     // loss.py:76-79 (epsilon = 1)
 
 struct Layout { size_t gx, gy, part, total; int bx, by; };
 
@@ -64,26 +69,7 @@ __device__ __forceinline__ void element(float p, float t, float logt, float& s_m
     const float e = expf(p);                                    // pred_01 = torch.exp(pred_masked)
     if (MSE) { const float d = e - t; s_mse = fmaf(d, d, s_mse); }
     if (KL) s_kl += t > 0.f ? t * (logt - p) : 0.f;             // xlogy(t, t) - t * p; target 0 contributes 0 (t is never negative)
-    if (AW) {
-        const float delta = fabsf(t - e), alpha_t = AW_ALPHA - t;
-        const float P = exp2f(-alpha_t);                        // pow(theta / epsilon, alpha_t), theta / epsilon = 1/2
-        const float P1 = exp2f(-(alpha_t - 1.0f));              // pow(theta / epsilon, alpha - target - 1)
-        const float A = AW_OMEGA * (1.0f / (1.0f + P)) * alpha_t * P1;
-        const float C = AW_THETA * A - AW_OMEGA * log1pf(P);
-        s_aw += delta < AW_THETA ? AW_OMEGA * log1pf(powf(delta, alpha_t)) : A * delta - C;
-    }
-}
-
-template <int V> struct Vec;
-template <> struct Vec<4> { using type = float4; };
-template <> struct Vec<1> { using type = float; };
-__device__ __forceinline__ float lane_of(const float4& v, int j) { return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w; }
-__device__ __forceinline__ float lane_of(const float& v, int) { return v; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
+    if (AW) s_aw += sncal::adaptive_wing(e, t);                 // awing.hpp, shared with line_loss.hip
 }
 
 template <int V, bool MSE, bool KL, bool AW>

@@ -5,6 +5,10 @@
   HRNetLoss.forward                 loss.py:89-144         csrc/loss.hip: MSE + KLDiv + adaptive wing in one read of the heatmap,
                                                            the target rebuilt on the fly, never written
 
+  EHMDataset._generate_keypoint_maps line/dataset.py:107-178   create_keypoint_maps: csrc/line_loss.hip writes the (B,C,h,w) two-peak maps
+  EHMLoss.forward                   line/loss.py:34-108        csrc/line_loss.hip: GMSE + adaptive wing in one read of the softmax heatmap;
+                                                           the target read from maps, or rebuilt from the endpoints and never written
+
 Forward values only: the backward pass (training) and refinement stages (num_refinement_stages > 0) are out of scope.
 """
 import ctypes
@@ -124,6 +128,121 @@ class HRNetLoss:
             loss = loss + self.kldiv_w * (s[1] / float(B))        # nn.KLDivLoss(reduction='batchmean')
         if self.awing_w > 0.0:
             loss = loss + self.awing_w * (s[2] / n)               # torch.mean
+        return loss.to(torch.float32)
+
+    __call__ = forward
+
+
+def _endpoints(keypoints, device) -> torch.Tensor:
+    """(B, C*6) or (B,C,2,3) [x, y, flag] rows in image pixels -> (B,C,2,3) fp32 contiguous on `device`."""
+    kp = keypoints.detach().to(device, torch.float32)
+    if kp.dim() == 2 and kp.shape[1] % 6 == 0:
+        kp = kp.reshape(kp.shape[0], kp.shape[1] // 6, 2, 3)
+    if kp.dim() != 4 or tuple(kp.shape[2:]) != (2, 3):
+        raise _lib.SncalError(f'keypoints {tuple(keypoints.shape)} must be (B, C*6) or (B,C,2,3)')
+    return kp.contiguous()
+
+
+def create_keypoint_maps(keypoints: torch.Tensor, sigma: float = 1.0, stride: float = 4.0, size: Tuple[int, int] = (135, 240)) -> torch.Tensor:
+    """EHMDataset._generate_keypoint_maps (line/dataset.py:107-178) for a batch: keypoints (B, C*6) or (B,C,2,3) [x, y, flag] in
+    image pixels (any device) -> (B,C,h,w) fp32 maps on the GPU, size = (h, w) of the map (the frame's size over the stride).
+    Asynchronous on the current stream."""
+    if not keypoints.is_cuda:
+        raise _lib.SncalError('keypoints must be a tensor on the GPU (libsncal has no CPU path)')
+    kp = _endpoints(keypoints, keypoints.device)
+    B, C = kp.shape[0], kp.shape[1]
+    h, w = int(size[0]), int(size[1])
+    out = torch.empty((B, C, h, w), dtype=torch.float32, device=kp.device)
+    with torch.cuda.device(kp.device):
+        _lib.check(_lib.lib().sncal_line_target(kp.data_ptr(), B, C, float(sigma), float(stride), h, w, out.data_ptr(),
+                                                _lib.current_stream_ptr()), 'sncal_line_target')
+    return out
+
+
+TERM_GMSE, TERM_LINE_AWING = 1, 2
+
+
+def line_loss_sums(pred: torch.Tensor, target=None, keypoints=None, target_sigma: float = 1.0, stride: float = 4.0,
+                   gmse_sigma: float = 4.0, terms: int = 3) -> torch.Tensor:
+    """sncal_line_loss: pred (B,C,h,w) fp32 softmax output; exactly one of target (B,C,h,w) fp32 maps and keypoints (B,C,2,3) fp32
+    endpoints in image pixels (the target is then rebuilt, never written) -> (B,2) fp64 per-frame sums of the GMSE and
+    adaptive-wing terms (0 where the term's bit is clear).  Asynchronous on the current stream."""
+    pred = _lib.require_device(pred, torch.float32, 'pred')
+    if (target is None) == (keypoints is None):
+        raise _lib.SncalError('exactly one of target and keypoints must be given')
+    if pred.dim() != 4:
+        raise _lib.SncalError(f'pred {tuple(pred.shape)} must be (B,C,h,w)')
+    B, C, h, w = pred.shape
+    if target is not None:
+        target = _lib.require_device(target, torch.float32, 'target')
+        if target.shape != pred.shape:
+            raise _lib.SncalError(f'target {tuple(target.shape)} must have the shape of pred {tuple(pred.shape)}')
+    else:
+        keypoints = _lib.require_device(keypoints, torch.float32, 'keypoints')
+        if tuple(keypoints.shape) != (B, C, 2, 3):
+            raise _lib.SncalError(f'keypoints {tuple(keypoints.shape)} must be (B,C,2,3) = {(B, C, 2, 3)}')
+    out = torch.zeros((B, 2), dtype=torch.float64, device=pred.device)
+    n = ctypes.c_size_t()
+    _lib.check(_lib.lib().sncal_line_loss_workspace(B, C, h, w, ctypes.byref(n)), 'sncal_line_loss_workspace')
+    with torch.cuda.device(pred.device):
+        ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=pred.device)
+        _lib.check(_lib.lib().sncal_line_loss(pred.data_ptr(), target.data_ptr() if target is not None else None,
+                                              keypoints.data_ptr() if keypoints is not None else None, B, C, h, w,
+                                              float(target_sigma), float(stride), float(gmse_sigma), int(terms), out.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()), 'sncal_line_loss')
+    return out
+
+
+class EHMLoss:
+    """EHMLoss (line/loss.py:5-108), forward value only, for num_refinement_stages = 0 (anything else raises SncalError; the
+    default here is 0 where the reference's is 1, because 0 is what is built and what train_config.yaml sets).
+
+    forward(pred, target): `pred` is the list the network returns (its entry 0, (B,C,h,w) softmax output, is used; a bare tensor is
+    taken as that entry).  A 4-D `target` holds maps (batch['keypoint_maps']); a (B, C*6) or (B,C,2,3) `target` holds the
+    endpoints (batch['keypoints'], image pixels) and the maps are rebuilt on the fly with `target_sigma` and `stride` -- this
+    build's additions, defaults = data_params of line/train_config.yaml.  Returns a 0-dim fp32 tensor on the device, with no host
+    synchronisation:  gmse_w * mean(d^2 exp(-d^2 / (2 sigma^2))) + awing_w * mean(adaptive_wing(pred, target)).
+    Terms whose weight is not > 0 are not computed, as in the reference.  B == 0 gives nan, as torch's means of nothing do."""
+
+    def __init__(self, num_refinement_stages: int = 0, gmse_w: float = 1.0, awing_w: float = 1.0, sigma: float = 4,
+                 target_sigma: float = 1, stride: float = 4):
+        if int(num_refinement_stages) != 0:
+            raise _lib.SncalError(f'EHMLoss: num_refinement_stages = {num_refinement_stages}; only 0 (one heatmap) is built')
+        self.n_losses = 1
+        self.gmse_w, self.awing_w = gmse_w, awing_w
+        self.sigma = sigma
+        self.target_sigma, self.stride = target_sigma, stride
+
+    @property
+    def terms(self) -> int:
+        return (TERM_GMSE if self.gmse_w > 0 else 0) | (TERM_LINE_AWING if self.awing_w > 0 else 0)
+
+    def create_keypoint_maps(self, keypoints: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
+        return create_keypoint_maps(keypoints, self.target_sigma, self.stride, size)
+
+    def components(self, pred_list, target) -> torch.Tensor:
+        """(B,2) fp64 on the device: per-frame sums over C*h*w of the GMSE and adaptive-wing terms (only those with a weight > 0;
+        the others are 0)."""
+        pred = pred_list[0] if isinstance(pred_list, (list, tuple)) else pred_list
+        if not isinstance(pred, torch.Tensor) or pred.dim() != 4:
+            raise _lib.SncalError(f'EHMLoss: pred {tuple(getattr(pred, "shape", ()))} must be (B,C,h,w)')
+        pred = pred.detach().contiguous()
+        # 4-D means maps; (B,C,2,3) means endpoints unless the heatmap itself is 2 x 3
+        if target.dim() == 4 and (tuple(target.shape[2:]) != (2, 3) or tuple(pred.shape[2:]) == (2, 3)):
+            maps = target.detach().to(pred.device, torch.float32).contiguous()
+            return line_loss_sums(pred, target=maps, gmse_sigma=self.sigma, terms=self.terms)
+        return line_loss_sums(pred, keypoints=_endpoints(target, pred.device), target_sigma=self.target_sigma, stride=self.stride,
+                              gmse_sigma=self.sigma, terms=self.terms)
+
+    def forward(self, pred_list, target) -> torch.Tensor:
+        s = self.components(pred_list, target).sum(dim=0)
+        pred = pred_list[0] if isinstance(pred_list, (list, tuple)) else pred_list
+        n = float(pred.numel())
+        loss = torch.zeros((), dtype=torch.float64, device=pred.device)
+        if self.gmse_w > 0:
+            loss = loss + self.gmse_w * (s[0] / n)
+        if self.awing_w > 0:
+            loss = loss + self.awing_w * (s[1] / n)
         return loss.to(torch.float32)
 
     __call__ = forward

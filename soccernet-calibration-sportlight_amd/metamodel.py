@@ -9,13 +9,14 @@ import torch
 
 from . import _lib
 from .hrnet import HRNetHeatmap, _plain
-from .loss import HRNetLoss
+from .loss import EHMLoss, HRNetLoss, create_keypoint_maps
 from .transforms import HRNetPredictionTransform, EHMPredictionTransform
 
 
 class HRNetMetaModel:
     """Inference-side mirror of the argus Model subclasses (keypoint: HRNetMetaModel, line: EHMMetaModel)."""
     prediction_transform_cls = HRNetPredictionTransform
+    loss_cls = HRNetLoss
     # what the model CLASS fixes in code, whatever the yaml says (None = read the yaml): the keypoint network's head and
     # upscale come from its config (src/models/hrnet/hrnet.py:306-330)
     head = None
@@ -58,9 +59,10 @@ class HRNetMetaModel:
         if self.loss is None:
             lp = _plain(self.params.get('loss', None) or {})
             if not lp:
-                raise _lib.SncalError("val_step(): params hold no 'loss' section; set model.loss = HRNetLoss(...) "
-                                      'or pass load_model(..., loss=HRNetLoss(...))')
-            self.loss = HRNetLoss(**lp)
+                name = self.loss_cls.__name__
+                raise _lib.SncalError(f"val_step(): params hold no 'loss' section; set model.loss = {name}(...) "
+                                      f'or pass load_model(..., loss={name}(...))')
+            self.loss = self.loss_cls(**lp)
         return self.loss
 
     def val_step(self, batch: dict, state=None, sync: bool = False) -> dict:
@@ -101,8 +103,37 @@ class EHMMetaModel(HRNetMetaModel):
     """Line model.  Its network ends in a hard-coded Softmax and never upscales (src/models/line/hrnet.py:86-102,
     236-245); the yaml inside a genuine checkpoint (line/model_config/hrnet_w48.yaml) has no 'head' / 'upscale' key."""
     prediction_transform_cls = EHMPredictionTransform
+    loss_cls = EHMLoss
     head = 'softmax'
     upscale = 1
+
+    def val_step(self, batch: dict, state=None, sync: bool = False, want_target: bool = False) -> dict:
+        """line/metamodel.py:51-71: batch {'image', 'keypoints' (B,138), 'line_para', ['keypoint_maps']} as the reference's loader
+        collates it ('image' (B,3,H,W) float32 BGR in [0,1], or (B,H,W,3) uint8 frames) -> {'prediction' (B,23,2,3), 'target',
+        'keypoints', 'line_para', 'loss'}.  ONE forward; the loss reads the batch's maps if it carries them, else rebuilds the target
+        from the endpoints inside the kernel (EHMLoss target_sigma / stride) and writes none.  'target' is the batch's maps, or
+        create_keypoint_maps(...) when want_target, else None.  'loss' stays a 0-dim device tensor and nothing waits for the GPU
+        unless sync=True (a float, after the range check of the split-fp16 engine, as in the keypoint val_step); with sync=False the
+        caller owes a check_range().  The batch dict is not modified."""
+        if self.prediction_transform is None:
+            raise _lib.SncalError('val_step(): params hold no prediction_transform')
+        loss_fn = self._loss()
+        image = batch['image'].to(self.device, non_blocking=True)
+        keypoints = batch['keypoints'].to(self.device, non_blocking=True)
+        maps = batch.get('keypoint_maps')
+        if maps is not None:
+            maps = maps.to(self.device, non_blocking=True)
+        heat = self.nn_module(image.contiguous())[-1]
+        loss = loss_fn([heat], maps if maps is not None else keypoints)
+        prediction = self.prediction_transform(heat)
+        target = maps
+        if target is None and want_target:
+            target = create_keypoint_maps(keypoints, loss_fn.target_sigma, loss_fn.stride, tuple(heat.shape[2:]))
+        if sync:
+            self.check_range()
+            loss = loss.item()
+        return {'prediction': prediction, 'target': None if target is None else target.detach(), 'keypoints': keypoints.detach(),
+                'line_para': batch.get('line_para'), 'loss': loss}
 
 
 _MODELS = {'HRNetMetaModel': HRNetMetaModel, 'EHMMetaModel': EHMMetaModel}
@@ -110,8 +141,8 @@ _MODELS = {'HRNetMetaModel': HRNetMetaModel, 'EHMMetaModel': EHMMetaModel}
 
 def load_model(file_path, loss=None, optimizer=None, device='cuda:0', dtype: str = None, **_ignored):
     """argus.load_model(path, loss=None, optimizer=None, device=...) for the two inference models.
-    loss: None (default) leaves val_step() to build HRNetLoss from the checkpoint's params['loss']; an HRNetLoss instance or a dict of
-    its arguments replaces that.
+    loss: None (default) leaves val_step() to build HRNetLoss from the checkpoint's params['loss']; an HRNetLoss instance (EHMLoss for the line
+    model) or a dict of its arguments replaces that.
     dtype: None (default) = 'fp16x3' WITH a fall-back to 'fp32' when the checkpoint's folded weights do not fit the split-fp16 range
     (SNCAL_ERR_RANGE at finalize; a warning names the layer).  'fp16x3' is the fp32-class engine bench.py measures (fp32 tensors, split-fp16 products, fp32 accumulation):
     on 2048 deep-path frames it reproduced the exact engine's keypoint indices on every usable row and its camera on every frame
@@ -141,5 +172,5 @@ def load_model(file_path, loss=None, optimizer=None, device='cuda:0', dtype: str
         model = cls(params, dtype='fp32')
         model.nn_module.load_state_dict(state['nn_state_dict'])
     if loss is not None:
-        model.loss = HRNetLoss(**_plain(loss)) if not isinstance(loss, HRNetLoss) else loss
+        model.loss = loss if isinstance(loss, (HRNetLoss, EHMLoss)) else cls.loss_cls(**_plain(loss))
     return model

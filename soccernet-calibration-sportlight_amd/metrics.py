@@ -2,6 +2,8 @@
 /root/reference/src/models/hrnet/metrics.py:14-94, 142-229 -- same names, constructor arguments, methods
 (reset / update(step_output) / compute / epoch_complete(state)) and dictionary keys.
 
+AccMetric is the line model's (/root/reference/src/models/line/metrics.py:20-137): csrc/line_loss.hip counts, the host aggregates.
+
 `state` is any object with `.phase` and `.metrics` (pytorch-argus is not a dependency).  update() queues device work only; the host
 reads the accumulators once, in compute() / epoch_complete().  The per-class confusion matrices the reference also sums
 (metrics.py:198-199) are never reported by it and are not kept here (CameraEvaluator.class_report gives them).  EvalAImetric sends the whole batch through the batched solve
@@ -18,6 +20,7 @@ from typing import Callable, List, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import _lib
 from .evaluate import CameraEvaluator
 
 
@@ -168,3 +171,83 @@ class EvalAImetric:
         state.metrics[f'{p}eval_recall'] = float(recall)
         state.metrics[f'{p}eval_accuracy'] = float(accuracy)
         state.metrics[f'{p}{self.name}'] = float(completeness * accuracy)
+
+
+ACC_TS = (5.0, 10.0, 20.0)          # metrics.py:117-118
+ACC_WS = (0.5, 0.35, 0.15)
+
+
+def line_acc_counts(gt: torch.Tensor, pred: torch.Tensor, p_threshold: float, ts: Sequence[float] = ACC_TS) -> torch.Tensor:
+    """sncal_line_acc_counts: gt, pred (B,C,2,3) fp32 on the GPU -> (len(ts),3) int64 [tp, fp, fn] on the device, all thresholds in
+    one launch.  Asynchronous on the current stream."""
+    import ctypes
+    pred = _lib.require_device(pred, torch.float32, 'prediction')
+    gt = _lib.require_device(gt, torch.float32, 'keypoints')
+    if pred.dim() != 4 or tuple(pred.shape[2:]) != (2, 3) or gt.shape != pred.shape:
+        raise _lib.SncalError(f'prediction {tuple(pred.shape)} and keypoints {tuple(gt.shape)} must both be (B,C,2,3)')
+    out = torch.zeros((len(ts), 3), dtype=torch.int64, device=pred.device)
+    c_ts = (ctypes.c_float * len(ts))(*[float(t) for t in ts])
+    with torch.cuda.device(pred.device):
+        _lib.check(_lib.lib().sncal_line_acc_counts(gt.data_ptr(), pred.data_ptr(), pred.shape[0], pred.shape[1], float(p_threshold),
+                                                    c_ts, len(ts), out.data_ptr(), _lib.current_stream_ptr()), 'sncal_line_acc_counts')
+    return out
+
+
+def acc_from_counts(counts) -> float:
+    """AccMetric.update + compute (metrics.py:105-137) on per-batch counts (n_batches, 3, 3) [threshold 5/10/20][tp, fp, fn].
+    Mirrored, not fixed: the loop over the thresholds OVERWRITES acc each time and then adds acc * ws[i], so a batch is worth
+    a@20 * 1.15 and the weights 0.5 / 0.35 never act; the epoch value is the plain mean over batches, whatever their sizes; a
+    batch with tp + fp + fn == 0 raises ZeroDivisionError."""
+    accs = []
+    for batch in counts:
+        acc = 0
+        for i in range(len(ACC_TS)):
+            tp, fp, fn = (int(v) for v in batch[i])
+            acc = tp / (tp + fp + fn)
+            acc += acc * ACC_WS[i]
+        accs.append(acc)
+    return float(np.mean(accs))
+
+
+class AccMetric:
+    """update() queues one kernel launch and keeps its (3,3) counts on the device; compute() reads them all at once."""
+    name = 'acc'
+    better = 'max'
+
+    def __init__(self, num_keypoints: int = 23, conf_threshold: float = 0.2, device: str = 'cuda:0'):
+        self.num_keypoints = num_keypoints
+        self.conf_threshold = conf_threshold
+        self.device = device
+        self.reset()
+
+    def reset(self):
+        self._counts = []           # per update: (3,3) int64 on the device
+
+    def update(self, step_output: dict):
+        preds = step_output['prediction'].detach().to(torch.float32).contiguous()
+        kpts = step_output['keypoints'].detach().to(preds.device, torch.float32).reshape(-1, self.num_keypoints, 2, 3).contiguous()
+        self._counts.append(line_acc_counts(kpts, preds, self.conf_threshold))
+
+    def _read(self) -> np.ndarray:
+        if not self._counts:
+            return np.zeros((0, len(ACC_TS), 3), dtype=np.int64)
+        return torch.stack(self._counts).cpu().numpy()
+
+    def compute(self) -> float:
+        """nan (with numpy's warning) when nothing was added, as np.mean([]) is in the reference."""
+        counts = self._read()
+        return acc_from_counts(counts) if len(counts) else float(np.mean([]))
+
+    def compute_detail(self) -> dict:
+        """Not in the reference: a@5, a@10, a@20 over the POOLED counts of the epoch and the weighted score its docstring describes,
+        0.5 a@5 + 0.35 a@10 + 0.15 a@20."""
+        tot = self._read().sum(axis=0)
+        out = {}
+        for i, t in enumerate(ACC_TS):
+            tp, fp, fn = (int(v) for v in tot[i])
+            out[f'a@{int(t)}'] = tp / (tp + fp + fn)
+        out['weighted'] = sum(w * out[f'a@{int(t)}'] for w, t in zip(ACC_WS, ACC_TS))
+        return out
+
+    def epoch_complete(self, state):
+        state.metrics[f'{_prefix(state)}{self.name}'] = self.compute()

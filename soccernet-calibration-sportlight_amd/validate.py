@@ -9,6 +9,13 @@ every stage on the GPU path.
     Loss metric (argus)                                           mean of the step losses weighted by step size (see validate())
 
     python -m sncal_amd.validate --data DIR --model model.pth [--lines-file lines.pkl] [--batch-size 16]
+
+The line model (line/train_config.yaml: val_loss and the monitored val_acc) is scored by validate_line():
+    EHMDataset listing, sort_anno, extreme points  line/dataset.py:54-92   list_line_split, annotations.line_keypoints
+    model.val_step: forward, EHMLoss, decode       line/metamodel.py:51-71 EHMMetaModel.val_step: one forward, fused loss, target rebuilt
+    AccMetric                                      line/metrics.py:20-137  metrics.AccMetric: counts on the device
+
+    python -m sncal_amd.validate --line --data DIR --model line.pth [--batch-size 8]
 """
 import argparse
 import json
@@ -20,10 +27,11 @@ import numpy as np
 import torch
 
 from . import _lib
-from .annotations import get_intersections
+from .annotations import get_extreme_points, get_intersections, line_keypoints, sort_anno
 from .evaluate import scale_points
 from .jpeg import JpegDecoder, probe
-from .metrics import EvalAImetric, L2metric
+from .lines import LINE_CLS
+from .metrics import AccMetric, EvalAImetric, L2metric
 from .prediction import CameraCreator
 
 
@@ -70,12 +78,12 @@ def list_split(folder: str):
     return names, annots
 
 
-def folder_batches(folder: str, batch_size: int, device, num_keypoints: int, margin: float, img_size, decoder_threads: int,
-                   skipped: List[str]) -> Iterator[dict]:
-    """The batch dicts of a split folder, frames decoded on the device as uint8 BGR.  A file the decoder cannot take is left out
-    of its batch and named in `skipped`."""
-    names, annots = list_split(folder)
-    dec, size = None, None
+def decoded_batches(folder: str, names: Sequence[str], batch_size: int, device, decoder_threads: int, skipped: List[str],
+                    frame_size=None) -> Iterator[tuple]:
+    """(indices into `names`, (n,H,W,3) uint8 BGR frames on the device) per batch of the JPEG files `names` of `folder`.  A file
+    the decoder cannot take, or whose size is not the run's (frame_size (H, W), or the first frame's when None), is left out of
+    its batch and named in `skipped`; a batch left empty is not yielded."""
+    dec, size = None, frame_size
 
     def skip(name, why):
         warnings.warn(f'{name}: skipped ({why})')
@@ -91,9 +99,10 @@ def folder_batches(folder: str, batch_size: int, device, num_keypoints: int, mar
                     fi = probe(blob)
                     if size is None:
                         size = (fi['height'], fi['width'])
-                        dec = JpegDecoder(size[0], size[1], max_batch=batch_size, threads=decoder_threads, device=device)
-                    if (fi['height'], fi['width']) != size:
+                    if (fi['height'], fi['width']) != tuple(size):
                         raise _lib.SncalError(f"{fi['width']}x{fi['height']} where the run's frames are {size[1]}x{size[0]}")
+                    if dec is None:
+                        dec = JpegDecoder(size[0], size[1], max_batch=batch_size, threads=decoder_threads, device=device)
                 except (_lib.SncalError, OSError) as e:
                     skip(names[j], e)
                     continue
@@ -115,15 +124,65 @@ def folder_batches(folder: str, batch_size: int, device, num_keypoints: int, mar
                     continue
                 keep, blobs = [j for j, _ in good], [b for _, b in good]
                 image = dec.decode(blobs)
+            yield keep, image
+    finally:                                            # also when the consumer stops early or raises: generator.close() lands here
+        if dec is not None:
+            dec.close()
+
+
+def folder_batches(folder: str, batch_size: int, device, num_keypoints: int, margin: float, img_size, decoder_threads: int,
+                   skipped: List[str]) -> Iterator[dict]:
+    """The batch dicts of a split folder, frames decoded on the device as uint8 BGR.  A file the decoder cannot take is left out
+    of its batch and named in `skipped`."""
+    names, annots = list_split(folder)
+    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped)
+    try:
+        for keep, image in frames:
             pairs = [annot_to_keypoints(annots[j], num_keypoints, margin) for j in keep]
             yield {'image': image,
                    'keypoints': torch.from_numpy(np.stack([p[0] for p in pairs])),
                    'mask': torch.from_numpy(np.stack([p[1] for p in pairs])),
                    'raw_annot': [scale_points(annots[j], img_size[0], img_size[1]) for j in keep],
                    'img_name': [names[j] for j in keep]}
-    finally:                                            # also when the consumer stops early or raises: generator.close() lands here
-        if dec is not None:
-            dec.close()
+    finally:
+        frames.close()
+
+
+def list_line_split(folder: str, input_size=(960, 540)):
+    """EHMDataset.__init__ (line/dataset.py:54-67): (image names, labels) of the frames whose annotation sort_anno finds usable;
+    labels are get_extreme_points' dicts.  Sorted by name (the reference takes os.listdir's order)."""
+    names, labels = [], []
+    for fname in sorted(os.listdir(folder)):
+        if 'info' in fname or not fname.endswith('.json'):
+            continue
+        img = fname.replace('.json', '.jpg')
+        if not os.path.exists(os.path.join(folder, img)):
+            continue
+        with open(os.path.join(folder, fname), 'r') as f:
+            annot = json.load(f)
+        points = {cls: [(p['x'], p['y']) for p in pts] for cls, pts in annot.items()}           # reader.decode_annot
+        res, usable = sort_anno(points, img_size=input_size)
+        if usable:
+            names.append(img)
+            labels.append(get_extreme_points(res, img_size=input_size))
+    return names, labels
+
+
+def line_folder_batches(folder: str, batch_size: int, device, num_keypoint_pairs: int, input_size, decoder_threads: int,
+                        skipped: List[str]) -> Iterator[dict]:
+    """The line model's batch dicts {'image', 'keypoints', 'line_para', 'img_name'} of a split folder (no 'keypoint_maps': the
+    loss rebuilds them).  Frames must be input_size (W, H): the reference's cv2.resize is not built, another size is skipped."""
+    names, labels = list_line_split(folder, input_size)
+    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped, frame_size=(input_size[1], input_size[0]))
+    try:
+        for keep, image in frames:
+            pairs = [line_keypoints(labels[j], num_keypoint_pairs) for j in keep]
+            yield {'image': image,
+                   'keypoints': torch.from_numpy(np.stack([p[0] for p in pairs])),
+                   'line_para': torch.tensor([p[1] for p in pairs], dtype=torch.float64),
+                   'img_name': [names[j] for j in keep]}
+    finally:
+        frames.close()
 
 
 def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreator, Sequence[CameraCreator]], batch_size: int = 16,
@@ -186,21 +245,71 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
     return results if isinstance(camera, (list, tuple)) else results[0]
 
 
+def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, loss=None, conf_threshold: float = 0.2,
+                  decoder_threads: int = 0, input_size=(960, 540)):
+    """Score a line-model checkpoint (EHMMetaModel) -> {'val_loss', 'val_acc'} as floats (a ValidationResult): the two numbers
+    line/train_config.yaml logs and monitors.
+
+    data    a SoccerNet split folder of input_size frames (NNNNN.jpg + NNNNN.json; frames whose annotation the reference's
+            sort_anno rejects are dropped, as its dataset drops them), or any iterable of the batch dicts the reference's loader
+            yields ({'image', 'keypoints', 'line_para', ['keypoint_maps']}; batch_size then is whatever the iterable delivers)
+    loss    an EHMLoss; default: the model's own (params['loss'] of the checkpoint)
+
+    val_loss is the mean of the step losses weighted by step size, as in validate(); val_acc is AccMetric's value (the plain mean
+    of the per-batch a@20 * 1.15, so it depends on batch_size, as in the reference).  A frame the decoder refuses (folder form) is
+    left out and named in .skipped.  The host waits for the GPU once, at the end."""
+    own_loss = model.loss
+    if loss is not None:
+        model.loss = loss                      # for this call only: restored below
+    batches = None
+    try:
+        model._loss()
+        acc = AccMetric(num_keypoints=len(LINE_CLS), conf_threshold=conf_threshold)
+        skipped: List[str] = []
+        if isinstance(data, (str, os.PathLike)):
+            batches = line_folder_batches(os.fspath(data), batch_size, model.device, acc.num_keypoints, input_size, decoder_threads, skipped)
+        loss_sum = torch.zeros((), dtype=torch.float64, device=model.device)
+        frames = 0
+        for batch in (batches if batches is not None else data):
+            out = model.val_step(batch)
+            acc.num_keypoints = out['prediction'].shape[1]          # the channel count is the network's
+            B = out['prediction'].shape[0]
+            frames += B
+            loss_sum = loss_sum + out['loss'].to(torch.float64) * B
+            acc.update(out)
+        model.check_range()
+    finally:
+        if batches is not None:
+            batches.close()
+        if loss is not None:
+            model.loss = own_loss
+    state = _State('val')
+    state.metrics['val_loss'] = float(loss_sum.item()) / frames if frames else float('nan')
+    acc.epoch_complete(state)
+    res = ValidationResult({k: float(v) for k, v in state.metrics.items()})
+    res.frames, res.skipped = frames + len(skipped), list(skipped)
+    return res
+
+
 def main(argv=None):
     from .metamodel import load_model
     from .submit import default_calibrator
     ap = argparse.ArgumentParser(description='Validate a keypoint checkpoint on a SoccerNet split (validate.py counterpart)')
+    ap.add_argument('--line', action='store_true', help='the checkpoint is the line model (EHMMetaModel): val_loss and val_acc')
     ap.add_argument('--data', required=True, help='split folder: NNNNN.jpg + NNNNN.json')
     ap.add_argument('--model', required=True, help='argus checkpoint of the keypoint model (model_name/params/nn_state_dict)')
     ap.add_argument('--lines-file', default=None, help='lines pickle of export_line_result.py (optional)')
-    ap.add_argument('--batch-size', type=int, default=16)
+    ap.add_argument('--batch-size', type=int, default=None, help='default 16, with --line 8')
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--dtype', default=None, choices=['fp16x3', 'bf16x3', 'fp32', 'bf16', 'fp8'])
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise _lib.SncalError('no GPU visible: this package has no CPU path')
     model = load_model(a.model, device=a.device, dtype=a.dtype)
-    res = validate(model, a.data, default_calibrator(a.lines_file), batch_size=a.batch_size)
+    if a.line:
+        res = validate_line(model, a.data, batch_size=a.batch_size or 8)
+    else:
+        res = validate(model, a.data, default_calibrator(a.lines_file), batch_size=a.batch_size or 16)
     for k, v in res.items():
         print(f'{k}: {v:.6f}')
     if res.skipped:

@@ -2,7 +2,7 @@
 
     python tools/bench_validate.py                      # A/B of the loss, roof share, validate() vs make_submit rates
     python tools/bench_validate.py --kernel-only        # just the fused loss, a few calls: the program to put behind
-                                                        #   rocprofv3 --kernel-trace --stats -d DIR -- python tools/bench_validate.py --kernel-only
+                                                        #   rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/bench_validate.py --kernel-only
     python tools/bench_validate.py --trace-dir DIR      # the run above, then read DIR's kernel stats into the report
 
 A/B: fused kernel (sncal_heatmap_loss) vs the composed path (sncal_create_target + the torch ops of HRNetLoss.forward, fp32, same
