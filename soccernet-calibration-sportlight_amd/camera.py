@@ -15,8 +15,8 @@ The arithmetic underneath is this build's own:
 * pan / tilt / roll are the ZXZ Euler angles of rotation^T, both tilt branches evaluated, the branch with the
   smaller |roll| kept (the reference's selection rule, camera.py:56-58).
 
-``solve_pnp`` / ``refine_camera`` run on the GPU through libsncal.so (csrc/solve.hip).  Pinned by
-tests/golden/camera.npz (captured from the imported reference).  ``draw_*`` is out of scope.
+``solve_pnp`` / ``refine_camera`` run on the GPU through libsncal.so (pnp_kernel in csrc/solve.hip, the
+minimisers in csrc/solve_pose.hpp).  Pinned by tests/golden/camera.npz (captured from the imported reference).  ``draw_*`` is out of scope.
 """
 import numpy as np
 

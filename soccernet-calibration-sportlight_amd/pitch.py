@@ -4,7 +4,8 @@ PITCH_POINTS / INTERSECTON_TO_PITCH_POINTS mirror /root/reference/src/datatools/
 SoccerPitch.point_dict (/root/reference/baseline/soccerpitch.py:109-263); the point sets mirror
 /root/reference/src/models/hrnet/prediction.py:15-41.  World frame: metres, origin at the centre mark,
 x along the pitch length (left goal at x = -52.5), +y towards the main-camera ("bottom") touch line,
-z = -height.  The device copy of the same table lives in csrc/solve.hip (build_pitch).
+z = -height.  The device copy of the same table lives in csrc/solve.hip (build_pitch fills it on the host;
+the solve_*.hpp device functions read it as c_P64 / c_P32).
 """
 import math
 

@@ -4,8 +4,8 @@ Same constructor (pitch, img_size, conf_thresh, algorithm, lines_file, **kwargs 
 ``__call__(pred (57,3) float32, name) -> Optional[Camera]`` that never raises, same five algorithm names,
 picklable (it holds only python data, so it can be shipped to worker processes exactly like the reference's
 at make_submit.py:53-54,69).  The solve itself -- every heuristic of the reference's voters -- runs on the
-GPU: one wavefront per frame in sncal_calibrate (csrc/solve.hip).  ``solve_batch`` is the batched entry the
-frame pipeline uses; ``__call__`` is the one-frame form of it.
+GPU: one wavefront per frame in sncal_calibrate (kernels and entry points: csrc/solve.hip; the control flow
+of this file: csrc/solve_flow.hpp).  ``solve_batch`` is the batched entry the frame pipeline uses; ``__call__`` is the one-frame form of it.
 """
 import ctypes
 import os

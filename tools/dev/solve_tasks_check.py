@@ -1,8 +1,10 @@
 """The one-wavefront-per-camera voter (sncal_calibrate's default since round 4) against the four-wave voter_kernel it replaces
 (SNCAL_SOLVE_TASKS=0): records byte for byte and time per batch of 64, on N noisy synthetic frames (the library's default refine
 criterion AND the bench's 200-iteration cap) and on the bench's own keypoints if gpurun_out/bench_kp.npy exists.  GPU box:
-    python tools/dev/solve_tasks_check.py run out.npz [N]      (once per setting of SNCAL_SOLVE_TASKS)
-    python tools/dev/solve_tasks_check.py cmp a.npz b.npz"""
+    python tools/dev/solve_tasks_check.py run out.npz [N [algorithms]]      (once per setting of SNCAL_SOLVE_TASKS)
+    python tools/dev/solve_tasks_check.py cmp a.npz b.npz
+`algorithms` lists further algorithms (comma-separated): each solves the first 63 of the N frames as ONE batch at the default refine
+criterion -> rec_<algorithm> (63 leaves calibrate_kernel's last workgroup partly empty at two and at four frames per workgroup)."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -48,4 +50,7 @@ for cap in (20000, 200):
         res[f'rec_{name}_cap{cap}'] = np.concatenate(recs)
         res[f'ms_{name}_cap{cap}'] = np.array(ts)
         print(name, cap, f'{np.mean(ts):.2f} ms per batch, max {np.max(ts):.2f}', flush=True)
+for alg in (sys.argv[4].split(',') if len(sys.argv) > 4 else ()):
+    cc = sncal_amd.CameraCreator(sncal_amd.PITCH_POINTS, algorithm=alg, **KW)
+    res[f'rec_{alg}'] = cc.solve_device(torch.from_numpy(kps[:63]).cuda()).cpu().numpy()
 np.savez(out, **res)
