@@ -2,6 +2,7 @@
 #include "common.hpp"
 #include "x3.hpp"
 #include <cstring>
+#include <vector>
 
 namespace sncal {
 static thread_local char g_err[512] = "";
@@ -12,6 +13,21 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 LaunchEvents& launch_events() { static thread_local LaunchEvents e; return e; }
+
+unsigned long long* trace_arm(size_t n, hipStream_t stream) {
+    unsigned long long* d = nullptr;
+    if (hipMalloc(&d, n * 8) != hipSuccess) return nullptr;
+    (void)hipMemsetAsync(d, 0, n * 8, stream);
+    return d;
+}
+void trace_dump(unsigned long long* d_trace, size_t n, const char* file, hipStream_t stream) {
+    if (!d_trace) return;
+    std::vector<unsigned long long> h(n);
+    (void)hipStreamSynchronize(stream);
+    (void)hipMemcpy(h.data(), d_trace, n * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(d_trace);
+    if (FILE* f = fopen(file, "wb")) { fwrite(h.data(), 8, n, f); fclose(f); }
+}
 }  // namespace sncal
 
 extern "C" int sncal_version(void) { return SNCAL_VERSION; }

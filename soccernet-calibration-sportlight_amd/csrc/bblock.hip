@@ -325,7 +325,7 @@ int launch_bblock48(const BBlockParams& p0, hipStream_t s) {
     p.tiles_x = (p.W + BB_TW - 1) / BB_TW;
     p.tiles_y = (p.H + BB_TH - 1) / BB_TH;
     p.trace = nullptr;
-    static const int dbg = getenv("SNCAL_BB_DBG") ? atoi(getenv("SNCAL_BB_DBG")) : 0;
+    static const int dbg = env_int("SNCAL_BB_DBG", 0);
     p.dbg = dbg;
     static int n_wgs = 0;
     if (!n_wgs) {
@@ -336,17 +336,12 @@ int launch_bblock48(const BBlockParams& p0, hipStream_t s) {
         n_wgs = cus >= 8 ? cus / 8 * 8 : 256;                 // one workgroup per CU, a multiple of the 8 XCDs
     }
     static const char* trace_file = getenv("SNCAL_BB_TRACE");
-    if (trace_file && hipMalloc(&p.trace, (size_t)n_wgs * BB_NW * 64) == hipSuccess) (void)hipMemsetAsync(p.trace, 0, (size_t)n_wgs * BB_NW * 64, s);
+    const size_t n_trace = (size_t)n_wgs * BB_NW * 8;
+    if (trace_file) p.trace = trace_arm(n_trace, s);
     if (!p.ticket) { set_error("launch_bblock48: no ticket words"); return SNCAL_ERR_ARG; }
     SNCAL_LAUNCH(bblock48_kernel, dim3((unsigned)n_wgs), dim3(64 * BB_NW), (size_t)BB_LDS + 16, s, p);
     SNCAL_CHECK_LAUNCH();
-    if (p.trace) {      // every launch overwrites the dump: the file holds the last fused block of the run
-        std::vector<unsigned long long> h((size_t)n_wgs * BB_NW * 8);
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h.data(), p.trace, h.size() * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(p.trace);
-        if (FILE* f = fopen(trace_file, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-    }
+    trace_dump(p.trace, n_trace, trace_file, s);      // every launch overwrites the dump: the file holds the last fused block of the run
     return SNCAL_OK;
 }
 

@@ -514,10 +514,10 @@ int launch_bblockx3(const BBlockX3Params& p0, hipStream_t s) {
     p.tiles_x = (p.W + TW - 1) / TW;
     p.tiles_y = (p.N * (p.H + 1) - 1 + TH - 1) / TH;
     p.h1_magic = (unsigned)((((unsigned long long)1 << 32) / (unsigned)(p.H + 1)) + 1ull);
-    static const int run_max = getenv("SNCAL_BBX_RUNS") ? atoi(getenv("SNCAL_BBX_RUNS")) : RUN_MAX;
+    static const int run_max = env_int("SNCAL_BBX_RUNS", RUN_MAX);
     p.run_max = run_max < 1 ? 1 : run_max;
     p.trace = nullptr;
-    static const int dbg = getenv("SNCAL_BBX_DBG") ? atoi(getenv("SNCAL_BBX_DBG")) : 0;
+    static const int dbg = env_int("SNCAL_BBX_DBG", 0);
     p.dbg = dbg;
     static int n_wgs = 0;
     if (!n_wgs) {
@@ -528,17 +528,12 @@ int launch_bblockx3(const BBlockX3Params& p0, hipStream_t s) {
         n_wgs = cus >= 8 ? cus / 8 * 8 : 256;                 // one workgroup per CU, a multiple of the 8 XCDs
     }
     static const char* trace_file = getenv("SNCAL_BBX_TRACE");
-    if (trace_file && hipMalloc(&p.trace, (size_t)n_wgs * NW * 64) == hipSuccess) (void)hipMemsetAsync(p.trace, 0, (size_t)n_wgs * NW * 64, s);
+    const size_t n_trace = (size_t)n_wgs * NW * 8;
+    if (trace_file) p.trace = trace_arm(n_trace, s);
     if (!p.ticket) { set_error("launch_bblockx3: no ticket words"); return SNCAL_ERR_ARG; }
     SNCAL_LAUNCH(bblockx3_kernel, dim3((unsigned)n_wgs), dim3(64 * (NW + 2)), (size_t)LDS_BYTES, s, p);
     SNCAL_CHECK_LAUNCH();
-    if (p.trace) {      // every launch overwrites the dump: the file holds the last fused block of the run
-        std::vector<unsigned long long> h((size_t)n_wgs * NW * 8);
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h.data(), p.trace, h.size() * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(p.trace);
-        if (FILE* f = fopen(trace_file, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
-    }
+    trace_dump(p.trace, n_trace, trace_file, s);      // every launch overwrites the dump: the file holds the last fused block of the run
     return SNCAL_OK;
 }
 

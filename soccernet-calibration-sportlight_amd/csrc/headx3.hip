@@ -1,4 +1,4 @@
-// Fused HRNet head of the bf16x3 engine: head32.hip's structure in SPLIT-bf16 arithmetic on fp32 tensors (keypoint network: stem
+// Fused HRNet head of the fp16x3 engine: head32.hip's structure in SPLIT-fp16 arithmetic on fp32 tensors (keypoint network: stem
 // features direct, two narrow branches folded into stage 1's K, two wide branches gathered; /root/reference/src/models/hrnet/hrnet.py
 // :489-510, :316-329).
 //
@@ -18,20 +18,15 @@
 // slice (they land under stage 1 + gather), a wave's gather boxes requested as soon as the wave has read the current ones.
 #include "common.hpp"
 #include "head.hpp"
-#include <vector>
-#include <cstdio>
 #include "softmax_px.hpp"
 #include "x3.hpp"
-#include <cstdio>
-#include <cstdlib>
 
 #pragma clang fp contract(off)
+#include "head_frame.hpp"
 
 namespace sncal {
 
 typedef x3h8 bf16x8;            // (x3.hpp: the 16-bit type of the split, fp16 or bf16; the name is historical)
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((address_space(3))) void lds_void;
 
 namespace {
 constexpr int KS = 13, RB = 2;
@@ -72,13 +67,8 @@ __global__ __launch_bounds__(256, 2) void headx3_kernel(const HeadParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int tile = blockIdx.x;
-    const unsigned q1 = p.tiles_x == 1 ? (unsigned)tile : __umulhi((unsigned)tile, p.tiles_x_magic);
-    const int tx = tile - (int)q1 * p.tiles_x;
-    const unsigned q2 = p.tiles_y == 1 ? q1 : __umulhi(q1, p.tiles_y_magic);
-    const int ty = (int)q1 - (int)q2 * p.tiles_y;
-    const int n = (int)q2;
-    const int oy0 = ty * 4, ox0 = tx * 32;
+    const HeadTile tl = head_tile(p, 32, 4);
+    const int n = tl.n, oy0 = tl.oy0, ox0 = tl.ox0;
     const int y = oy0 + wave, yc = min(y, p.H - 1);
     const int x = ox0 + l31, xc = min(x, p.W - 1);
     const bool valid = y < p.H && x < p.W;
@@ -90,37 +80,10 @@ __global__ __launch_bounds__(256, 2) void headx3_kernel(const HeadParams p) {
     bf16x8 wih[2], wil[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-        const int xlast = min(ox0 + 31, p.W - 1);
-        const float fy = p.sy[s] * (float)yc;
-        int by0 = (int)fy;
-        by0 = by0 > p.Hs[s] - 1 ? p.Hs[s] - 1 : by0;
-        const int nrows = by0 < p.Hs[s] - 1 ? 2 : 1;
-        const int bx0 = (int)(p.sx[s] * (float)ox0);
-        const int bx1 = min((int)(p.sx[s] * (float)xlast) + 1, p.Ws[s] - 1);
-        const int bw = bx1 - bx0 + 1, npx = nrows * bw;            // <= 16: checked on the host for the worst case
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int slot = j * 64 + lane, pi = slot >> 3, part = slot & 7;
-            const int ly = pi >= bw ? 1 : 0, lx = pi - ly * bw;
-            dma_voff[s][j] = pi < npx ? (unsigned)((((by0 + ly) * p.Ws[s] + bx0 + lx) * p.HP) * 4 + part * 16) : 0x80000000u;
-        }
-        const float fx = p.sx[s] * (float)xc;
-        int ix = (int)fx;
-        ix = ix > p.Ws[s] - 1 ? p.Ws[s] - 1 : ix;
-        const float ly1 = fy - (float)by0, lx1 = fx - (float)ix;
-        const float w00 = (1.f - lx1) * (1.f - ly1), w01 = lx1 * (1.f - ly1), w10 = (1.f - lx1) * ly1, w11 = lx1 * ly1;
-        const int t00 = ix - bx0, t01 = t00 + (ix < p.Ws[s] - 1 ? 1 : 0), t10 = t00 + (nrows == 2 ? bw : 0), t11 = t10 + (ix < p.Ws[s] - 1 ? 1 : 0);
+        const HeadBoxTaps b = head_box32<4, 2>(p, s, ox0, yc, xc, lane, dma_voff[s]);
         float wv[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int slot = 8 * hi + e;
-            float w = 0.f;
-            w += slot == t00 ? w00 : 0.f;
-            w += slot == t01 ? w01 : 0.f;
-            w += slot == t10 ? w10 : 0.f;
-            w += slot == t11 ? w11 : 0.f;
-            wv[e] = w;
-        }
+        for (int e = 0; e < 8; ++e) wv[e] = head_box_weight(b, 8 * hi + e);
         split8(wv, wih[s], wil[s]);
     }
 
@@ -220,14 +183,11 @@ __global__ __launch_bounds__(256, 2) void headx3_kernel(const HeadParams p) {
     for (int f = 0; f < HEAD_MAX_FOLD; ++f) {
         f_t0[f] = f_dx[f] = f_dy[f] = 0; f_lx[f] = f_ly[f] = 0.f;
         if (p.stage_folds && f < p.nfold) {
-            const float fy = p.fsy[f] * (float)yc, fx = p.fsx[f] * (float)xc;     // align_corners=True
-            int iy = (int)fy, ix = (int)fx;
-            iy = iy > p.Hf[f] - 1 ? p.Hf[f] - 1 : iy;
-            ix = ix > p.Wf[f] - 1 ? p.Wf[f] - 1 : ix;
-            f_ly[f] = fy - (float)iy; f_lx[f] = fx - (float)ix;
-            f_dx[f] = ix < p.Wf[f] - 1 ? p.Cf[f] : 0;
-            f_dy[f] = iy < p.Hf[f] - 1 ? f_bw[f] * p.Cf[f] : 0;
-            f_t0[f] = (OFF_W0 + W0_BUF + f_off[f]) / 4 + ((iy - f_iy0[f]) * f_bw[f] + (ix - f_ix0[f])) * p.Cf[f];
+            const HeadTap tp = head_tap(p.fsy[f], p.fsx[f], p.Hf[f], p.Wf[f], yc, xc);
+            f_ly[f] = tp.ly1; f_lx[f] = tp.lx1;
+            f_dx[f] = tp.more_x ? p.Cf[f] : 0;
+            f_dy[f] = tp.more_y ? f_bw[f] * p.Cf[f] : 0;
+            f_t0[f] = (OFF_W0 + W0_BUF + f_off[f]) / 4 + ((tp.iy - f_iy0[f]) * f_bw[f] + (tp.ix - f_ix0[f])) * p.Cf[f];
         }
     }
     bool staged_ready = false;
@@ -254,14 +214,10 @@ __global__ __launch_bounds__(256, 2) void headx3_kernel(const HeadParams p) {
                         if (p.stage_folds) {
                             blend8(reinterpret_cast<const float*>(smem) + f_t0[f] + (kk - seg0), f_dx[f], f_dy[f], f_lx[f], f_ly[f], v);
                         } else {
-                            const float fy = p.fsy[f] * (float)yc, fx = p.fsx[f] * (float)xc;     // align_corners=True
-                            int iy = (int)fy, ix = (int)fx;
-                            iy = iy > p.Hf[f] - 1 ? p.Hf[f] - 1 : iy;
-                            ix = ix > p.Wf[f] - 1 ? p.Wf[f] - 1 : ix;
-                            const float ly1 = fy - (float)iy, lx1 = fx - (float)ix;
-                            const int dx = ix < p.Wf[f] - 1 ? p.Cf[f] : 0, dy = iy < p.Hf[f] - 1 ? p.Wf[f] * p.Cf[f] : 0;
-                            const float* t = reinterpret_cast<const float*>(p.fold[f]) + (((size_t)n * p.Hf[f] + iy) * p.Wf[f] + ix) * p.Cf[f] + (kk - seg0);
-                            blend8(t, dx, dy, lx1, ly1, v);
+                            const HeadTap tp = head_tap(p.fsy[f], p.fsx[f], p.Hf[f], p.Wf[f], yc, xc);
+                            const int dx = tp.more_x ? p.Cf[f] : 0, dy = tp.more_y ? p.Wf[f] * p.Cf[f] : 0;
+                            const float* t = reinterpret_cast<const float*>(p.fold[f]) + (((size_t)n * p.Hf[f] + tp.iy) * p.Wf[f] + tp.ix) * p.Cf[f] + (kk - seg0);
+                            blend8(t, dx, dy, tp.lx1, tp.ly1, v);
                         }
                     }
                     seg0 += p.Cf[f];
@@ -297,14 +253,7 @@ __global__ __launch_bounds__(256, 2) void headx3_kernel(const HeadParams p) {
         lap(1);
         const char* const w0b = smem + OFF_W0 + (q & 1) * W0_BUF;
         // ---- stage 1: 32 hidden channels x 32 pixels, started at the folded-BN shift
-        f32x16 acc1;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float4 b0 = *reinterpret_cast<const float4*>(w0b + 2 * KS * 1024 + (16 * h + 8 * hi) * 4);
-            const float4 b1 = *reinterpret_cast<const float4*>(w0b + 2 * KS * 1024 + (16 * h + 8 * hi + 4) * 4);
-            acc1[8 * h + 0] = b0.x; acc1[8 * h + 1] = b0.y; acc1[8 * h + 2] = b0.z; acc1[8 * h + 3] = b0.w;
-            acc1[8 * h + 4] = b1.x; acc1[8 * h + 5] = b1.y; acc1[8 * h + 6] = b1.z; acc1[8 * h + 7] = b1.w;
-        }
+        f32x16 acc1 = head_acc_start(w0b + 2 * KS * 1024, hi);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const bf16x8 ah = *reinterpret_cast<const bf16x8*>(w0b + (ks * 64 + lane) * 16);
@@ -364,73 +313,19 @@ __global__ __launch_bounds__(256, 2) void headx3_kernel(const HeadParams p) {
         p.trace[(size_t)(blockIdx.x / 97) * 8 + 6] = tpro[0];
         p.trace[(size_t)(blockIdx.x / 97) * 8 + 7] = tpro[1];
     }
-    if constexpr (DEC) {
-        // decode-fused epilogue (head32.hip's): per-pixel log-softmax (softmax_px.hpp: the same arithmetic and summation order as the
-        // softmax kernels), then the tile's maxima per class over its 32 columns for every row and over its 4 rows for every column
-        float v[32], r[32];
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int c = rb * 32 + 16 * h + 8 * hi;
-                const float4 b0 = *reinterpret_cast<const float4*>(p.bias1 + c), b1 = *reinterpret_cast<const float4*>(p.bias1 + c + 4);
-                const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[8 * (2 * rb + h) + e] = c + e < p.dec_C ? acc2[rb][8 * h + e] + bb[e] : -INFINITY;
-            }
-        logsoftmax_px32x2(v, hi, p.dec_C, r);
-        asm volatile("s_barrier" ::: "memory");
-        float* const s_lp = reinterpret_cast<float*>(smem);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s_lp[(wave * 64 + 16 * k + 8 * hi + e) * 32 + l31] = valid ? r[8 * k + e] : -INFINITY;
-        __syncthreads();
-        const int C1 = p.dec_C - 1, t = threadIdx.x;
-        {
-            const int rw = t >> 6, c = t & 63, yy = oy0 + rw;
-            if (c < C1 && yy < p.H) {
-                const float4* qq = reinterpret_cast<const float4*>(s_lp + (rw * 64 + c) * 32);
-                float m = -INFINITY;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { const float4 u = qq[i]; m = fmaxf(m, fmaxf(fmaxf(u.x, u.y), fmaxf(u.z, u.w))); }
-                p.dec_row[(((size_t)n * C1 + c) * p.H + yy) * p.tiles_x + tx] = m;
-            }
-        }
-        for (int id = t; id < C1 * 32; id += 256) {
-            const int c = id >> 5, xx = id & 31;
-            if (ox0 + xx < p.W) {
-                const float m = fmaxf(fmaxf(s_lp[(0 * 64 + c) * 32 + xx], s_lp[(1 * 64 + c) * 32 + xx]), fmaxf(s_lp[(2 * 64 + c) * 32 + xx], s_lp[(3 * 64 + c) * 32 + xx]));
-                p.dec_col[(((size_t)n * p.tiles_y + ty) * C1 + c) * p.W + ox0 + xx] = m;
-            }
-        }
-        return;
-    }
-    if (valid) {
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int c = rb * 32 + 16 * h + 8 * hi;
-                if (c < p.LC) {
-                    const float4 b0 = *reinterpret_cast<const float4*>(p.bias1 + c), b1 = *reinterpret_cast<const float4*>(p.bias1 + c + 4);
-                    float* o = p.logits + pix * p.LC + c;
-                    *reinterpret_cast<float4*>(o) = make_float4(acc2[rb][8 * h] + b0.x, acc2[rb][8 * h + 1] + b0.y, acc2[rb][8 * h + 2] + b0.z, acc2[rb][8 * h + 3] + b0.w);
-                    *reinterpret_cast<float4*>(o + 4) = make_float4(acc2[rb][8 * h + 4] + b1.x, acc2[rb][8 * h + 5] + b1.y, acc2[rb][8 * h + 6] + b1.z, acc2[rb][8 * h + 7] + b1.w);
-                }
-            }
-    }
+    // decode-fused form (head_frame.hpp): log-softmax and the tile's row / column maxima in place of the logits
+    if constexpr (DEC) head_decode_epilogue(p, tl, acc2, smem, wave, hi, l31, valid);
+    else if (valid) head_store_logits32<RB>(p, acc2, pix, hi);
 }
 
 // applies to the keypoint network's head: two gather sources whose per-wave boxes hold at most 16 pixels, K1 = 13 x 16, 33..64 classes
+bool headx3_enabled() {
+    static const int enabled = env_int("SNCAL_HEADX3", 1);      // 0 = the split head on the generic fp32 kernels
+    return enabled != 0;
+}
 bool headx3_applies(const HeadParams& p) {
-    static const int enabled = getenv("SNCAL_HEADX3") ? atoi(getenv("SNCAL_HEADX3")) : 1;      // 0 = the split head on the generic fp32 kernels
-    if (!enabled || p.nsrc != 2 || !p.w0_32 || !p.w0_32_lo || !p.w1_32 || !p.w1_32_lo || p.ks16 != KS || p.LC != 64 || p.Cd % 8) return false;
-    for (int s2 = 0; s2 < 2; ++s2) {
-        const int bwid = (int)(p.sx[s2] * 31) + 3;
-        if (2 * bwid > 16) return false;
-    }
-    return true;
+    if (!headx3_enabled() || p.nsrc != 2 || !p.w0_32 || !p.w0_32_lo || !p.w1_32 || !p.w1_32_lo || p.ks16 != KS || p.LC != 64 || p.Cd % 8) return false;
+    return head_boxes_fit(p.sx[0]) && head_boxes_fit(p.sx[1]);
 }
 
 bool launch_headx3(const HeadParams& p, hipStream_t s) {
@@ -443,7 +338,7 @@ bool launch_headx3(const HeadParams& p, hipStream_t s) {
     }
     HeadParams q = p;
     // the folded branches' boxes through LDS (kernel prologue): at most four source rows per tile, both boxes within one stage-1 weight buffer
-    static const int stage = getenv("SNCAL_HEAD_STAGE") ? atoi(getenv("SNCAL_HEAD_STAGE")) : 1;
+    static const int stage = env_int("SNCAL_HEAD_STAGE", 1);
     q.stage_folds = stage != 0 && p.Cd % 16 == 0 ? 1 : 0;
     {
         int bytes = 0;
@@ -454,24 +349,13 @@ bool launch_headx3(const HeadParams& p, hipStream_t s) {
         }
         if (bytes > W0_BUF) q.stage_folds = 0;
     }
-    q.tiles_x = (p.W + 31) / 32;
-    q.tiles_y = (p.H + 3) / 4;
-    q.tiles_x_magic = q.tiles_x <= 1 ? 0u : 0xFFFFFFFFu / (unsigned)q.tiles_x + 1u;
-    q.tiles_y_magic = q.tiles_y <= 1 ? 0u : 0xFFFFFFFFu / (unsigned)q.tiles_y + 1u;
-    const unsigned blocks = (unsigned)(q.tiles_x * q.tiles_y * p.N);
+    const unsigned blocks = head_set_tiling(q, 32, 4);
     static const char* trace_file = getenv("SNCAL_HEAD_TRACE");
     const size_t n_tr = (size_t)(blocks / 97 + 1) * 8;
-    q.trace = nullptr;
-    if (trace_file && hipMalloc(&q.trace, n_tr * 8) == hipSuccess) (void)hipMemsetAsync(q.trace, 0, n_tr * 8, s);
+    q.trace = trace_file ? trace_arm(n_tr, s) : nullptr;
     if (p.dec_row && p.dec_col) SNCAL_LAUNCH((headx3_kernel<1>), dim3(blocks), dim3(256), (size_t)X_LDS, s, q);
     else SNCAL_LAUNCH((headx3_kernel<0>), dim3(blocks), dim3(256), (size_t)X_LDS, s, q);
-    if (q.trace) {
-        std::vector<unsigned long long> h(n_tr);
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h.data(), q.trace, n_tr * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(q.trace);
-        if (FILE* f = fopen(trace_file, "wb")) { fwrite(h.data(), 8, n_tr, f); fclose(f); }
-    }
+    trace_dump(q.trace, n_tr, trace_file, s);
     return true;
 }
 

@@ -42,7 +42,7 @@ void conv_params(const sncal_hrnet& net, const Op& op, int sb, char* ws, const M
     p.halo_w_magic = 0xFFFFFFFFu / (unsigned)((16 * m.twf - 1) * L.stride + L.k) + 1u;
     p.tiles_x = m.tiles_x; p.tiles_y = m.tiles_y;
     p.epi_lds = m.epi_lds ? 1 : 0;
-    { static const int abl = getenv("SNCAL_ABLATE") ? atoi(getenv("SNCAL_ABLATE")) : 0; p.ablate = abl; }
+    { static const int abl = env_int("SNCAL_ABLATE", 0); p.ablate = abl; }
     p.w_bytes = (unsigned)((size_t)L.nblk * L.chunks * conv_nks(L.k, L.g) * L.mi * 1024);
     p.nblk = L.nblk;
     p.n_work = (unsigned)(p.tiles_x * p.tiles_y * sb * L.nblk);
@@ -137,15 +137,6 @@ int tt_build_plan(const sncal_hrnet& net, const TTMember* mem, int n, TTPlanDev&
     return SNCAL_OK;
 }
 
-// tuning aids: write a device buffer of n_trace timestamps to `file` and free it (synchronises the stream)
-void dump_trace(unsigned long long* d_trace, size_t n_trace, const char* file, hipStream_t stream) {
-    std::vector<unsigned long long> h(n_trace);
-    (void)hipStreamSynchronize(stream);
-    (void)hipMemcpy(h.data(), d_trace, n_trace * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d_trace);
-    if (FILE* f = fopen(file, "wb")) { fwrite(h.data(), 8, n_trace, f); fclose(f); }
-}
-
 int run_input(const sncal_hrnet& net, const Launch& e, const Call& c) {
     const Tensor& t = net.tensors[net.ops[e.op].out];
     if (c.x8) return launch_u8hwc_to_nhwc(net.dtype, c.x8 + (size_t)c.b0 * 3 * t.H * t.W, c.ws + t.offset, c.sb, t.H, t.W, c.stream);
@@ -161,11 +152,11 @@ int run_conv(const sncal_hrnet& net, const Launch& e, const Call& c) {
     unsigned long long* d_trace = nullptr; size_t n_trace = 0;
     if (trace_name && net.layers[op.conv].name == trace_name) {
         n_trace = (size_t)8 * ((p.n_work + 7) / 8) * 16;
-        if (hipMalloc(&d_trace, n_trace * 8) == hipSuccess) { (void)hipMemsetAsync(d_trace, 0, n_trace * 8, c.stream); p.trace = d_trace; }
+        p.trace = d_trace = trace_arm(n_trace, c.stream);
     }
     e.m[0].v->launch(p, dim3(8 * p.per_xcd), e.m[0].lds, c.stream);
     SNCAL_CHECK_LAUNCH();
-    if (d_trace) dump_trace(d_trace, n_trace, "conv_trace.bin", c.stream);
+    trace_dump(d_trace, n_trace, "conv_trace.bin", c.stream);
     return SNCAL_OK;
 }
 
@@ -207,15 +198,15 @@ int run_tt(sncal_hrnet& net, Launch& e, const Call& c) {
     // (SNCAL_TT_TRACE_CFG64=1: of the last launch of the 64-channel tile instead)
     static const char* trace_file = getenv("SNCAL_TT_TRACE");
     static const bool trace_cfg64 = getenv("SNCAL_TT_TRACE_CFG64") && atoi(getenv("SNCAL_TT_TRACE_CFG64")) != 0;
-    static const int trace_nth = getenv("SNCAL_TT_TRACE_NTH") ? atoi(getenv("SNCAL_TT_TRACE_NTH")) : -1;      // only the n-th such launch of the process
+    static const int trace_nth = env_int("SNCAL_TT_TRACE_NTH", -1);      // only the n-th such launch of the process
     static int trace_seen = 0;
     unsigned long long* d_trace = nullptr;
     const size_t n_trace = (size_t)e.plan.n_wgs * 2 * 256;
-    if (trace_file && (trace_cfg64 ? e.plan.cfg == 1 : n == 3) && (trace_nth < 0 || trace_seen++ == trace_nth) && hipMalloc(&d_trace, n_trace * 8) == hipSuccess) { (void)hipMemsetAsync(d_trace, 0, n_trace * 8, stream); tp.trace = d_trace; }
-    { static const int abl = getenv("SNCAL_TT_ABLATE") ? atoi(getenv("SNCAL_TT_ABLATE")) : 0; tp.ablate = abl; }
+    if (trace_file && (trace_cfg64 ? e.plan.cfg == 1 : n == 3) && (trace_nth < 0 || trace_seen++ == trace_nth)) tp.trace = d_trace = trace_arm(n_trace, stream);
+    { static const int abl = env_int("SNCAL_TT_ABLATE", 0); tp.ablate = abl; }
     launch_conv_tt(tp, e.plan.n_wgs, fp8 ? 1 : x3 ? 2 : 0, stream, e.plan.cfg);
     SNCAL_CHECK_LAUNCH();
-    if (d_trace) dump_trace(d_trace, n_trace, trace_file, stream);
+    trace_dump(d_trace, n_trace, trace_file, stream);
     return SNCAL_OK;
 }
 
@@ -373,7 +364,7 @@ int run_head(const sncal_hrnet& net, const Launch& e, const Call& c) {
         hp.dec_row = hp.logits; hp.dec_col = hp.logits + (size_t)c.sb * (net.desc.num_classes - 1) * to.H * rp; hp.dec_C = net.desc.num_classes;
     }
     if (!net.x3) return launch_head_fused(hp, net.head_m2, c.stream);
-    if (!launch_headx3(hp, c.stream)) { set_error("bf16x3 head: configuration not served by headx3 (set SNCAL_HEADX3=0)"); return SNCAL_ERR_STATE; }
+    if (!launch_headx3(hp, c.stream)) { set_error("fp16x3 head: configuration not served by headx3 (set SNCAL_HEADX3=0)"); return SNCAL_ERR_STATE; }
     SNCAL_CHECK_LAUNCH();
     return SNCAL_OK;
 }

@@ -22,11 +22,12 @@ int sncal::layout(sncal_hrnet& net, int sb, int H, int W) {
         const bool dims_ok = net.desc.upscale == 1 || (sh == bh * net.desc.upscale && sw == bw * net.desc.upscale);
         net.use_fused = net.fused_enabled && net.dtype == SNCAL_BF16 && dims_ok && net.d_hw0 != nullptr;
         if (net.x3 && net.fused_enabled && dims_ok && net.desc.upscale == 2 && net.d_hw0_32l && net.head_ks16 == 13 && net.head_m2 == 4 &&
-            !(getenv("SNCAL_HEADX3") && atoi(getenv("SNCAL_HEADX3")) == 0)) {
-            // bf16x3: the fused split-arithmetic head (headx3.hip) when its gather boxes fit: branches 2 and 3 against the head's width
+            headx3_enabled()) {
+            // fp16x3: the fused split-arithmetic head (headx3.hip) when its gather boxes fit: branches 2 and 3 against the head's width
+            // (the scales head_params will hand headx3_applies, before the tensors have their shapes)
             const int w2 = half(half(bw)), w3 = half(w2);
             const float sx2 = sw > 1 ? (float)(w2 - 1) / (float)(sw - 1) : 0.f, sx3 = sw > 1 ? (float)(w3 - 1) / (float)(sw - 1) : 0.f;
-            net.use_fused = 2 * ((int)(sx2 * 31) + 3) <= 16 && 2 * ((int)(sx3 * 31) + 3) <= 16;
+            net.use_fused = head_boxes_fit(sx2) && head_boxes_fit(sx3);
         }
         net.use_split = !net.use_fused && net.has_split && net.dtype == SNCAL_F32 && dims_ok;
     }

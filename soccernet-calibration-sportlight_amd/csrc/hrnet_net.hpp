@@ -160,10 +160,10 @@ struct sncal_hrnet {
     std::vector<int> producer;                // per tensor: active op that writes it
     bool fuse_bblock = getenv("SNCAL_FUSE_BBLOCK") ? atoi(getenv("SNCAL_FUSE_BBLOCK")) != 0 : true;   // 48-channel BasicBlocks as one kernel (bblock.hip), bf16 path
     // split engines, layer1 (bneckx3.hip): bit 0 = conv3 of a Bottleneck + conv1 of the next as one pass, bit 1 = block 0's downsample branch inside its conv3
-    int fuse_bneck = getenv("SNCAL_FUSE_BNECK") ? atoi(getenv("SNCAL_FUSE_BNECK")) : 3;
+    int fuse_bneck = sncal::env_int("SNCAL_FUSE_BNECK", 3);
     void *d_hw0 = nullptr, *d_hw1 = nullptr;
     void *d_hw0_32 = nullptr, *d_hw1_32 = nullptr;      // head32.hip packing (null when K1 is not a multiple of 16)
-    void *d_hw0_32l = nullptr, *d_hw1_32l = nullptr;    // bf16x3 engine (headx3.hip): lo parts of the split weights; d_hw0_32 / d_hw1_32 then hold the hi parts
+    void *d_hw0_32l = nullptr, *d_hw1_32l = nullptr;    // fp16x3 engine (headx3.hip): lo parts of the split weights; d_hw0_32 / d_hw1_32 then hold the hi parts
     int head_ks16 = 0;
     float *d_hb0 = nullptr, *d_hb1 = nullptr;
     int cur_group = sncal::GRP_ALL;

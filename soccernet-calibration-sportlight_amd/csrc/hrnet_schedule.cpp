@@ -140,7 +140,7 @@ int tt_cfg(const sncal_hrnet& net, const Op* ops, int n, int sb) {
     const ConvLayer& L0 = net.layers[ops[0].conv];
     if (!L0.x3_on) return 0;
     if (n == 1 && L0.x3_blk == 64) return 1;
-    const int per_team = getenv("SNCAL_TT_SMALL_ITEMS") ? atoi(getenv("SNCAL_TT_SMALL_ITEMS")) : 2;      // (read per plan: tests run both tiles in one process; 0 = never)
+    const int per_team = env_int("SNCAL_TT_SMALL_ITEMS", 2);      // (read per plan: tests run both tiles in one process; 0 = never)
     long items = 0;
     for (int i = 0; i < n; ++i) {
         const Tensor& ti = net.tensors[ops[i].in];

@@ -176,29 +176,39 @@ def test_fused_basicblock_is_bit_identical_to_two_convs(sncal, cuda, monkeypatch
     assert torch.equal(outs[0], outs[1])
 
 
-@pytest.mark.parametrize('cfg_name,hw', [('hrnet_w18', (64, 96)), ('hrnet_w18', (135, 240)), ('hrnet_w48', (540, 960)), ('hrnet_w48', (1080, 1920)),
-                                         ('hrnet_w48', (270, 500))])
-def test_fused_logsoftmax_decode_is_bit_identical(sncal, cuda, cfg_name, hw):
-    """predict() without the heatmap runs log-softmax + keypoint decode fused: inside the head kernel where head32.hip applies
-    (W48 at 540x960: neither logits nor the (B,58,h,w) tensor are written, `kp_finish` reduces the tiles' maxima), as
-    logsoftmax_rowcol + kp_finish on the logits otherwise (decode.hip).  Same per-pixel arithmetic (softmax_px.hpp) and exact
-    maxima, so the keypoints must equal, bit for bit, those decoded from the heatmap the unfused path writes -- including
-    sizes that are not multiples of the tiles or the 18-row strip."""
+def _fused_decode_case(sncal, cuda, cfg_name, hw, dtype):
     cfg = hr.load_config(cfg_name)
-    net = sncal.HRNetHeatmap(cfg_name, dtype='bf16', device=cuda)
+    net = sncal.HRNetHeatmap(cfg_name, dtype=dtype, device=cuda)
     net.load_state_dict(hr.seeded_state_dict(cfg, 7, 3.0))
     x = hr.seeded_input(3, hw[0], hw[1], 11).to(cuda)
     net.set_profiling(True)
     _, k_fused = net.forward(x, want_heat=False, decode_size=(540, 960))
     kernels = {p['kernel'] for p in net.get_profile()}
     assert ('logsoftmax_decode_fused' in kernels or 'kp_finish' in kernels) and 'softmax_nchw' not in kernels
-    if cfg_name == 'hrnet_w48' and hw[0] >= 540:
+    if cfg_name == 'hrnet_w48' and (hw[0] >= 540 or hw == (140, 240)):
         assert 'kp_finish' in kernels and 'logsoftmax_decode_fused' not in kernels      # the head kernel did the first half
     net.set_profiling(False)
     heat, k_heat = net.forward(x, want_heat=True, decode_size=(540, 960))
     assert torch.equal(k_fused, k_heat)
     ref = od.keypoint_decode(heat.cpu().numpy(), (540, 960))
     assert np.array_equal(k_fused.cpu().numpy()[..., :2], ref[..., :2])
+
+
+@pytest.mark.parametrize('cfg_name,hw', [('hrnet_w18', (64, 96)), ('hrnet_w18', (135, 240)), ('hrnet_w48', (540, 960)), ('hrnet_w48', (1080, 1920)),
+                                         ('hrnet_w48', (270, 500)), ('hrnet_w48', (140, 240))])
+def test_fused_logsoftmax_decode_is_bit_identical(sncal, cuda, cfg_name, hw):
+    """predict() without the heatmap runs log-softmax + keypoint decode fused: inside the head kernel where head32.hip applies
+    (W48 at 540x960: neither logits nor the (B,58,h,w) tensor are written, `kp_finish` reduces the tiles' maxima), as
+    logsoftmax_rowcol + kp_finish on the logits otherwise (decode.hip).  Same per-pixel arithmetic (softmax_px.hpp) and exact
+    maxima, so the keypoints must equal, bit for bit, those decoded from the heatmap the unfused path writes -- including
+    sizes that are not multiples of the tiles or the 18-row strip (140x240: a 70x120 head, partial 4 x 32 tiles in both directions)."""
+    _fused_decode_case(sncal, cuda, cfg_name, hw, 'bf16')
+
+
+@pytest.mark.parametrize('hw', [(540, 960), (1080, 1920), (270, 500), (140, 240)])
+def test_fused_logsoftmax_decode_is_bit_identical_fp16x3(sncal, cuda, hw):
+    """The same on the fp16x3 engine: headx3.hip includes the same decode-fused epilogue (head_frame.hpp) as head32.hip."""
+    _fused_decode_case(sncal, cuda, 'hrnet_w48', hw, 'fp16x3')
 
 
 def test_grouped_branch_convs_are_bit_identical(sncal, cuda, monkeypatch):

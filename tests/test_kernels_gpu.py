@@ -502,6 +502,19 @@ def test_every_launch_of_the_bf16_engine_odd_sizes(sncal, cuda):
     assert stats['conv_tt<bf16,k3,s1,8x32x96>']['ops'] == 144
 
 
+@pytest.mark.parametrize('dtype', ['bf16', 'fp16x3'])
+def test_every_launch_with_partial_head_tiles_in_both_directions(sncal, cuda, dtype):
+    """2 frames of 140x240: a 70x120 head on the fused 32-wide kernels (head32.hip / headx3.hip, tiles of 4 rows x 32 columns) whose
+    last row tile holds 2 of 4 rows AND whose last column tile holds 24 of 32 columns -- the `valid` / column masks of the shared
+    epilogue and logits store (head_frame.hpp); the 540p and 1080p heads have full column tiles, 270x500 takes the unfused head.
+    The profile labels the bf16 head by engine, not by kernel: that head32.hip (and not head.hip's 16-wide kernel) serves this shape is
+    what tests/test_hrnet_gpu.py::test_fused_logsoftmax_decode_is_bit_identical asserts at 140x240 (only head32 fuses the decode)."""
+    sd = _weights('hrnet_w48')
+    stats = verify_plan(sncal, cuda, 'hrnet_w48', sd, _frames(2, 140, 240, 24, cuda), dtype, tag='w48 140x240 ' + dtype)
+    _report(stats, dtype + '_w48_140x240')
+    assert ('head_fused' if dtype == 'bf16' else 'headx3_fused') in stats, list(stats)      # not some other head path
+
+
 @pytest.mark.parametrize('layers', ['all', 'stage4,c192,c384'])
 def test_every_launch_of_the_fp8_engine_w48_540p(sncal, cuda, layers):
     """C5 arithmetic: the e4m3 convolutions against torch fp32 on the e4m3 codes they read (per-tensor input scale x per-channel
