@@ -426,6 +426,23 @@ int sncal_heatmap_loss(const float* d_logp, const float* d_kpts, const float* d_
                        float stride, int terms, double* d_out, void* d_ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Gradient of that loss with respect to the log-probabilities: one more read of the heatmap, one write of the gradient
+ * replaces torch autograd through HRNetLoss.forward                src/models/hrnet/loss.py:89-144
+ *   d_logp, d_kpts, d_mask, sigma, stride, terms   as for sncal_heatmap_loss; the target is rebuilt and not differentiated
+ *   coef   HOST array read inside the call: the weight of each term over its divisor,
+ *          l2_w / (B*(N+1)*h*w), kldiv_w / B, awing_w / (B*(N+1)*h*w); rounded to fp32 once
+ *   d_gout device fp32 scalar, the upstream gradient (a GradScaler's factor needs no host sync), or NULL for 1
+ *   d_grad (B,N+1,h,w) fp32 = gout * sum_k coef_k * term_k, per element with m the mask entry, e = exp(x*m), t = target*m:
+ *          MSE 2(e - t) e m;  KL -t m;  adaptive wing w'(|t - e|) sign(e - t) e m, where w'(d) = omega a d^(a-1) / (1 + d^a) for
+ *          d < theta and A(t) otherwise, a = alpha - t, and sign(0) = 0.  A term whose bit is clear is not evaluated.
+ *   d_ws   scratch of sncal_heatmap_loss_workspace bytes (only its tables' share is used), 16-byte aligned
+ * Limits and statuses of sncal_heatmap_loss.  No atomics and no reduction: two runs give the same bits.  Asynchronous on `stream`.
+ * ---------------------------------------------------------------------------------------------- */
+int sncal_heatmap_loss_grad(const float* d_logp, const float* d_kpts, const float* d_mask, int B, int N, int h, int w,
+                            float sigma, float stride, int terms, const double coef[3], const float* d_gout,
+                            float* d_grad, void* d_ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Line model, validation tail: target maps, fused loss, accuracy counts
  *
  * sncal_line_target replaces EHMDataset._generate_keypoint_maps / _add_gaussian      src/models/line/dataset.py:107-178
@@ -452,12 +469,25 @@ int sncal_heatmap_loss(const float* d_logp, const float* d_kpts, const float* d_
  *   pred_exists = pred[i,2] >= p_threshold, within = min_j |gt[i,:2] - pred[j,:2]| <= t over BOTH predicted points;
  *   tp += gt & pred & within, fn += gt & ~pred, fp += pred & ~gt, fp += gt & pred & ~within (the reference's pairing by slot)
  *
- * All three are asynchronous on `stream`; the library allocates nothing.
+ * sncal_ehm_loss_grad replaces torch autograd through EHMLoss.forward                src/models/line/loss.py:61-108
+ *   (named after the class: tests/test_validate_line_host.py pins the set of sncal_line_* names to the validation tail's five)
+ *   d_pred, d_target / d_kpts, target_sigma, stride, gmse_sigma, terms   as for sncal_line_loss; the target is not differentiated
+ *   coef     HOST array read inside the call: gmse_w / (B*C*h*w), awing_w / (B*C*h*w); rounded to fp32 once
+ *   d_gout   device fp32 scalar, the upstream gradient, or NULL for 1
+ *   d_grad   (B,C,h,w) fp32 = gout * sum_k coef_k * term_k with d = pred - target, u = d^2 / (2 gmse_sigma^2):
+ *            GMSE 2 d exp(-u) (1 - u);  adaptive wing w'(|d|) sign(d), w' as in sncal_heatmap_loss_grad, sign(0) = 0
+ *   d_ws     scratch of sncal_line_loss_workspace bytes when d_kpts is given (only its tables' share is used); unused with d_target
+ *   Fed sncal_line_target's output as d_target it writes the bits the d_kpts form writes.  No atomics, no reduction.
+ *
+ * All four are asynchronous on `stream`; the library allocates nothing.
  * ---------------------------------------------------------------------------------------------- */
 int sncal_line_target(const float* d_kpts, int B, int C, float sigma, float stride, int h, int w, float* d_out, void* stream);
 int sncal_line_loss_workspace(int B, int C, int h, int w, size_t* bytes);
 int sncal_line_loss(const float* d_pred, const float* d_target, const float* d_kpts, int B, int C, int h, int w, float target_sigma,
                     float stride, float gmse_sigma, int terms, double* d_out, void* d_ws, size_t ws_bytes, void* stream);
+int sncal_ehm_loss_grad(const float* d_pred, const float* d_target, const float* d_kpts, int B, int C, int h, int w,
+                         float target_sigma, float stride, float gmse_sigma, int terms, const double coef[2],
+                         const float* d_gout, float* d_grad, void* d_ws, size_t ws_bytes, void* stream);
 int sncal_line_acc_counts(const float* d_gt, const float* d_pred, int B, int C, float p_threshold, const float* ts, int n_t,
                           long long* d_out, void* stream);
 

@@ -131,12 +131,16 @@ SIGNATURES = {
                                                     ctypes.POINTER(ctypes.c_size_t)]),
     'sncal_heatmap_loss': (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                           ctypes.c_float, ctypes.c_int, vp, vp, ctypes.c_size_t, vp]),
+    'sncal_heatmap_loss_grad': (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                               ctypes.c_float, ctypes.c_int, c_double_p, vp, vp, vp, ctypes.c_size_t, vp]),
     'sncal_line_target': (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int,
                                          vp, vp]),
     'sncal_line_loss_workspace': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                  ctypes.POINTER(ctypes.c_size_t)]),
     'sncal_line_loss': (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                        ctypes.c_float, ctypes.c_float, ctypes.c_int, vp, vp, ctypes.c_size_t, vp]),
+    'sncal_ehm_loss_grad': (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
+                                            ctypes.c_float, ctypes.c_float, ctypes.c_int, c_double_p, vp, vp, vp, ctypes.c_size_t, vp]),
     'sncal_line_acc_counts': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_float_p, ctypes.c_int, vp, vp]),
     'sncal_calibrate': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.POINTER(VoterCfg), vp, vp]),
     'sncal_calibrate_workspace': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(VoterCfg), ctypes.POINTER(ctypes.c_size_t)]),

@@ -1,5 +1,5 @@
-// The validation tail of the line model: the two-peak target maps, EHMLoss.forward for num_refinement_stages = 0 in ONE read of
-// the softmax heatmap, and the tp / fp / fn counts of AccMetric
+// The loss and validation tail of the line model: the two-peak target maps, EHMLoss.forward for num_refinement_stages = 0 in ONE
+// read of the softmax heatmap, its gradient in one more read and one write, and the tp / fp / fn counts of AccMetric
 //   /root/reference/src/models/line/dataset.py:107-178 (_generate_keypoint_maps, _add_gaussian)
 //   /root/reference/src/models/line/loss.py:34-108     (forward, gmse_loss, adaptive_wing)
 //   /root/reference/src/models/line/metrics.py:53-103  (a_t_score)
@@ -18,6 +18,10 @@
 //                       workgroup; line_fold_kernel adds the partials of a frame in index order.  No atomics: two runs give the
 //                       same bits.  REBUILD = false reads the target from memory instead (maps as a loader delivers them); fed
 //                       with sncal_line_target's output it sees the very values REBUILD = true forms, in the same order.
+//   sncal_ehm_loss_grad    the gradient of that loss with respect to the prediction (torch autograd through line/loss.py:61-108,
+//                       the target held fixed): line_grad_kernel is line_loss_kernel's tiling and its two forms with a store in
+//                       place of the sums -- prediction read once, gradient written once, gout * sum_k coef_k * term_k in fp32.
+//                       The maps form needs no table and no workspace; on sncal_line_target's output it writes the rebuild form's bits.
 //   sncal_line_acc_counts   one workgroup; a thread walks (frame, channel) pairs with integer counters, then a fixed-order fold
 // exp in the GMSE term is expf (1 ulp), as in loss.hip.  The wing arithmetic is awing.hpp's and the lane / wave helpers are tile.hpp's, both shared with
 // loss.hip.
@@ -183,6 +187,79 @@ void launch(int terms, dim3 grid, hipStream_t st, const float* pred, const float
 #undef LL_CASE
 }
 
+struct Coef2 { float c[2]; };
+
+// The tiling, the two forms and the target arithmetic of line_loss_kernel; each element's gradient with respect to the prediction
+// is stored where the prediction was read (no sums: no reduction, no partials)
+//   d^2 exp(-d^2 / 2s^2), d = p - t   ->  2 d exp(-u) (1 - u),  u = d^2 / 2s^2
+//   adaptive_wing(p, t)               ->  w'(|t - p|) sign(p - t)
+template <bool REBUILD, int V, bool GMSE, bool AW>
+__global__ __launch_bounds__(256) void line_grad_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                        const float* __restrict__ gxt, const float* __restrict__ gyt, int C, int h, int w,
+                                                        float two_gs2, Coef2 cf, const float* __restrict__ gout, float* __restrict__ grad) {
+    using VT = typename Vec<V>::type;
+    __shared__ float s_gy[REBUILD ? LL_MAXC : 1][2][LS_ROWS];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, b = blockIdx.z;
+    const int y0 = blockIdx.y * LS_ROWS, x0 = (blockIdx.x * 64 + lane) * V;
+    if (REBUILD) {
+        for (int i = t; i < C * 2 * LS_ROWS; i += 256) {
+            const int cp = i / LS_ROWS, r = i - cp * LS_ROWS;   // cp = c * 2 + p
+            s_gy[cp >> 1][cp & 1][r] = y0 + r < h ? gyt[((size_t)b * C * 2 + cp) * h + y0 + r] : 0.f;
+        }
+        __syncthreads();
+    }
+    const int yw = y0 + wv * LS_R;
+    const int rows = min(LS_R, h - yw);
+    if (x0 >= w || rows <= 0) return;                           // w % V == 0, so a live lane owns V whole columns
+    const float go = gout ? *gout : 1.0f;
+    const size_t plane = (size_t)h * w, off = (size_t)b * C * plane + (size_t)yw * w + x0;
+#pragma unroll 2
+    for (int c = 0; c < C; ++c) {
+        VT pv[LS_R], tv[LS_R], cx0, cx1;
+        if (REBUILD) {
+            cx0 = *reinterpret_cast<const VT*>(gxt + ((size_t)b * C + c) * 2 * w + x0);
+            cx1 = *reinterpret_cast<const VT*>(gxt + (((size_t)b * C + c) * 2 + 1) * w + x0);
+        }
+#pragma unroll
+        for (int r = 0; r < LS_R; ++r)
+            if (r < rows) {
+                pv[r] = *reinterpret_cast<const VT*>(pred + off + (size_t)c * plane + (size_t)r * w);
+                if (!REBUILD) tv[r] = *reinterpret_cast<const VT*>(target + off + (size_t)c * plane + (size_t)r * w);
+            }
+#pragma unroll
+        for (int r = 0; r < LS_R; ++r) {
+            if (r < rows) {
+                float cy0 = 0.f, cy1 = 0.f;
+                if (REBUILD) { cy0 = s_gy[c][0][wv * LS_R + r]; cy1 = s_gy[c][1][wv * LS_R + r]; }
+                float gv[V];
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const float p = lane_of(pv[r], j);
+                    const float tt = REBUILD ? line_target_value(lane_of(cx0, j), cy0, lane_of(cx1, j), cy1) : lane_of(tv[r], j);
+                    float g = 0.f;
+                    if (GMSE) {
+                        const float d = p - tt, u = d * d / two_gs2;
+                        g += cf.c[0] * (2.0f * d * expf(-u) * (1.0f - u));
+                    }
+                    if (AW) g += cf.c[1] * sncal::adaptive_wing_grad(p, tt);
+                    gv[j] = go * g;
+                }
+                float* const o = grad + off + (size_t)c * plane + (size_t)r * w;
+                if constexpr (V == 4) *reinterpret_cast<float4*>(o) = make_float4(gv[0], gv[1], gv[2], gv[3]);
+                else *o = gv[0];
+            }
+        }
+    }
+}
+
+template <bool REBUILD, int V>
+void launch_grad(int terms, dim3 grid, hipStream_t st, const float* pred, const float* target, const float* gx, const float* gy, int C, int h,
+                 int w, float two_gs2, Coef2 cf, const float* gout, float* grad) {
+#define LL_CASE(T, G, A) case T: hipLaunchKernelGGL((line_grad_kernel<REBUILD, V, G, A>), grid, dim3(256), 0, st, pred, target, gx, gy, C, h, w, two_gs2, cf, gout, grad); break;
+    switch (terms) { LL_CASE(1, true, false) LL_CASE(2, false, true) LL_CASE(3, true, true) }
+#undef LL_CASE
+}
+
 struct AccTs { float t[ACC_MAXT]; };
 
 // metrics.py:70-98 per (frame, channel); the pairing is by slot index i, the nearest prediction is taken over both slots
@@ -297,6 +374,52 @@ extern "C" int sncal_line_loss(const float* d_pred, const float* d_target, const
     }
     SNCAL_CHECK_LAUNCH();
     hipLaunchKernelGGL(line_fold_kernel, dim3((B * 2 + 63) / 64), dim3(64), 0, st, part, B, L.bx * L.by, d_out);
+    SNCAL_CHECK_LAUNCH();
+    return SNCAL_OK;
+}
+
+extern "C" int sncal_ehm_loss_grad(const float* d_pred, const float* d_target, const float* d_kpts, int B, int C, int h, int w,
+                                    float target_sigma, float stride, float gmse_sigma, int terms, const double coef[2],
+                                    const float* d_gout, float* d_grad, void* d_ws, size_t ws_bytes, void* stream) {
+    SNCAL_CHECK_ARG(B >= 0 && C > 0 && C <= LL_MAXC && h > 0 && w > 0, "sncal_ehm_loss_grad: B=%d C=%d h=%d w=%d (C <= %d)", B, C, h, w,
+                    LL_MAXC);
+    SNCAL_CHECK_ARG(terms >= 0 && terms <= 3, "sncal_ehm_loss_grad: terms %d (bit0 gmse, bit1 awing)", terms);
+    SNCAL_CHECK_ARG(!(terms & 1) || gmse_sigma > 0.f, "sncal_ehm_loss_grad: gmse_sigma %g", (double)gmse_sigma);
+    SNCAL_CHECK_ARG(coef, "sncal_ehm_loss_grad: null coef");
+    if (B == 0) return SNCAL_OK;                                // before the pointers: an empty tensor's is NULL
+    SNCAL_CHECK_ARG((d_target != nullptr) != (d_kpts != nullptr), "sncal_ehm_loss_grad: exactly one of d_target and d_kpts must be given");
+    if (d_kpts) {
+        SNCAL_CHECK_ARG(target_sigma > 0.f, "sncal_ehm_loss_grad: target_sigma %g", (double)target_sigma);
+        SNCAL_CHECK_ARG(stride > 0.f, "sncal_ehm_loss_grad: stride %g", (double)stride);
+    }
+    SNCAL_CHECK_ARG(d_pred && d_grad, "sncal_ehm_loss_grad: null pointer");
+    hipStream_t st = sncal::as_stream(stream);
+    if (terms == 0) {
+        SNCAL_CHECK_HIP(hipMemsetAsync(d_grad, 0, (size_t)B * C * h * w * sizeof(float), st));
+        return SNCAL_OK;
+    }
+    const int V = (w % 4 == 0 && aligned16(d_pred) && aligned16(d_grad) && (!d_target || aligned16(d_target))) ? 4 : 1;
+    const Layout L = layout(B, C, h, w, V);
+    SNCAL_CHECK_ARG(B <= 65535 && L.by <= 65535 && (size_t)B * C <= 0x7fffffffu, "sncal_ehm_loss_grad: grid too large");
+    const float two_gs2 = 2.0f * gmse_sigma * gmse_sigma;
+    const Coef2 cf = {{(float)coef[0], (float)coef[1]}};
+    const dim3 grid(L.bx, L.by, B);
+    if (d_kpts) {
+        SNCAL_CHECK_ARG(d_ws && aligned16(d_ws), "sncal_ehm_loss_grad: workspace pointer null or not 16-byte aligned");
+        if (ws_bytes < L.part) {                                // the tables only: no partial sums here
+            sncal::set_error("sncal_ehm_loss_grad: workspace %zu bytes, need %zu (sncal_line_loss_workspace covers it)", ws_bytes, L.part);
+            return SNCAL_ERR_WORKSPACE;
+        }
+        float* const gx = reinterpret_cast<float*>((char*)d_ws + L.gx);
+        float* const gy = reinterpret_cast<float*>((char*)d_ws + L.gy);
+        hipLaunchKernelGGL(line_tables_kernel, dim3(B * C), dim3(256), 0, st, d_kpts, target_sigma, stride, h, w, gx, gy);
+        SNCAL_CHECK_LAUNCH();
+        if (V == 4) launch_grad<true, 4>(terms, grid, st, d_pred, d_target, gx, gy, C, h, w, two_gs2, cf, d_gout, d_grad);
+        else launch_grad<true, 1>(terms, grid, st, d_pred, d_target, gx, gy, C, h, w, two_gs2, cf, d_gout, d_grad);
+    } else {                                                    // the maps form needs no table, hence no workspace
+        if (V == 4) launch_grad<false, 4>(terms, grid, st, d_pred, d_target, nullptr, nullptr, C, h, w, two_gs2, cf, d_gout, d_grad);
+        else launch_grad<false, 1>(terms, grid, st, d_pred, d_target, nullptr, nullptr, C, h, w, two_gs2, cf, d_gout, d_grad);
+    }
     SNCAL_CHECK_LAUNCH();
     return SNCAL_OK;
 }

@@ -19,6 +19,11 @@
 // 2e-7 absolute, and where the product underflowed to 0 the term is 0 either way).  The background channel and channels whose mask
 // is neither 0 nor 1 take a real logf.  exp of the prediction is expf (1 ulp), not the fast intrinsic: the intrinsic's argument
 // scaling is biased by the rounding of log2(e), which does not average out over a sum.
+// Gradient (sncal_heatmap_loss_grad, what torch autograd gives through loss.py:89-144 with the target held fixed): the losses are
+// elementwise given the tables, so loss_grad_kernel is loss_kernel's tiling and channel walk with a store in place of the sums --
+// the prediction read once, the gradient written once (16-byte stores when V = 4), the background channel's last because its target
+// needs the running max.  grad = gout * m * sum_k coef_k * term_k in fp32, coef_k = weight / divisor from the host, gout a device
+// scalar (NULL = 1).  No partials, no fold, no atomics.  What was measured is in profiles/loss_grad.md.
 // Cost per element with the default terms: one expf + about a dozen fp32 ops and a share of a float2 table load.  Which of HBM
 // or VALU issue bounds each variant is a question for measurement, not for this header: profiles/validate_loss.md holds what was
 // measured (kernel times from a trace, algorithmic bytes over time against the HBM rate) and says so where nothing was.
@@ -174,6 +179,100 @@ void launch(int terms, dim3 grid, hipStream_t st, const float* logp, const float
 
 int vec_width(const float* d_logp, int w) { return (w % 4 == 0 && ((uintptr_t)d_logp & 15) == 0) ? 4 : 1; }
 
+struct Coef3 { float c[3]; };
+
+// d/dx of the three terms at one element, x the logit, p = x * m, t = target * m; the common factor m is applied by the caller
+//   (exp(p) - t)^2          ->  2 (e - t) e
+//   xlogy(t, t) - t p       ->  -t                       (0 where t = 0)
+//   adaptive_wing(e, t)     ->  w'(|t - e|) sign(e - t) e
+template <bool MSE, bool KL, bool AW>
+__device__ __forceinline__ float grad_element(float p, float t, const Coef3& cf) {
+    const float e = expf(p);
+    float g = 0.f;
+    if (MSE) g += cf.c[0] * (2.0f * (e - t) * e);
+    if (KL) g += cf.c[1] * -t;
+    if (AW) g += cf.c[2] * (sncal::adaptive_wing_grad(e, t) * e);
+    return g;
+}
+
+// The tiling and the channel walk of loss_kernel; each element's gradient is stored where its logit was read.  No sums, so no
+// LDS reduction and no partials: a lane's V gradients of a row go out in one store.
+template <int V, bool MSE, bool KL, bool AW>
+__global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict__ logp, const float* __restrict__ mask,
+                                                        const float2* __restrict__ gxt, const float2* __restrict__ gyt, int N, int h, int w,
+                                                        Coef3 cf, const float* __restrict__ gout, float* __restrict__ grad) {
+    using VT = typename Vec<V>::type;
+    __shared__ float s_gy[LS_MAXN][LS_ROWS];
+    __shared__ float s_m[LS_MAXN + 1];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, b = blockIdx.z;
+    const int y0 = blockIdx.y * LS_ROWS, x0 = (blockIdx.x * 64 + lane) * V;
+    for (int i = t; i < N * LS_ROWS; i += 256) {
+        const int n = i / LS_ROWS, r = i - n * LS_ROWS;
+        s_gy[n][r] = y0 + r < h ? gyt[((size_t)b * N + n) * h + y0 + r].x : 0.f;
+    }
+    for (int i = t; i <= N; i += 256) s_m[i] = mask ? mask[(size_t)b * (N + 1) + i] : 1.0f;
+    __syncthreads();
+    const int yw = y0 + wv * LS_R;
+    const int rows = min(LS_R, h - yw);
+    if (x0 >= w || rows <= 0) return;                           // w % V == 0, so a live lane owns V whole columns
+    const float go = gout ? *gout : 1.0f;
+    const size_t plane = (size_t)h * w, off = (size_t)b * (N + 1) * plane + (size_t)yw * w + x0;
+    float mx[LS_R][V];
+#pragma unroll
+    for (int r = 0; r < LS_R; ++r)
+#pragma unroll
+        for (int j = 0; j < V; ++j) mx[r][j] = 0.f;
+#pragma unroll 2
+    for (int n = 0; n <= N; ++n) {
+        const bool bg = n == N;
+        const float m = s_m[n];
+        float cx[V];
+        if (!bg) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) cx[j] = gxt[((size_t)b * N + n) * w + x0 + j].x;
+        }
+        VT pv[LS_R];
+#pragma unroll
+        for (int r = 0; r < LS_R; ++r)
+            if (r < rows) pv[r] = *reinterpret_cast<const VT*>(logp + off + (size_t)n * plane + (size_t)r * w);
+#pragma unroll
+        for (int r = 0; r < LS_R; ++r) {
+            if (r < rows) {
+                const float cy = bg ? 0.f : s_gy[n][wv * LS_R + r];
+                float gv[V];
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    float p = lane_of(pv[r], j), tt;
+                    if (!bg) {
+                        tt = cx[j] * cy;                        // the target of loss_kernel, formed the same way
+                        mx[r][j] = fmaxf(mx[r][j], tt);
+                    } else {
+                        tt = 1.0f - mx[r][j];
+                    }
+                    if (m != 1.0f) { p *= m; tt *= m; }
+                    float g = grad_element<MSE, KL, AW>(p, tt, cf);
+                    if (m != 1.0f) g *= m;                      // d(x * m) / dx
+                    gv[j] = go * g;
+                }
+                float* const o = grad + off + (size_t)n * plane + (size_t)r * w;
+                if constexpr (V == 4) *reinterpret_cast<float4*>(o) = make_float4(gv[0], gv[1], gv[2], gv[3]);
+                else *o = gv[0];
+            }
+        }
+    }
+}
+
+template <int V>
+void launch_grad(int terms, dim3 grid, hipStream_t st, const float* logp, const float* mask, const float2* gx, const float2* gy, int N, int h,
+                 int w, Coef3 cf, const float* gout, float* grad) {
+#define LS_CASE(T, A, B_, C) case T: hipLaunchKernelGGL((loss_grad_kernel<V, A, B_, C>), grid, dim3(256), 0, st, logp, mask, gx, gy, N, h, w, cf, gout, grad); break;
+    switch (terms) {
+        LS_CASE(1, true, false, false) LS_CASE(2, false, true, false) LS_CASE(3, true, true, false) LS_CASE(4, false, false, true)
+        LS_CASE(5, true, false, true) LS_CASE(6, false, true, true) LS_CASE(7, true, true, true)
+    }
+#undef LS_CASE
+}
+
 }  // namespace
 
 extern "C" int sncal_heatmap_loss_workspace(int B, int N, int h, int w, size_t* bytes) {
@@ -215,6 +314,42 @@ extern "C" int sncal_heatmap_loss(const float* d_logp, const float* d_kpts, cons
     else launch<1>(terms, grid, st, d_logp, d_mask, gx, gy, N, h, w, part);
     SNCAL_CHECK_LAUNCH();
     hipLaunchKernelGGL(loss_fold_kernel, dim3((B * 3 + 63) / 64), dim3(64), 0, st, part, B, L.bx * L.by, d_out);
+    SNCAL_CHECK_LAUNCH();
+    return SNCAL_OK;
+}
+
+extern "C" int sncal_heatmap_loss_grad(const float* d_logp, const float* d_kpts, const float* d_mask, int B, int N, int h, int w,
+                                       float sigma, float stride, int terms, const double coef[3], const float* d_gout, float* d_grad,
+                                       void* d_ws, size_t ws_bytes, void* stream) {
+    SNCAL_CHECK_ARG(B >= 0 && N > 0 && N <= LS_MAXN && h > 0 && w > 0, "sncal_heatmap_loss_grad: B=%d N=%d h=%d w=%d (N <= %d)", B, N, h, w,
+                    LS_MAXN);
+    SNCAL_CHECK_ARG(sigma > 0.f, "sncal_heatmap_loss_grad: sigma %g", (double)sigma);
+    SNCAL_CHECK_ARG(stride > 0.f, "sncal_heatmap_loss_grad: stride %g", (double)stride);
+    SNCAL_CHECK_ARG(terms >= 0 && terms <= 7, "sncal_heatmap_loss_grad: terms %d (bit0 mse, bit1 kl, bit2 awing)", terms);
+    SNCAL_CHECK_ARG(coef, "sncal_heatmap_loss_grad: null coef");
+    if (B == 0) return SNCAL_OK;
+    SNCAL_CHECK_ARG(d_logp && d_kpts && d_grad, "sncal_heatmap_loss_grad: null pointer");
+    hipStream_t st = sncal::as_stream(stream);
+    if (terms == 0) {
+        SNCAL_CHECK_HIP(hipMemsetAsync(d_grad, 0, (size_t)B * (N + 1) * h * w * sizeof(float), st));
+        return SNCAL_OK;
+    }
+    const int V = vec_width(d_logp, w) == 4 && vec_width(d_grad, w) == 4 ? 4 : 1;
+    const Layout L = layout(B, N, h, w, V);
+    SNCAL_CHECK_ARG(B <= 65535 && L.by <= 65535 && (size_t)B * N <= 0x7fffffffu, "sncal_heatmap_loss_grad: grid too large");
+    SNCAL_CHECK_ARG(d_ws && ((uintptr_t)d_ws & 15) == 0, "sncal_heatmap_loss_grad: workspace pointer null or not 16-byte aligned");
+    if (ws_bytes < L.part) {                                    // the tables only: no partial sums here
+        sncal::set_error("sncal_heatmap_loss_grad: workspace %zu bytes, need %zu (sncal_heatmap_loss_workspace covers it)", ws_bytes, L.part);
+        return SNCAL_ERR_WORKSPACE;
+    }
+    float2* const gx = reinterpret_cast<float2*>((char*)d_ws + L.gx);
+    float2* const gy = reinterpret_cast<float2*>((char*)d_ws + L.gy);
+    const Coef3 cf = {{(float)coef[0], (float)coef[1], (float)coef[2]}};
+    hipLaunchKernelGGL(loss_tables_kernel, dim3(B * N), dim3(256), 0, st, d_kpts, N, sigma, stride, h, w, gx, gy);
+    SNCAL_CHECK_LAUNCH();
+    const dim3 grid(L.bx, L.by, B);
+    if (V == 4) launch_grad<4>(terms, grid, st, d_logp, d_mask, gx, gy, N, h, w, cf, d_gout, d_grad);
+    else launch_grad<1>(terms, grid, st, d_logp, d_mask, gx, gy, N, h, w, cf, d_gout, d_grad);
     SNCAL_CHECK_LAUNCH();
     return SNCAL_OK;
 }
