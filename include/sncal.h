@@ -492,6 +492,52 @@ int sncal_line_acc_counts(const float* d_gt, const float* d_pred, int B, int C, 
                           long long* d_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Train-time augmentation, fused: colour, noise, flip, and the uint8 / fp32 CHW output in one pass
+ * replaces ColorAugment, GaussNoise, Flip (image side), ToTensor      src/models/hrnet/transforms.py:16-68, 122-133
+ *          (the line model's copies: src/models/line/transforms.py:10-139)
+ *   d_src    (B,H,W,3) uint8, the JPEG stage's output
+ *   d_params DEVICE array of B entries: one frame's draws, made on the host in the reference's order (augment.py)
+ *   d_noise  (B,H,W,3) fp64 normals in SOURCE coordinates (read only for frames with the noise flag), or NULL;
+ *            it may not overlap an output (SNCAL_ERR_ARG), and a base off a 16-byte boundary selects the narrow path
+ *   d_dst    (B,H,W,3) uint8 or NULL;  d_chw (B,3,H,W) fp32 or NULL = ToTensor: float(v) / 255.0f, the correctly rounded division
+ *            that torch.div is on the host, where the reference's ToTensor runs (on the device torch multiplies by
+ *            float32(1 / 255) instead, which differs in the last bit for 126 of the 256 byte values).  At least one is non-NULL; requested together they hold the same values.
+ * Each frame passes the reference's stages in the reference's order, each gated by its flag, with the reference's uint8
+ * truncation between them:
+ *   colour   p = double(x) * gain[c];  v = (p - mean[c]) * contrast + mean[c];  clip to [0, 255];  truncate -- fp64 in numpy's
+ *            operation order, no contraction.  mean[c] = double(S_c) * gain[c] / double(H*W) with S_c the EXACT integer sum of the
+ *            channel (a first kernel, no atomics); numpy sums the rounded products instead, which moves the mean by parts in 1e12
+ *            and can change a truncated value only where v lies that close to an integer.
+ *   noise    d_noise given: v = double(u8) + d_noise[b,y,x,c], clip, truncate toward zero (fp64): the reference's arithmetic on the
+ *            caller's normals.  d_noise NULL: v = float(u8) + float(noise_sigma) * z, clip, truncate (fp32), z from the device
+ *            generator below.
+ *   flip     out[b, y, W-1-x, :] = v[b, y, x, :]                                                       (cv2.flip(img, 1))
+ * Device noise -- a KNOWN DEVIATION from the reference's numbers, like the RANSAC sampling of sncal_calibrate above: GaussNoise draws
+ * H*W*3 doubles from numpy's MT19937 stream, which a device cannot replay in parallel.  Here z comes from Philox4x32-10 keyed by
+ * the frame's `seed`; the counter is the index of the element quad in the frame's flat SOURCE order (element (y*W + x)*3 + c, four
+ * per counter); Box-Muller in fp32 turns the four uniforms into four normals (|z| < 5.8).  A frame's noise depends on its seed and on
+ * its pixels' source positions and on nothing else: not on its place in the batch, the tiling, the pointers' alignment or the flip
+ * flag.  Same distribution, other numbers.
+ * d_src may not overlap an output (SNCAL_ERR_ARG): the flip reads and writes different columns.  B == 0 returns SNCAL_OK without
+ * touching a pointer.  d_ws: sncal_augment_workspace bytes, 16-byte aligned (SNCAL_ERR_WORKSPACE when short).  16-byte aligned
+ * pointers and W % 16 == 0 take 16-byte accesses; anything else takes a byte path that writes the same bits.  H*W*3 < 2^31,
+ * B <= 65535.  Asynchronous on `stream`; the library allocates nothing; no atomics, two runs give the same bits.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {            /* one frame's draws; what the reference takes from random / np.random */
+    double gain[3];         /* ColorAugment: brightness * color[c], in the frame's channel order   */
+    double contrast;
+    double noise_sigma;     /* GaussNoise: the value drawn by np.random.uniform(0, sigma_sq), used as the scale */
+    uint64_t seed;          /* device noise stream of this frame */
+    uint32_t flags;         /* bit0 colour, bit1 noise, bit2 flip */
+    uint32_t reserved;
+} sncal_augment_params;
+
+int sncal_augment_workspace(int B, int H, int W, size_t* bytes);
+int sncal_augment_u8(const unsigned char* d_src, int B, int H, int W, const sncal_augment_params* d_params,
+                     const double* d_noise, unsigned char* d_dst, float* d_chw,
+                     void* d_ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Pipeline plumbing: a stream confined to `cus_per_xcd` compute units of each XCD (for the camera solves)
  * replaces the 16-process CPU pool of make_submit.py:25,53-54,69 (ProcessPoolExecutor workers beside the GPU loop): the solves of
  * up to four batches run beside the network on these streams; what they may occupy is bounded by the mask instead of by a process

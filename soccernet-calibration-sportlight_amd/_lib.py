@@ -76,6 +76,12 @@ class JpegInfo(ctypes.Structure):
                 ('blocks', ctypes.c_int32 * 3)]
 
 
+class AugmentParams(ctypes.Structure):
+    """sncal_augment_params."""
+    _fields_ = [('gain', ctypes.c_double * 3), ('contrast', ctypes.c_double), ('noise_sigma', ctypes.c_double),
+                ('seed', ctypes.c_uint64), ('flags', ctypes.c_uint32), ('reserved', ctypes.c_uint32)]
+
+
 # name -> (restype, argtypes); must list every function include/sncal.h declares
 SIGNATURES = {
     'sncal_version': (ctypes.c_int, []),
@@ -142,6 +148,8 @@ SIGNATURES = {
     'sncal_ehm_loss_grad': (ctypes.c_int, [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                             ctypes.c_float, ctypes.c_float, ctypes.c_int, c_double_p, vp, vp, vp, ctypes.c_size_t, vp]),
     'sncal_line_acc_counts': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_float_p, ctypes.c_int, vp, vp]),
+    'sncal_augment_workspace': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    'sncal_augment_u8': (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
     'sncal_calibrate': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.POINTER(VoterCfg), vp, vp]),
     'sncal_calibrate_workspace': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(VoterCfg), ctypes.POINTER(ctypes.c_size_t)]),
     'sncal_calibrate_ws': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.POINTER(VoterCfg), vp, vp, ctypes.c_size_t, vp]),

@@ -131,19 +131,48 @@ def decoded_batches(folder: str, names: Sequence[str], batch_size: int, device, 
 
 
 def folder_batches(folder: str, batch_size: int, device, num_keypoints: int, margin: float, img_size, decoder_threads: int,
-                   skipped: List[str]) -> Iterator[dict]:
+                   skipped: List[str], transform=None) -> Iterator[dict]:
     """The batch dicts of a split folder, frames decoded on the device as uint8 BGR.  A file the decoder cannot take is left out
-    of its batch and named in `skipped`."""
+    of its batch and named in `skipped`.  transform: None, or the label transform of the reference's validation loader
+    (augment.test_transform(): FixLRAmbiguous), applied to each annotation before scale_points and annot_to_keypoints as
+    HRNetDataset.__getitem__ does (dataset.py:60-64)."""
     names, annots = list_split(folder)
+    if transform is not None:
+        annots = [transform.labels(a) for a in annots]
     frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped)
     try:
         for keep, image in frames:
-            pairs = [annot_to_keypoints(annots[j], num_keypoints, margin) for j in keep]
-            yield {'image': image,
-                   'keypoints': torch.from_numpy(np.stack([p[0] for p in pairs])),
-                   'mask': torch.from_numpy(np.stack([p[1] for p in pairs])),
-                   'raw_annot': [scale_points(annots[j], img_size[0], img_size[1]) for j in keep],
-                   'img_name': [names[j] for j in keep]}
+            yield labelled_batch(image, [annots[j] for j in keep], [names[j] for j in keep], num_keypoints, margin, img_size)
+    finally:
+        frames.close()
+
+
+def labelled_batch(image, annots: Sequence[dict], names: Sequence[str], num_keypoints: int, margin: float, img_size) -> dict:
+    """The reference's batch dict (dataset.py:52-71 + custom_collate) from frames and their (already transformed) annotations."""
+    pairs = [annot_to_keypoints(a, num_keypoints, margin) for a in annots]
+    return {'image': image,
+            'keypoints': torch.from_numpy(np.stack([p[0] for p in pairs])),
+            'mask': torch.from_numpy(np.stack([p[1] for p in pairs])),
+            'raw_annot': [scale_points(a, img_size[0], img_size[1]) for a in annots],
+            'img_name': list(names)}
+
+
+def train_batches(folder: str, batch_size: int, transform, shuffle: bool = True, seed=None, device='cuda:0', num_keypoints: int = 57,
+                  margin: float = 0.0, img_size=(960, 540), decoder_threads: int = 0, skipped: List[str] = None) -> Iterator[dict]:
+    """One epoch of the reference's TRAINING batches (train.py:31-33: HRNetDataset with train_transform under a shuffling loader)
+    of a split folder: {'image', 'keypoints', 'mask', 'raw_annot', 'img_name'}.  Frames are decoded and augmented on the device
+    (augment.train_transform: 'image' is fp32 (B,3,H,W) with ToTensor in the list, uint8 (B,H,W,3) without); the labels come from
+    the transformed annotations.  shuffle draws the epoch's order from numpy.random.RandomState(seed) -- a generator of its own, so
+    the transform's draws from random / numpy.random are those of a run without shuffling.  A file the decoder cannot take is
+    left out of its batch and named in `skipped` (when a list is given); the last batch may be short, as the reference's is."""
+    names, annots = list_split(folder)
+    order = np.random.RandomState(seed).permutation(len(names)) if shuffle else np.arange(len(names))
+    names, annots = [names[j] for j in order], [annots[j] for j in order]
+    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped if skipped is not None else [])
+    try:
+        for keep, image in frames:
+            out = transform({'image': image, 'annot': [annots[j] for j in keep]})
+            yield labelled_batch(out['image'], out['annot'], [names[j] for j in keep], num_keypoints, margin, img_size)
     finally:
         frames.close()
 
@@ -187,7 +216,7 @@ def line_folder_batches(folder: str, batch_size: int, device, num_keypoint_pairs
 
 def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreator, Sequence[CameraCreator]], batch_size: int = 16,
              loss=None, decoder_threads: int = 0, conf_threshold: float = 0.5, pckhs_thres: Sequence[float] = (2.0, 5.0, 10.0, 50.0),
-             threshold: int = 5, img_size=(960, 540)):
+             threshold: int = 5, img_size=(960, 540), transform=None):
     """-> {'val_loss', 'val_l2', 'val_precision', 'val_recall', 'val_pcks-2.0', ..., 'val_l2_reprojection', 'val_completeness',
     'val_eval_precision', 'val_eval_recall', 'val_eval_accuracy', 'val_evalai'} as floats (a ValidationResult).
 
@@ -197,11 +226,17 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
             per calibrator, and a list of results comes back, one per calibrator -- the trials of optimize_valid.yaml without
             running the network once per trial
     loss    an HRNetLoss; default: the model's own (params['loss'] of the checkpoint)
+    transform  folder form only.  None: the annotations as they are on disk.  augment.test_transform(): what the reference's
+            validation loader applies (validate.py:33, train.py:34) -- FixLRAmbiguous mirrors the class names of a behind-the-goal
+            frame annotated the other way round, so val_loss and the keypoint metrics of such frames are taken against the
+            keypoints the reference takes them against
 
     val_loss is the mean of the step losses weighted by step size.  This is the one definition here NOT taken from the reference:
     it is computed by pytorch-argus' Loss metric there, whose source is not part of the reference tree.
     A frame the decoder refuses (folder form) gets no prediction: it is left out of val_loss and the keypoint metrics and counted
     as a missed frame by the camera metrics, as a frame without a camera is.  The host waits for the GPU once, at the end."""
+    if transform is not None and not isinstance(data, (str, os.PathLike)):
+        raise _lib.SncalError('transform applies to the folder form: batches handed in carry their labels already')
     cams = list(camera) if isinstance(camera, (list, tuple)) else [camera]
     own_loss = model.loss
     if loss is not None:
@@ -214,7 +249,8 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
         evals = [EvalAImetric(c, threshold=threshold, img_size=img_size) for c in cams]
         skipped: List[str] = []
         if isinstance(data, (str, os.PathLike)):
-            batches = folder_batches(os.fspath(data), batch_size, model.device, nk, float(loss_fn.sigma), img_size, decoder_threads, skipped)
+            batches = folder_batches(os.fspath(data), batch_size, model.device, nk, float(loss_fn.sigma), img_size, decoder_threads, skipped,
+                                     transform=transform)
         loss_sum = torch.zeros((), dtype=torch.float64, device=model.device)
         frames = 0
         for batch in (batches if batches is not None else data):
