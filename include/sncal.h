@@ -546,6 +546,55 @@ int sncal_augment_u8(const unsigned char* d_src, int B, int H, int W, const snca
 int sncal_stream_create_cu_mask(int cus_per_xcd, void** stream);
 int sncal_stream_destroy(void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Keypoint labels: SoccerNet line / circle annotations -> the 57 keypoint labels of a batch, one launch
+ * replaces get_intersections                       src/datatools/intersections.py:104 (with ellipse.py:275-516 behind it)
+ *          HRNetDataset._annot2keypoints           src/models/hrnet/dataset.py:73-87  (the [x, y, 1] / [-1, -1, 0] rows and the mask)
+ *          FixLRAmbiguous (with SNCAL_LABELS_FIX_LR) src/models/hrnet/transforms.py:136-186
+ * The specification is this build's host restatement, annotations.get_intersections: same stages, same decisions; fp64.
+ *   d_points   (total_points, 2) fp64, NORMALISED image coordinates as annotated, the frames' classes one after the other
+ *   d_offsets  (B, n_classes + 1) int32: frame b's class c owns points [d_offsets[b][c], d_offsets[b][c + 1]); a range that leaves
+ *              [0, total_points] reads as an empty class.  n_classes = 28, the class order is fixed:
+ *                0 Circle central, 1 Circle left, 2 Circle right,
+ *                3..25 the 23 line classes in LINE_CLS order (src/datatools/line.py:35-57): Goal left post left , Goal right post
+ *                right, Middle line, Small rect. right top, Side line bottom, Goal right post left, Big rect. right main, Goal left
+ *                crossbar, Small rect. left bottom, Side line left, Big rect. right top, Small rect. left top, Side line right, Big
+ *                rect. left top, Goal left post right, Small rect. right bottom, Side line top, Goal right crossbar, Small rect. left
+ *                main, Big rect. left main, Big rect. right bottom, Small rect. right main, Big rect. left bottom,
+ *                26 Goal unknown, 27 Line unknown (carried, read by no label)
+ *   d_present  (B) uint32: bit c set = class c is a KEY of the frame's annotation (an empty polyline still counts: FixLRAmbiguous
+ *              counts names, pick_side walks them)
+ *   img_w, img_h, within_image, margin   get_intersections' img_size, within_image, margin
+ *   num_keypoints  N <= 57: rows and mask entries written per frame
+ *   flags      SNCAL_LABELS_FIX_LR: labels at margin 0 first, FixLRAmbiguous.decide on them (threshold 10), d_swapped[b] = its verdict;
+ *              a swapped frame's outputs are those of the annotation renamed by flip_annot_names(swap_top_bottom=False,
+ *              swap_posts=False) -- a fixed permutation of the class ids -- at the caller's margin
+ *   d_samples  (54, 200, 4) uint8: at index n (5 <= n <= 53) the 200 index quadruples numpy draws for n correspondences with
+ *              Generator(PCG64(12345)).choice(n, 4, replace=False), the host RANSAC's sequence (annotations.ransac_samples); entries
+ *              below 5 are not read (4 correspondences are one hypothesis on 0..3).  An index >= n is clamped to n - 1.
+ *   d_keypoints (B, 3N) fp32 rows [x, y, 1], or [-1, -1, 0] for an absent label;  d_mask (B, N + 1) int64 ones, zero at the ids
+ *              30..56 that neither the circles nor the homography produced
+ *   d_labels   (B, 57, 2) fp64 labels before the fp32 rounding (NaN where absent) with d_label_present (B, 57) bytes, or both NULL
+ *   d_swapped  (B) bytes; may be NULL without the flag
+ *   d_ws       sncal_keypoint_labels_workspace bytes (0 in this version: a frame's state lives in its workgroup's LDS and polylines
+ *              of any length are read where they lie); may be NULL when that is 0
+ * Degenerate 4-point samples: exactly three collinear PITCH points give the host's DLT one exact solution, the rank-one d4 l^T
+ * (every point off the line l lands on the fourth point's image, a point on it is 0 / 0 = NaN), which is restated; it decides a
+ * frame only when it is the one hypothesis of n == 4.  Declared deviations from the host path, rounding apart: any other degenerate
+ * sample (four collinear pitch points, collinear image points) is skipped, where the host's SVD returns a vector of a null space of
+ * more than one dimension; the ellipse's eigenvector comes from the characteristic cubic, so a fit whose 3x3 has a complex pair is
+ * judged on its real eigenvector alone.
+ * One wavefront per frame, plain stores, no atomics: two runs write the same bits.  B == 0 returns SNCAL_OK without touching a
+ * pointer.  Asynchronous on `stream`; the library allocates nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define SNCAL_LABELS_FIX_LR 1u
+int sncal_keypoint_labels_workspace(int B, int total_points, size_t* bytes);
+int sncal_keypoint_labels(const double* d_points, int total_points, const int* d_offsets, const unsigned* d_present, int B,
+                          int n_classes, int img_w, int img_h, int within_image, double margin, int num_keypoints,
+                          unsigned flags, const unsigned char* d_samples, float* d_keypoints, long long* d_mask,
+                          double* d_labels, unsigned char* d_label_present, unsigned char* d_swapped, void* d_ws,
+                          size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -150,6 +150,10 @@ SIGNATURES = {
     'sncal_line_acc_counts': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, c_float_p, ctypes.c_int, vp, vp]),
     'sncal_augment_workspace': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     'sncal_augment_u8': (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
+    'sncal_keypoint_labels_workspace': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    'sncal_keypoint_labels': (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_uint, vp, vp, vp, vp, vp, vp, vp,
+                                             ctypes.c_size_t, vp]),
     'sncal_calibrate': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.POINTER(VoterCfg), vp, vp]),
     'sncal_calibrate_workspace': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(VoterCfg), ctypes.POINTER(ctypes.c_size_t)]),
     'sncal_calibrate_ws': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.POINTER(VoterCfg), vp, vp, ctypes.c_size_t, vp]),

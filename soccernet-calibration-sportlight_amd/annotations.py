@@ -421,3 +421,101 @@ def line_keypoints(labels: Dict[int, Optional[tuple]], num_keypoint_pairs: int =
             kp[i * 6 + 2] = kp[i * 6 + 5] = 0
             paras.append((np.nan, np.nan))
     return kp, paras
+
+
+# ---- keypoint labels on the device (csrc/labels.hip) -----------------------------------------------------------------
+
+# the class ids of sncal_keypoint_labels: the three circles, the 23 LINE_CLS lines, the two classes SoccerNet annotates and no label
+# reads.  A class outside this order raises KeyError in pack_annotations, as augment.mirror_labels' lookup does.
+ANNOT_CLASSES: Tuple[str, ...] = (tuple(CONIC_POINTS) + tuple(LINE_CLS[i] for i in range(len(LINE_CLS)))
+                                  + ('Goal unknown', 'Line unknown'))
+LABELS_FIX_LR, LABELS_MAX_KNOWN = 1, 53
+_SAMPLES = {}            # device -> the uploaded sample tables
+
+
+def _xy(p):
+    return (p['x'], p['y']) if isinstance(p, dict) else (p[0], p[1])
+
+
+def pack_annotations(annots):
+    """B annotations {class: [{'x', 'y'} or (x, y), ...]} (normalised) -> (points (P,2) float64, offsets (B, n_classes + 1) int32,
+    present (B,) int32): frame b's class c owns points[offsets[b, c]:offsets[b, c + 1]], classes in ANNOT_CLASSES order, frames one
+    after the other; bit c of present[b] says that the class is a KEY of the dict (an empty list still counts)."""
+    cid = {c: i for i, c in enumerate(ANNOT_CLASSES)}
+    B, C = len(annots), len(ANNOT_CLASSES)
+    offsets = np.zeros((B, C + 1), dtype=np.int32)
+    present = np.zeros(B, dtype=np.int32)
+    rows, at = [], 0
+    for b, annot in enumerate(annots):
+        by_id = {cid[name]: pts for name, pts in annot.items()}                # KeyError: a class outside the order
+        for c in range(C):
+            offsets[b, c] = at
+            if c in by_id:
+                present[b] |= 1 << c
+                rows.extend(_xy(p) for p in by_id[c])
+                at += len(by_id[c])
+        offsets[b, C] = at
+    points = np.asarray(rows, dtype=np.float64).reshape(-1, 2)
+    return points, offsets, present
+
+
+def unpack_annotations(points, offsets, present):
+    """pack_annotations' inverse: a list of {class: [(x, y), ...]}, keys in ANNOT_CLASSES order."""
+    out = []
+    for b in range(len(present)):
+        out.append({name: [(float(x), float(y)) for x, y in points[offsets[b, c]:offsets[b, c + 1]]]
+                    for c, name in enumerate(ANNOT_CLASSES) if (int(present[b]) >> c) & 1})
+    return out
+
+
+def ransac_samples(n: int, iters: int = 200) -> np.ndarray:
+    """The (iters, 4) uint8 index table homography_ransac draws for n > 4 correspondences, from the very calls it makes."""
+    rng = np.random.Generator(np.random.PCG64(12345))
+    return np.stack([rng.choice(n, 4, replace=False) for _ in range(iters)]).astype(np.uint8)
+
+
+def sample_tables() -> np.ndarray:
+    """(LABELS_MAX_KNOWN + 1, 200, 4) uint8: ransac_samples(n) at index n for 5 <= n <= 53 (53 ground-plane keypoints exist), zeros
+    below."""
+    t = np.zeros((LABELS_MAX_KNOWN + 1, 200, 4), dtype=np.uint8)
+    for n in range(5, LABELS_MAX_KNOWN + 1):
+        t[n] = ransac_samples(n)
+    return t
+
+
+def keypoint_labels_device(annots, img_size=(960, 540), within_image: bool = True, margin: float = 0.0, num_keypoints: int = 57,
+                           fix_lr: bool = False, device='cuda:0', return_labels: bool = False):
+    """get_intersections + annot_to_keypoints' packing (+ FixLRAmbiguous with fix_lr) for a batch, in one launch
+    (sncal_keypoint_labels) -> (keypoints (B, 3*num_keypoints) float32, mask (B, num_keypoints + 1) int64, swapped (B,) uint8), on
+    the device; with return_labels also (labels (B,57,2) float64, present (B,57) uint8): the fp64 labels before the float32 rows.
+    swapped[b] = 1: the labels are those of flip_annot_names(annot, False, False), as FixLRAmbiguous would have renamed it."""
+    import ctypes
+    import torch
+    from . import _lib
+    dev = torch.device(device)
+    points, offsets, present = pack_annotations(annots)
+    B, N = len(annots), int(num_keypoints)
+    n = ctypes.c_size_t()
+    _lib.check(_lib.lib().sncal_keypoint_labels_workspace(B, len(points), ctypes.byref(n)), 'sncal_keypoint_labels_workspace')
+    with torch.cuda.device(dev):
+        key = (dev.type, torch.cuda.current_device())
+        if key not in _SAMPLES:
+            _SAMPLES[key] = torch.from_numpy(sample_tables()).to(dev)
+        keypoints = torch.empty((B, 3 * N), dtype=torch.float32, device=dev)
+        mask = torch.empty((B, N + 1), dtype=torch.int64, device=dev)
+        swapped = torch.zeros(B, dtype=torch.uint8, device=dev)
+        labels = torch.empty((B, 57, 2), dtype=torch.float64, device=dev) if return_labels else None
+        lpres = torch.empty((B, 57), dtype=torch.uint8, device=dev) if return_labels else None
+        if B:
+            flat = np.concatenate([points.reshape(-1).view(np.uint8), offsets.reshape(-1).view(np.uint8), present.view(np.uint8)])
+            d_in = torch.from_numpy(flat).to(dev)                             # one upload: points | offsets | present (8-byte multiples first)
+            p_pts = d_in.data_ptr()
+            p_off = p_pts + points.nbytes
+            ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=dev)
+            _lib.check(_lib.lib().sncal_keypoint_labels(
+                p_pts, len(points), p_off, p_off + offsets.nbytes, B, len(ANNOT_CLASSES), int(img_size[0]), int(img_size[1]),
+                int(bool(within_image)), float(margin), N, LABELS_FIX_LR if fix_lr else 0, _SAMPLES[key].data_ptr(),
+                keypoints.data_ptr(), mask.data_ptr(), labels.data_ptr() if return_labels else None,
+                lpres.data_ptr() if return_labels else None, swapped.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
+                'sncal_keypoint_labels')
+    return (keypoints, mask, swapped, labels, lpres) if return_labels else (keypoints, mask, swapped)

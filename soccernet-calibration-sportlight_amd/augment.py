@@ -250,6 +250,25 @@ class ComposeTransform(_Transform):
             samples.append(s)
         return params, samples
 
+    def deferring_fix_lr(self):
+        """-> (a ComposeTransform without this list's FixLRAmbiguous, whether there was one): for callers that let the label kernel
+        take the decision (sncal_keypoint_labels with SNCAL_LABELS_FIX_LR, validate.labelled_batch(labels='device', fix_lr=True)).
+        This object is left as it is.  Refused where the kernel could not stand in: a FixLRAmbiguous under UseWithProb or in a
+        nested list, one that is not the last label transform, or one with another threshold than the kernel's 10."""
+        fix = [i for i, t in enumerate(self.transforms) if isinstance(t, FixLRAmbiguous)]
+        for t in self.transforms:
+            inner = t.transform if isinstance(t, UseWithProb) else t
+            if isinstance(inner, ComposeTransform) or (inner is not t and isinstance(inner, FixLRAmbiguous)):
+                raise _lib.SncalError('deferring_fix_lr: FixLRAmbiguous under UseWithProb or a nested list cannot be deferred')
+        if not fix:
+            return self, False
+        if len(fix) > 1 or self.transforms[fix[0]].threshold != 10:
+            raise _lib.SncalError('deferring_fix_lr: the label kernel applies one FixLRAmbiguous with threshold 10')
+        for t in self.transforms[fix[0] + 1:]:
+            if isinstance(t.transform if isinstance(t, UseWithProb) else t, (Flip, LineFlip)):
+                raise _lib.SncalError('deferring_fix_lr: a flip after FixLRAmbiguous would have to run after the label kernel')
+        return ComposeTransform([t for i, t in enumerate(self.transforms) if i != fix[0]]), True
+
     def labels(self, annot: dict) -> dict:
         """The label side alone, on one annotation (validate()'s transform=): a list that would change the image is refused."""
         params, (s,) = self.draw_batch(1, 0, [annot])

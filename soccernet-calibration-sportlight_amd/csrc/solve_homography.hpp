@@ -1,4 +1,5 @@
-// Part of the camera solve: included by solve.hip alone (one translation unit), after solve_wave.hpp and solve_linalg.hpp.
+// Part of the camera solve: included by solve.hip and by labels.hip (one translation unit each), after solve_wave.hpp and
+// solve_linalg.hpp.
 // Plane homographies: the 4-point fit, the normalised least-squares fit, RANSAC over lane-parallel hypotheses, and the focal length
 // from the image of the absolute conic.
 #pragma once

@@ -1,4 +1,4 @@
-// Part of the camera solve: included by solve.hip alone (one translation unit), after solve_wave.hpp.
+// Part of the camera solve: included by solve.hip and by labels.hip (one translation unit each), after solve_wave.hpp.
 // Lane-local dense algebra: 3x3 products and adjugates, NxN Cholesky, the polar iteration, the SO(3) maps (exp, log, left Jacobian)
 // and the two 6x6 solvers of the pose minimisers (Sym6: Cholesky with the eigen-decomposition fallback; Chol6: reciprocal-diagonal form).
 #pragma once

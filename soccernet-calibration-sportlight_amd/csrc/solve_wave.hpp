@@ -1,4 +1,4 @@
-// Part of the camera solve: included by solve.hip alone (one translation unit), after its point-id masks and u64.
+// Part of the camera solve: included by solve.hip after its point-id masks and u64, and by labels.hip (one translation unit each).
 // Wave reductions (shuffle and DPP forms), lane broadcasts, bit-set helpers, the RANSAC sampler and the best-hypothesis reduction.
 #pragma once
 

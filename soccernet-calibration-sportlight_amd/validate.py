@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .annotations import get_extreme_points, get_intersections, line_keypoints, sort_anno
+from .annotations import get_extreme_points, get_intersections, keypoint_labels_device, line_keypoints, sort_anno
 from .evaluate import scale_points
 from .jpeg import JpegDecoder, probe
 from .lines import LINE_CLS
@@ -130,49 +130,86 @@ def decoded_batches(folder: str, names: Sequence[str], batch_size: int, device, 
             dec.close()
 
 
+def _label_mode(labels: str, transform):
+    """labels='host' | 'device' -> (the transform to run on the host, whether the label kernel takes FixLRAmbiguous' decision)."""
+    if labels not in ('host', 'device'):
+        raise _lib.SncalError(f"labels={labels!r}: 'host' or 'device'")
+    if labels == 'host' or transform is None:
+        return transform, False
+    if not hasattr(transform, 'deferring_fix_lr'):
+        raise _lib.SncalError("labels='device' takes an augment.ComposeTransform (its FixLRAmbiguous moves into the label kernel)")
+    return transform.deferring_fix_lr()
+
+
 def folder_batches(folder: str, batch_size: int, device, num_keypoints: int, margin: float, img_size, decoder_threads: int,
-                   skipped: List[str], transform=None) -> Iterator[dict]:
+                   skipped: List[str], transform=None, labels: str = 'host') -> Iterator[dict]:
     """The batch dicts of a split folder, frames decoded on the device as uint8 BGR.  A file the decoder cannot take is left out
     of its batch and named in `skipped`.  transform: None, or the label transform of the reference's validation loader
     (augment.test_transform(): FixLRAmbiguous), applied to each annotation before scale_points and annot_to_keypoints as
-    HRNetDataset.__getitem__ does (dataset.py:60-64)."""
+    HRNetDataset.__getitem__ does (dataset.py:60-64).  labels: see labelled_batch."""
     names, annots = list_split(folder)
+    transform, fix_lr = _label_mode(labels, transform)
     if transform is not None:
         annots = [transform.labels(a) for a in annots]
     frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped)
     try:
         for keep, image in frames:
-            yield labelled_batch(image, [annots[j] for j in keep], [names[j] for j in keep], num_keypoints, margin, img_size)
+            yield labelled_batch(image, [annots[j] for j in keep], [names[j] for j in keep], num_keypoints, margin, img_size,
+                                 labels=labels, fix_lr=fix_lr)
     finally:
         frames.close()
 
 
-def labelled_batch(image, annots: Sequence[dict], names: Sequence[str], num_keypoints: int, margin: float, img_size) -> dict:
-    """The reference's batch dict (dataset.py:52-71 + custom_collate) from frames and their (already transformed) annotations."""
-    pairs = [annot_to_keypoints(a, num_keypoints, margin) for a in annots]
+def labelled_batch(image, annots: Sequence[dict], names: Sequence[str], num_keypoints: int, margin: float, img_size,
+                   labels: str = 'host', fix_lr: bool = False) -> dict:
+    """The reference's batch dict (dataset.py:52-71 + custom_collate) from frames and their (already transformed) annotations.
+    labels='host': annot_to_keypoints per frame, 'keypoints' and 'mask' on the host.  labels='device': one launch of the label kernel
+    for the batch (annotations.keypoint_labels_device), 'keypoints' and 'mask' on the image's device; with fix_lr the kernel also
+    takes FixLRAmbiguous' decision -- the annotations then come in WITHOUT that transform applied (ComposeTransform.deferring_fix_lr)
+    -- and the host renames the swapped frames' annotations for 'raw_annot' from one copy of B bytes."""
+    if labels == 'host':
+        if fix_lr:
+            raise _lib.SncalError("fix_lr is the label kernel's: with labels='host' FixLRAmbiguous runs in the transform")
+        pairs = [annot_to_keypoints(a, num_keypoints, margin) for a in annots]
+        keypoints = torch.from_numpy(np.stack([p[0] for p in pairs]))
+        mask = torch.from_numpy(np.stack([p[1] for p in pairs]))
+    elif labels == 'device':
+        keypoints, mask, swapped = keypoint_labels_device(annots, margin=margin, num_keypoints=num_keypoints, fix_lr=fix_lr,
+                                                          device=image.device)
+        if fix_lr:
+            from .augment import flip_annot_names
+            annots = [flip_annot_names(a, swap_top_bottom=False, swap_posts=False) if s else a
+                      for a, s in zip(annots, swapped.cpu().tolist())]
+    else:
+        raise _lib.SncalError(f"labels={labels!r}: 'host' or 'device'")
     return {'image': image,
-            'keypoints': torch.from_numpy(np.stack([p[0] for p in pairs])),
-            'mask': torch.from_numpy(np.stack([p[1] for p in pairs])),
+            'keypoints': keypoints,
+            'mask': mask,
             'raw_annot': [scale_points(a, img_size[0], img_size[1]) for a in annots],
             'img_name': list(names)}
 
 
 def train_batches(folder: str, batch_size: int, transform, shuffle: bool = True, seed=None, device='cuda:0', num_keypoints: int = 57,
-                  margin: float = 0.0, img_size=(960, 540), decoder_threads: int = 0, skipped: List[str] = None) -> Iterator[dict]:
+                  margin: float = 0.0, img_size=(960, 540), decoder_threads: int = 0, skipped: List[str] = None,
+                  labels: str = 'host') -> Iterator[dict]:
     """One epoch of the reference's TRAINING batches (train.py:31-33: HRNetDataset with train_transform under a shuffling loader)
     of a split folder: {'image', 'keypoints', 'mask', 'raw_annot', 'img_name'}.  Frames are decoded and augmented on the device
     (augment.train_transform: 'image' is fp32 (B,3,H,W) with ToTensor in the list, uint8 (B,H,W,3) without); the labels come from
     the transformed annotations.  shuffle draws the epoch's order from numpy.random.RandomState(seed) -- a generator of its own, so
     the transform's draws from random / numpy.random are those of a run without shuffling.  A file the decoder cannot take is
-    left out of its batch and named in `skipped` (when a list is given); the last batch may be short, as the reference's is."""
+    left out of its batch and named in `skipped` (when a list is given); the last batch may be short, as the reference's is.
+    labels: see labelled_batch; with 'device' the transform's FixLRAmbiguous is carried out by the label kernel (it draws nothing,
+    so the other transforms' draws are those of labels='host')."""
     names, annots = list_split(folder)
     order = np.random.RandomState(seed).permutation(len(names)) if shuffle else np.arange(len(names))
     names, annots = [names[j] for j in order], [annots[j] for j in order]
+    transform, fix_lr = _label_mode(labels, transform)
     frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped if skipped is not None else [])
     try:
         for keep, image in frames:
             out = transform({'image': image, 'annot': [annots[j] for j in keep]})
-            yield labelled_batch(out['image'], out['annot'], [names[j] for j in keep], num_keypoints, margin, img_size)
+            yield labelled_batch(out['image'], out['annot'], [names[j] for j in keep], num_keypoints, margin, img_size,
+                                 labels=labels, fix_lr=fix_lr)
     finally:
         frames.close()
 
@@ -216,7 +253,7 @@ def line_folder_batches(folder: str, batch_size: int, device, num_keypoint_pairs
 
 def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreator, Sequence[CameraCreator]], batch_size: int = 16,
              loss=None, decoder_threads: int = 0, conf_threshold: float = 0.5, pckhs_thres: Sequence[float] = (2.0, 5.0, 10.0, 50.0),
-             threshold: int = 5, img_size=(960, 540), transform=None):
+             threshold: int = 5, img_size=(960, 540), transform=None, labels: str = 'host'):
     """-> {'val_loss', 'val_l2', 'val_precision', 'val_recall', 'val_pcks-2.0', ..., 'val_l2_reprojection', 'val_completeness',
     'val_eval_precision', 'val_eval_recall', 'val_eval_accuracy', 'val_evalai'} as floats (a ValidationResult).
 
@@ -230,6 +267,8 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
             validation loader applies (validate.py:33, train.py:34) -- FixLRAmbiguous mirrors the class names of a behind-the-goal
             frame annotated the other way round, so val_loss and the keypoint metrics of such frames are taken against the
             keypoints the reference takes them against
+    labels  folder form only.  'host': annotations.get_intersections per frame; 'device': one launch of the label kernel per batch,
+            the transform's FixLRAmbiguous included
 
     val_loss is the mean of the step losses weighted by step size.  This is the one definition here NOT taken from the reference:
     it is computed by pytorch-argus' Loss metric there, whose source is not part of the reference tree.
@@ -237,6 +276,8 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
     as a missed frame by the camera metrics, as a frame without a camera is.  The host waits for the GPU once, at the end."""
     if transform is not None and not isinstance(data, (str, os.PathLike)):
         raise _lib.SncalError('transform applies to the folder form: batches handed in carry their labels already')
+    if labels != 'host' and not isinstance(data, (str, os.PathLike)):
+        raise _lib.SncalError('labels applies to the folder form: batches handed in carry their labels already')
     cams = list(camera) if isinstance(camera, (list, tuple)) else [camera]
     own_loss = model.loss
     if loss is not None:
@@ -250,7 +291,7 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
         skipped: List[str] = []
         if isinstance(data, (str, os.PathLike)):
             batches = folder_batches(os.fspath(data), batch_size, model.device, nk, float(loss_fn.sigma), img_size, decoder_threads, skipped,
-                                     transform=transform)
+                                     transform=transform, labels=labels)
         loss_sum = torch.zeros((), dtype=torch.float64, device=model.device)
         frames = 0
         for batch in (batches if batches is not None else data):

@@ -1,0 +1,177 @@
+"""GPU: sncal_keypoint_labels (csrc/labels.hip) against the host path it restates -- annotations.get_intersections,
+validate.annot_to_keypoints, augment.FixLRAmbiguous -- run here on the same frames (tests/labels_ref.py).
+
+Bounds, for every frame of every set, none left out:
+  presence of each of the 57 labels, the mask vector and `swapped`: IDENTICAL to the host's;
+  fp64 labels: within 1e-5 px of the host's (a sixth of the fp32 spacing at x = 960; the host's own sensitivity to 64 ulps on its
+  inputs is 4e-7 px, so two correct fp64 implementations differ by far less);
+  fp32 rows: within 1 fp32 ulp of the host's rows (a label that sits within 1e-5 px of a rounding tie may round the other way).
+The measured maxima are printed before each assertion (pytest -s shows them)."""
+import json
+import random
+
+import numpy as np
+import pytest
+import torch
+
+import labels_ref as lr
+
+pytestmark = pytest.mark.gpu
+
+TOL_PX = 1e-5
+
+
+def device_labels(sncal, cuda, annots, margin=0.0, fix_lr=False, within_image=True):
+    kp, mask, swapped, labels, present = sncal.annotations.keypoint_labels_device(
+        annots, margin=margin, fix_lr=fix_lr, within_image=within_image, device=cuda, return_labels=True)
+    assert kp.is_cuda and kp.dtype == torch.float32 and tuple(kp.shape) == (len(annots), 171)
+    assert mask.dtype == torch.int64 and tuple(mask.shape) == (len(annots), 58) and swapped.dtype == torch.uint8
+    return kp.cpu().numpy(), mask.cpu().numpy(), swapped.cpu().numpy(), labels.cpu().numpy(), present.cpu().numpy()
+
+
+def ulp_distance(a, b):
+    """fp32 arrays -> distance in representable values (both finite, same sign or zero: label rows are >= -1)."""
+    def key(x):
+        i = x.view(np.int32).astype(np.int64)
+        return np.where(i < 0, -(i & 0x7fffffff), i)
+    return np.abs(key(np.ascontiguousarray(a)) - key(np.ascontiguousarray(b)))
+
+
+def compare(what, ref, dev):
+    """ref: labels_ref.host_reference's list; dev: device_labels' tuple -> the largest label distance in px."""
+    kp, mask, _, labels, present = dev
+    worst = (0.0, None)
+    for b, (hl, hmask, hrow, hvec) in enumerate(ref):
+        want = np.array([hl[i] is not None for i in range(57)])
+        assert np.array_equal(present[b].astype(bool), want), (what, b, np.nonzero(present[b].astype(bool) != want)[0])
+        assert np.array_equal(mask[b], hvec), (what, b)
+        assert [i for i in range(57) if mask[b, i] == 0] == hmask, (what, b)
+        for i in range(57):
+            if want[i]:
+                d = float(np.hypot(labels[b, i, 0] - hl[i][0], labels[b, i, 1] - hl[i][1]))
+                if d > worst[0] or not d == d:
+                    worst = (d, (b, i))
+    print(f'{what}: {len(ref)} frames, max |device - host| = {worst[0]:.3e} px at (frame, id) {worst[1]}')
+    assert worst[0] <= TOL_PX, (what, worst)
+    for b, (_, _, hrow, _) in enumerate(ref):
+        u = ulp_distance(kp[b], hrow)
+        assert u.max() <= 1, (what, b, int(u.max()), np.nonzero(u > 1)[0])
+    return worst[0]
+
+
+@pytest.fixture(scope='module')
+def frames():
+    fixture, cases = lr.fixture_frames()
+    assert len(fixture) == 24
+    plain = fixture + lr.synthetic_frames(40)
+    return {'plain': plain, 'cases': cases}
+
+
+def test_fixture_and_synthetic_frames(sncal, cuda, frames):
+    plain = frames['plain']
+    ref = lr.host_reference(plain, key='plain')
+    dev = device_labels(sncal, cuda, plain)
+    compare('24 fixture + 40 synthetic', ref, dev)
+    # the fixture's stored labels came from the reference's own functions
+    worst = 0.0
+    for b, c in enumerate(frames['cases']):
+        g = np.array(c['labels'], dtype=np.float64)
+        here = ~np.isnan(g[:, 0])
+        assert np.array_equal(dev[4][b].astype(bool), here), b
+        assert sorted(i for i in range(57) if dev[1][b, i] == 0) == c['mask'], b
+        worst = max(worst, float(np.hypot(dev[3][b, here, 0] - g[here, 0], dev[3][b, here, 1] - g[here, 1]).max()) if here.any() else 0.0)
+    print(f'fixture labels of the reference capture: max distance {worst:.3e} px')
+    assert worst <= TOL_PX
+    assert not dev[2].any()                                                   # without the flag nothing is swapped
+    # two calls, the same bytes
+    again = device_labels(sncal, cuda, plain)
+    for a, b in zip(dev, again):
+        assert a.tobytes() == b.tobytes()
+
+
+def test_flipped_frames(sncal, cuda, frames):
+    flipped = [sncal.augment.flip_annot(a) for a in frames['plain']]
+    compare('64 flipped', lr.host_reference(flipped, key='flipped'), device_labels(sncal, cuda, flipped))
+
+
+def test_mixed_batch_of_65(sncal, cuda, frames):
+    plain = frames['plain']
+    flipped = [sncal.augment.flip_annot(a) for a in plain]
+    rp, rf = lr.host_reference(plain, key='plain'), lr.host_reference(flipped, key='flipped')
+    annots = [x for i in range(32) for x in (plain[2 * i], flipped[2 * i + 1])] + [{}]
+    ref = [x for i in range(32) for x in (rp[2 * i], rf[2 * i + 1])] + lr.host_reference([{}])
+    assert len(annots) == 65
+    compare('mixed batch of 65', ref, device_labels(sncal, cuda, annots))
+
+
+@pytest.mark.parametrize('name', sorted(lr.hand_built()))
+def test_hand_built(sncal, cuda, name):
+    batch = lr.hand_built()[name]
+    assert 1 <= len(batch) <= 3
+    ref = lr.host_reference(batch)
+    if name == '3, 4 and 5 known ground points':
+        # (the circle-derived ids come after: 3 known points leave the circle ids masked, 4 and 5 fill them)
+        assert [len(m) for _, m, _, _ in ref] == [27, 0, 0]
+    if name == 'tangent reference inside the ellipse':
+        from sncal_amd import annotations as an
+        pts = np.array([(p['x'] * 960.0, p['y'] * 540.0) for p in batch[0]['Circle central']])
+        assert an.tangent_points(an.fit_ellipse(pts), ref[0][0][15]) is None and ref[0][0][30] is None and 30 not in ref[0][1]
+    compare(name, ref, device_labels(sncal, cuda, batch))
+
+
+def test_margin_and_outside_labels(sncal, cuda, frames):
+    some = frames['plain'][20:32]
+    compare('margin 50', lr.host_reference(some, margin=50.0), device_labels(sncal, cuda, some, margin=50.0))
+    from sncal_amd import annotations as an
+    kp, mask, _, labels, present = device_labels(sncal, cuda, some, within_image=False)
+    for b, a in enumerate(some):
+        hl, hmask = an.get_intersections({c: [(p['x'], p['y']) for p in v] for c, v in a.items()}, within_image=False)
+        assert [hl[i] is not None for i in range(57)] == list(present[b].astype(bool)), b
+        assert sorted(hmask) == [i for i in range(57) if mask[b, i] == 0]
+        for i in range(57):
+            if hl[i] is not None:
+                assert np.hypot(labels[b, i, 0] - hl[i][0], labels[b, i, 1] - hl[i][1]) <= TOL_PX, (b, i)
+
+
+def test_fix_lr(sncal, cuda, frames):
+    A, V = sncal.augment, sncal.validate
+    annots = lr.behind_goal_frames() + frames['plain'][:8]
+    fx = A.FixLRAmbiguous()
+    verdicts = [fx.decide(a) for a in annots]
+    assert {(s, br) for s, br in verdicts} >= {(True, 'medians'), (False, 'medians'), (True, 'count'), (False, 'count')}, verdicts
+    fixed = [A.test_transform().labels(a) for a in annots]                                # the host chain: FixLRAmbiguous first
+    for margin in (0.0, 50.0):
+        dev = device_labels(sncal, cuda, annots, margin=margin, fix_lr=True)
+        assert [bool(s) for s in dev[2]] == [s for s, _ in verdicts], margin
+        compare(f'fix_lr, margin {margin}', lr.host_reference(fixed, margin=margin), dev)
+
+
+def test_folder_and_train_batches(sncal, cuda, gold_dir, frames, tmp_path):
+    """labels='device' against labels='host' over a folder of 8 small frames, with test_transform() and train_transform()."""
+    import os
+    A, V = sncal.augment, sncal.validate
+    small = np.load(os.path.join(gold_dir, 'jpeg_cases.npz'))['jpg.48x64_420_q95_r0'].tobytes()
+    annots = lr.behind_goal_frames()[:4] + frames['plain'][:4]
+    for i, a in enumerate(annots):
+        (tmp_path / f'{i:05d}.json').write_text(json.dumps(a))
+        (tmp_path / f'{i:05d}.jpg').write_bytes(small)
+
+    def same(host, device):
+        assert len(host) == len(device) > 0
+        for h, d in zip(host, device):
+            assert d['keypoints'].is_cuda and d['mask'].is_cuda and d['keypoints'].dtype == torch.float32 and d['mask'].dtype == torch.int64
+            assert ulp_distance(d['keypoints'].cpu().numpy(), h['keypoints'].numpy()).max() <= 1
+            assert torch.equal(d['mask'].cpu(), h['mask'])
+            assert d['raw_annot'] == h['raw_annot'] and d['img_name'] == h['img_name']
+            assert torch.equal(d['image'], h['image'])
+
+    def folder(labels):
+        return list(V.folder_batches(str(tmp_path), 3, cuda, 57, 2.0, (960, 540), 0, [], transform=A.test_transform(), labels=labels))
+
+    def train(labels):
+        random.seed(5)
+        np.random.seed(5)
+        return list(V.train_batches(str(tmp_path), 3, A.train_transform(), shuffle=True, seed=2, device=cuda, margin=2.0, labels=labels))
+    same(folder('host'), folder('device'))
+    same(train('host'), train('device'))
+    assert any(fx_swapped for fx_swapped, _ in (A.FixLRAmbiguous().decide(a) for a in annots))        # the deferred decision mattered
