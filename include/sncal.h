@@ -176,6 +176,11 @@ int sncal_hrnet_forward(sncal_hrnet* net, const float* d_x, int B, int H, int W,
  *            (a layer is selected when its stage AND its width are selected; an empty class selects all of it).  The
  *            tolerance sweep of tests/test_fp8_gpu.py walks this selection. */
 int sncal_hrnet_calibrate_fp8(sncal_hrnet* net, const float* d_x, int B, int H, int W, void* d_ws, size_t ws_bytes, void* stream);
+/* Workspace bytes of that calibration forward.  It runs every layer in bf16, without the e4m3 twins: on a network that is already
+ * calibrated its layout is not the one sncal_hrnet_workspace describes, and may need MORE bytes.  NOT a pure query: it lays the network
+ * out as the calibration would and then drops that layout, like sncal_hrnet_set_fp8_layers -- cached launch schedules and their device work
+ * lists are freed, sncal_hrnet_plan_op / plan_tensor are invalid until the next sncal_hrnet_workspace or forward, which lay out again. */
+int sncal_hrnet_calibrate_fp8_workspace(sncal_hrnet* net, int B, int H, int W, size_t* bytes);
 int sncal_hrnet_set_fp8_layers(sncal_hrnet* net, const char* spec);
 
 /* Same forward from the frames as the reference's harness holds them BEFORE torchvision's ToTensor
@@ -222,6 +227,8 @@ typedef struct {
     char kernel[96];           /* label of the launch that executed it in the last mode-1 profiled forward ("" = unknown or
                                   executed by the launch of an earlier op: grouped members, second conv of a fused block)      */
     int res_twin;              /* bf16x3: this conv reads its residual from the split twin of tensor `res`, not from its fp32 form */
+    int launch;                /* index, in the launch schedule of the layout's own sub-batch size, of the launch that covers this op
+                                  (grouped members and the ops of a fused pair share one); -1 = inactive or no schedule yet        */
 } sncal_plan_op;
 typedef struct {
     int C, H, W;               /* NHWC, per frame                                                                              */
@@ -231,10 +238,15 @@ typedef struct {
     float scale;               /* e4m3 twins: value = code * scale                                                             */
     size_t bytes;              /* of the first sub-batch (sub_batch frames)                                                    */
     int sub_batch;
+    size_t offset;             /* byte offset of the slot in the workspace (alive tensors)                                     */
+    int first, last;           /* ops between which the allocator keeps the slot (lifetimes as stretched over launch groups and
+                                  fusable pairs), -1 = not allocated                                                           */
 } sncal_plan_tensor;
 int sncal_hrnet_plan_num_ops(const sncal_hrnet* net);
 int sncal_hrnet_plan_num_tensors(const sncal_hrnet* net);
-/* Valid after sncal_hrnet_workspace / a forward at the shape of interest (the layout decides sizes, twins and head variant). */
+/* Valid after sncal_hrnet_workspace / a forward at the shape of interest (the layout decides sizes, twins and head variant);
+ * on a finalized network sncal_hrnet_workspace also builds the launch schedule of that sub-batch size (host work only), so that
+ * sncal_plan_op.launch is valid without a forward. */
 int sncal_hrnet_plan_op(const sncal_hrnet* net, int idx, sncal_plan_op* out);
 int sncal_hrnet_plan_tensor(const sncal_hrnet* net, int id, sncal_plan_tensor* out);
 /* Register a tap (op_idx >= 0) or clear all taps (op_idx < 0).  d_dst must hold sncal_plan_tensor.bytes. */

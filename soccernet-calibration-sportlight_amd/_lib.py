@@ -38,13 +38,14 @@ class PlanOp(ctypes.Structure):
                 ('base', ctypes.c_int), ('src', ctypes.c_int * 4), ('nsrc', ctypes.c_int), ('head_direct', ctypes.c_int),
                 ('head_src', ctypes.c_int * 5), ('head_nsrc', ctypes.c_int), ('head_fold', ctypes.c_int * 2),
                 ('head_nfold', ctypes.c_int), ('relu', ctypes.c_int), ('out_coff', ctypes.c_int), ('out_f32', ctypes.c_int),
-                ('fp8', ctypes.c_int), ('kernel', ctypes.c_char * 96), ('res_twin', ctypes.c_int)]
+                ('fp8', ctypes.c_int), ('kernel', ctypes.c_char * 96), ('res_twin', ctypes.c_int), ('launch', ctypes.c_int)]
 
 
 class PlanTensor(ctypes.Structure):
     """sncal_plan_tensor."""
     _fields_ = [('C', ctypes.c_int), ('H', ctypes.c_int), ('W', ctypes.c_int), ('dtype', ctypes.c_int), ('twin', ctypes.c_int),
-                ('alive', ctypes.c_int), ('scale', ctypes.c_float), ('bytes', ctypes.c_size_t), ('sub_batch', ctypes.c_int)]
+                ('alive', ctypes.c_int), ('scale', ctypes.c_float), ('bytes', ctypes.c_size_t), ('sub_batch', ctypes.c_int),
+                ('offset', ctypes.c_size_t), ('first', ctypes.c_int), ('last', ctypes.c_int)]
 
 
 class Camera(ctypes.Structure):
@@ -116,6 +117,7 @@ SIGNATURES = {
                                               ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]),
     'sncal_hrnet_set_profiling': (ctypes.c_int, [vp, ctypes.c_int]),
     'sncal_hrnet_calibrate_fp8': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, ctypes.c_size_t, vp]),
+    'sncal_hrnet_calibrate_fp8_workspace': (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
     'sncal_hrnet_set_fp8_layers': (ctypes.c_int, [vp, ctypes.c_char_p]),
     'sncal_hrnet_plan_num_ops': (ctypes.c_int, [vp]),
     'sncal_hrnet_plan_num_tensors': (ctypes.c_int, [vp]),

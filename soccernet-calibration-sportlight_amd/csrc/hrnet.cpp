@@ -645,8 +645,13 @@ extern "C" int sncal_hrnet_workspace(const sncal_hrnet* cnet, int B, int H, int 
     SNCAL_CHECK_ARG(cnet && bytes && B >= 0 && H >= 32 && W >= 32, "sncal_hrnet_workspace: bad arguments");
     sncal_hrnet* net = const_cast<sncal_hrnet*>(cnet);
     const int sb = std::max(1, std::min(B, net->subbatch));
-    const int rc = layout(*net, sb, H, W);
+    int rc = layout(*net, sb, H, W);
     if (rc) return rc;
+    if (net->finalized) {         // the schedule the first forward of this shape would build (host work only): sncal_plan_op.launch
+        Schedule* s = nullptr;
+        rc = schedule_for(*net, sb, &s);
+        if (rc) return rc;
+    }
     *bytes = net->lay_bytes;
     return SNCAL_OK;
 }
@@ -673,6 +678,18 @@ extern "C" int sncal_hrnet_set_fp8_layers(sncal_hrnet* net, const char* spec) {
     net->fp8_stages = none ? (1u << 31) : stages;       // bit 31 matches no stage: nothing selected
     net->fp8_widths = widths;
     drop_layout(*net);                                  // twins / lifetimes depend on the selection
+    return SNCAL_OK;
+}
+
+extern "C" int sncal_hrnet_calibrate_fp8_workspace(sncal_hrnet* net, int B, int H, int W, size_t* bytes) {
+    SNCAL_CHECK_ARG(net && bytes && B >= 0 && H >= 32 && W >= 32, "sncal_hrnet_calibrate_fp8_workspace: bad arguments");
+    SNCAL_CHECK_ARG(net->fp8, "sncal_hrnet_calibrate_fp8_workspace: the network was not created with SNCAL_FP8");
+    net->calibrating = true; drop_layout(*net);         // the layout sncal_hrnet_calibrate_fp8's forward will use
+    const int rc = layout(*net, std::max(1, std::min(B, net->subbatch)), H, W);
+    const size_t n = net->lay_bytes;
+    net->calibrating = false; drop_layout(*net);
+    if (rc) return rc;
+    *bytes = n;
     return SNCAL_OK;
 }
 
@@ -768,6 +785,12 @@ extern "C" int sncal_hrnet_plan_op(const sncal_hrnet* net, int idx, sncal_plan_o
         out->fp8 = L.fp8_on ? 1 : L.x3_on ? 2 : (net->x3 && op.type == OP_CONV) ? 3 : 0;
     }
     out->res_twin = op.res_twin ? 1 : 0;
+    out->launch = -1;
+    for (const Schedule& s : net->schedules) {
+        if (s.sb != net->lay_sb) continue;
+        for (size_t k = 0; k < s.launches.size(); ++k)
+            if (idx >= s.launches[k].op && idx < s.launches[k].op + s.launches[k].n) out->launch = (int)k;
+    }
     if (idx < (int)net->op_label.size()) snprintf(out->kernel, sizeof(out->kernel), "%s", net->op_label[idx].c_str());
     return SNCAL_OK;
 }
@@ -783,6 +806,7 @@ extern "C" int sncal_hrnet_plan_tensor(const sncal_hrnet* net, int id, sncal_pla
         for (const Tensor& o : net->tensors) if (o.twin == id) out->scale = o.scale;
     out->sub_batch = net->lay_sb;
     out->bytes = (size_t)net->lay_sb * t.H * t.W * t.C * (t.f32 ? 4 : t.fp8 ? 1 : net->esize);
+    out->offset = t.first >= 0 ? t.offset : 0; out->first = t.first; out->last = t.first >= 0 ? t.last : -1;
     return SNCAL_OK;
 }
 

@@ -211,11 +211,16 @@ class HRNetHeatmap:
         _lib.check(self._L.sncal_hrnet_output_size(self._h, H, W, ctypes.byref(h), ctypes.byref(w)), 'output_size')
         return h.value, w.value
 
-    def _workspace(self, B, H, W):
+    def workspace_bytes(self, B, H, W):
+        """Bytes of workspace a forward of (B,3,H,W) needs; lays the plan out for that shape (plan_ops / plan_tensor), no device work."""
         n = ctypes.c_size_t()
         _lib.check(self._L.sncal_hrnet_workspace(self._h, B, H, W, ctypes.byref(n)), 'sncal_hrnet_workspace')
-        if self._ws is None or self._ws.numel() < n.value:
-            self._ws = torch.empty(n.value, dtype=torch.uint8, device=self.device)
+        return n.value
+
+    def _workspace(self, B, H, W):
+        n = self.workspace_bytes(B, H, W)
+        if self._ws is None or self._ws.numel() < n:
+            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
         return self._ws
 
     def forward(self, x: torch.Tensor, want_heat: bool = True, decode_size=None):
@@ -266,8 +271,10 @@ class HRNetHeatmap:
         """One bf16 forward of x (B,3,H,W) fp32 that records the per-tensor activation ranges the fp8 convolutions scale by."""
         _lib.require_device(x, torch.float32, 'x')
         B, C, H, W = x.shape
+        n = ctypes.c_size_t()        # the calibration forward has a layout of its own (no e4m3 twins): a calibrated handle can be calibrated again
+        _lib.check(self._L.sncal_hrnet_calibrate_fp8_workspace(self._h, B, H, W, ctypes.byref(n)), 'sncal_hrnet_calibrate_fp8_workspace')
         with torch.cuda.device(x.device):
-            ws = self._workspace(B, H, W)
+            ws = torch.empty(n.value, dtype=torch.uint8, device=self.device)
             _lib.check(self._L.sncal_hrnet_calibrate_fp8(self._h, x.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(),
                                                          _lib.current_stream_ptr()), 'sncal_hrnet_calibrate_fp8')
         self._ws = None            # the fp8 layout adds the e4m3 twins: re-query the workspace
@@ -296,7 +303,8 @@ class HRNetHeatmap:
     OP_TYPES = ('input', 'conv', 'upsample_add', 'softmax', 'decode', 'head')
 
     def plan_ops(self):
-        """The executor's op list at the current layout (valid after a forward / workspace query): list of dicts."""
+        """The executor's op list at the current layout (valid after a forward / workspace query): list of dicts.  `launch`: index of the
+        launch that covers the op in the schedule of the layout's own sub-batch size (-1: inactive)."""
         out = []
         po = _lib.PlanOp()
         for i in range(self._L.sncal_hrnet_plan_num_ops(self._h)):
@@ -306,14 +314,15 @@ class HRNetHeatmap:
                             **{'in': po.in_}, res=po.res, out=po.out, base=po.base, src=list(po.src)[:po.nsrc],
                             head_direct=po.head_direct, head_src=list(po.head_src)[:po.head_nsrc],
                             head_fold=list(po.head_fold)[:po.head_nfold], relu=bool(po.relu), out_coff=po.out_coff,
-                            out_f32=bool(po.out_f32), fp8=po.fp8 == 1, x3=po.fp8 == 2, x3g=po.fp8 == 3, res_twin=bool(po.res_twin), kernel=po.kernel.decode()))
+                            out_f32=bool(po.out_f32), fp8=po.fp8 == 1, x3=po.fp8 == 2, x3g=po.fp8 == 3, res_twin=bool(po.res_twin), kernel=po.kernel.decode(),
+                            launch=po.launch))
         return out
 
     def plan_tensor(self, tid):
         pt = _lib.PlanTensor()
         _lib.check(self._L.sncal_hrnet_plan_tensor(self._h, tid, ctypes.byref(pt)), 'plan_tensor')
         return dict(id=tid, C=pt.C, H=pt.H, W=pt.W, dtype=('fp32', 'bf16', 'e4m3')[pt.dtype], twin=pt.twin, alive=bool(pt.alive),
-                    scale=pt.scale, bytes=pt.bytes, sub_batch=pt.sub_batch)
+                    scale=pt.scale, bytes=pt.bytes, sub_batch=pt.sub_batch, offset=pt.offset, first=pt.first, last=pt.last)
 
     def clear_taps(self):
         _lib.check(self._L.sncal_hrnet_plan_tap(self._h, -1, 0, None), 'plan_tap')

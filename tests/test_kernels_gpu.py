@@ -16,6 +16,10 @@ is recomputed with torch (fp32 conv2d / index arithmetic) from the SAME rounded 
 Tolerance = one ulp of the output type (bf16: 2^-7 |y|, the worst-case ulp of a value; e4m3: 2^-3 |y| + one subnormal step)
 plus 1e-3 of fp32 accumulation-order slack -- a wrong tap, a wrong tile-edge pixel, a row of the neighbouring frame or a
 mis-scaled channel is two orders of magnitude above it.
+
+Between the launches (producer_reader_identity, run by every case on the same taps): a launch recomputed from the operands it READ is
+correct on clobbered operands too, so the tap of every tensor and twin at its producing op must equal, byte for byte, the tap of the same
+tensor at every later op that reads it.
 """
 import json
 import os
@@ -380,8 +384,116 @@ def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag=''):
             lg = logits[..., :C].permute(0, 3, 1, 2)
             ref = torch.softmax(lg, dim=1) if net.cfg.get('head') == 'softmax' else torch.log_softmax(lg, dim=1)
             check('softmax head', got, ref, 1e-5, 1e-5, stats, 'softmax_nchw')
-    stats['_case'] = dict(tag=tag, dtype=dtype, fp8_layers=fp8_layers, frames=int(B), input=list(x.shape[2:]))
+    pairs, skipped = producer_reader_identity(net, ops, taps, dtype)
+    stats['_case'] = dict(tag=tag, dtype=dtype, fp8_layers=fp8_layers, frames=int(B), input=list(x.shape[2:]),
+                          reader_pairs=pairs, lds_intermediates=len(skipped))
     return stats
+
+
+# ---- between the launches: what a producer wrote is what every later reader found --------------------------------------------
+FUSED_PAIR_KERNELS = ('bblock48_fused', 'bblockx3_fused', 'bneck_tail_ds_x3')     # their first op's output stays in LDS
+X3_ENGINES = ('fp16x3', 'bf16x3', 'x3')
+
+
+def _twin_by_producer(net, po, dtype):
+    """Does op `po` write the e4m3 / split twin of its output itself?  (hrnet_schedule.cpp twin_written_by_producer; otherwise a
+    quantise / split helper makes the twin in front of every launch that reads it.)"""
+    to = net.plan_tensor(po['out'])
+    if po['type'] == 'conv' and po['fp8']:
+        return True
+    if po['type'] == 'conv' and po.get('x3'):
+        return po['out_coff'] == 0 and to['C'] == po['cout']
+    if dtype in X3_ENGINES and po['type'] == 'conv' and po.get('x3g'):
+        return po['out_coff'] == 0 and not po['out_f32'] and to['C'] == po['cout'] and po['cout'] % 16 == 0
+    if dtype in X3_ENGINES and po['type'] == 'upsample_add':
+        return po['out_coff'] == 0 and to['C'] % 16 == 0
+    return False
+
+
+def _real_reads(net, o, producers, dtype):
+    """Tensor ids the launch of op `o` really reads for it: the twin in place of `in` for the e4m3 / split two-team convolutions (and
+    `in` itself beside it when the helper in front of the launch has to make the twin), the twin in place of `res` for res_twin."""
+    r = []
+    if o['in'] >= 0:
+        if o['type'] == 'conv' and (o['fp8'] or o.get('x3')):
+            r.append(net.plan_tensor(o['in'])['twin'])
+            if not _twin_by_producer(net, producers[o['in']][0], dtype):
+                r.append(o['in'])
+        else:
+            r.append(o['in'])
+    if o['res'] >= 0:
+        r.append(net.plan_tensor(o['res'])['twin'] if o.get('res_twin') else o['res'])
+    r += [o['base'], o['head_direct']] + o['src'] + o['head_src'] + o['head_fold']
+    return [t for t in r if t is not None and t >= 0]
+
+
+def _bits(t):
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+def producer_reader_identity(net, ops, taps, dtype):
+    """The per-launch checks above recompute a launch from the operands it READ; a launch in between that clobbered a live tensor would
+    hand the reader clobbered operands and pass.  So: for every allocated tensor and twin, the tap taken at its producing op equals, byte
+    for byte, the tap taken at every later op that really reads it (last reader included); concat tensors per producer slice, from that
+    producer's tap on.  Tensors no launch writes -- the intermediate of a fused pair, which stays in LDS -- are skipped, and the skipped
+    set must be exactly the intermediates of the launches labelled as fused pairs.  Returns (pairs compared, skipped tensor ids)."""
+    act = [o for o in ops if o['active'] and o['type'] != 'decode']
+    producers = {}
+    for o in act:
+        if o['out'] is not None and o['out'] >= 0:
+            producers.setdefault(o['out'], []).append(o)
+    twin_of = {}
+    for t in producers:
+        tw = net.plan_tensor(t)['twin']
+        if tw >= 0 and net.plan_tensor(tw)['alive']:
+            twin_of[tw] = t
+    readers = {}
+    for o in act:
+        for t in _real_reads(net, o, producers, dtype):
+            assert net.plan_tensor(t)['alive'], (o['idx'], t)
+            readers.setdefault(t, []).append(o)
+    for t in readers:
+        assert t in producers or t in twin_of, f'tensor {t} is read and nobody writes it'
+    # tensors that stay in LDS: produced and read inside ONE launch and nowhere else -- by the schedule, and by the labels
+    by_idx = {o['idx']: o for o in ops}
+    skipped = set()
+    for t, rs in readers.items():
+        p = producers[twin_of.get(t, t)][0]
+        if p['launch'] >= 0 and all(r['launch'] == p['launch'] for r in rs):
+            skipped.add(t)
+    expected = set()
+    for o in act:
+        if o['kernel'] in FUSED_PAIR_KERNELS:
+            nxt = by_idx[o['idx'] + 1]
+            assert nxt['launch'] == o['launch'], (o['idx'], o['kernel'])
+            expected |= {t for t in _real_reads(net, nxt, producers, dtype) if twin_of.get(t, t) == o['out']}
+    assert skipped == expected, f'tensors without a writer {sorted(skipped)} != intermediates of the fused pairs {sorted(expected)}'
+    pairs = 0
+    for t, rs in readers.items():
+        if t in skipped:
+            continue
+        base = twin_of.get(t, t)
+        in_front = t in twin_of and not _twin_by_producer(net, producers[base][0], dtype)
+        # (a twin its producer does not write is made in front of each reading launch, from the tensor -- itself compared as `base`)
+        writers = [rs[0]] if in_front else producers[base]
+        for p in writers:
+            lo, hi = 0, taps[(p['idx'], t)].shape[-1]
+            if not in_front and (len(writers) > 1 or p['out_coff']):       # a channel slice of a concat tensor
+                width = p['cout'] if p['type'] == 'conv' else net.plan_tensor(p['src'][0])['C']
+                lo, hi = p['out_coff'], p['out_coff'] + width
+            want = _bits(taps[(p['idx'], t)])[..., lo:hi]
+            for r in rs:
+                if r['idx'] <= p['idx']:
+                    continue
+                got = _bits(taps[(r['idx'], t)])[..., lo:hi]
+                if not torch.equal(got, want):
+                    n_bad = int((got != want).sum())
+                    raise AssertionError(f"tensor {t}{' (twin of %d)' % base if t != base else ''} channels {lo}:{hi}: what op {p['idx']} "
+                                         f"({p['name'] or p['type']}) wrote is not what op {r['idx']} ({r['name'] or r['type']}) read: "
+                                         f"{n_bad} of {want.numel()} elements differ")
+                pairs += 1
+    assert pairs >= len(act), (pairs, len(act))         # every op reads something
+    return pairs, skipped
 
 
 def _split_twin_value(raw):
