@@ -137,9 +137,20 @@ def field_table(dist=0.9, dist_circles=0.2):
     return np.array(pts, dtype=np.float64), np.array(start, dtype=np.int32)
 
 
-def get_polylines(position, rotation, fx, fy, pp, width, height, table=None):
-    """evaluate_camera.py:14-105 -> {class: [(x, y)]} for the classes with a non-empty projection."""
+def get_polylines(position, rotation, fx, fy, pp, width, height, table=None, classes=None, stats=None):
+    """evaluate_camera.py:14-105 -> {class: [(x, y)]} for the classes with a non-empty projection.
+
+    `classes` names the rows of `table` (default: CLASSES with field_table()), so any table of 1..n classes can be
+    walked.  `stats`, a dict, receives counts of the branches taken (tests/evaluate_ref.py census): 'behind' samples
+    skipped, 'enter' / 'leave' crossings, 'no_border' crossings without an in-image border point, 'first_prev_zero'
+    first valid sample inside while prev is still zeros(3), 'len1' polylines of one point."""
     pts, start = table if table is not None else field_table()
+    classes = CLASSES if classes is None else list(classes)
+    assert len(classes) == len(start) - 1
+
+    def count(key):
+        if stats is not None:
+            stats[key] = stats.get(key, 0) + 1
     sides = [np.array([1, 0, 0]), np.array([1, 0, -width + 1]), np.array([0, 1, 0]), np.array([0, 1, -height + 1])]
 
     def edge_point(ext, prev):
@@ -155,27 +166,39 @@ def get_polylines(position, rotation, fx, fy, pp, width, height, table=None):
         return cands[int(np.argmin(dists))] if cands else None
 
     out = {}
-    for ci, c in enumerate(CLASSES):
+    for ci, c in enumerate(classes):
         plist, in_img, prev = [], False, np.zeros(3)
         for i in range(start[ci], start[ci + 1]):
             ext = cm.project_point(position, rotation, fx, fy, pp, pts[i])
             if ext[2] < 1e-5:
+                count('behind')
                 continue
             if 0 <= ext[0] < width and 0 <= ext[1] < height:
                 if not in_img and i > start[ci]:
                     e = edge_point(ext, prev)
+                    if not prev.any():
+                        count('first_prev_zero')
+                    else:
+                        count('enter')
+                        if e is None:
+                            count('no_border')
                     if e is not None:
                         plist.append((e[0], e[1]))
                 plist.append((ext[0], ext[1]))
                 in_img = True
             elif in_img:
                 e = edge_point(ext, prev)
+                count('leave')
+                if e is None:
+                    count('no_border')
                 if e is not None:
                     plist.append((e[0], e[1]))
                 in_img = False
             prev = ext
         if plist:
             out[c] = plist
+            if len(plist) == 1:
+                count('len1')
     return out
 
 
@@ -237,16 +260,18 @@ def evaluate_camera_prediction(projected, groundtruth, threshold, detail=False):
     return (conf, per_class, errors) if detail else conf
 
 
-def mirror_labels(d):
-    return {SYMMETRIC[k]: v for k, v in d.items()}
+def mirror_labels(d, symmetric=None):
+    sym = SYMMETRIC if symmetric is None else symmetric
+    return {sym[k]: v for k, v in d.items()}
 
 
-def evaluate_frame(position, rotation, fx, fy, pp, groundtruth, threshold, width=960, height=540, table=None):
+def evaluate_frame(position, rotation, fx, fy, pp, groundtruth, threshold, width=960, height=540, table=None,
+                   classes=None, symmetric=None):
     """evaluate_camera.py:293-320 for one frame: (confusion, accuracy) of the better of plain / mirrored labels,
-    plus both confusions."""
-    poly = get_polylines(position, rotation, fx, fy, pp, width, height, table)
+    plus both confusions.  `classes` / `symmetric` go with a `table` other than the pitch model's (get_polylines)."""
+    poly = get_polylines(position, rotation, fx, fy, pp, width, height, table, classes)
     c1 = evaluate_camera_prediction(poly, groundtruth, threshold)
-    c2 = evaluate_camera_prediction(poly, mirror_labels(groundtruth), threshold)
+    c2 = evaluate_camera_prediction(poly, mirror_labels(groundtruth, symmetric), threshold)
     a1 = c1[0, 0] / c1.sum() if c1.sum() > 0 else 0.
     a2 = c2[0, 0] / c2.sum() if c2.sum() > 0 else 0.
     return (c1, a1, c1, c2) if a1 > a2 else (c2, a2, c1, c2)

@@ -16,6 +16,8 @@
 //   4. thread 0 assembles both confusions (plain and left/right-mirrored labels), accuracies and the choice.
 // fp64 throughout; counts are exact integers, so results equal the oracle's unless a distance sits within rounding
 // of the threshold.
+// Pinned by tests/test_evaluate_edges_gpu.py on hand-built tables (every boundary above with a closed-form answer) and
+// on cameras a metre above the grass / zoomed 3x against the oracle, the launch above 64 KiB of LDS included.
 #include "common.hpp"
 #include "../../include/sncal.h"
 
@@ -209,9 +211,11 @@ extern "C" int sncal_evaluate_cameras_detail(const sncal_camera* d_cams, int B, 
     SNCAL_CHECK_HIP(hipStreamSynchronize(sncal::as_stream(stream)));
     SNCAL_CHECK_ARG(n_pts > 0 && n_pts <= 2048, "sncal_evaluate_cameras: %d pitch samples", n_pts);
     const size_t lds = (size_t)n_pts * 16 + (size_t)(2 * n_pts + 2 * n_cls) * 16 + (size_t)n_pts * 4;
+    // Tables above 64 KiB of dynamic LDS (n_pts > 1244 at 26 classes) need the opt-in.  attr_done is per PROCESS, not per
+    // device: a second device used from the same process may never get the attribute (untested: needs two GPUs).
     static bool attr_done = false;
     if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&evaluate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);   // + 384 B static
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&evaluate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);   // + 896 B static
         attr_done = true;
     }
     hipLaunchKernelGGL(evaluate_kernel, dim3(B), dim3(256), lds, sncal::as_stream(stream), d_cams, B, d_field, d_class_start, d_mirror,
