@@ -52,28 +52,15 @@ def create_heatmaps(keypoints: torch.Tensor, sigma: float, pred_size: Tuple[int,
 TERM_MSE, TERM_KL, TERM_AWING = 1, 2, 4
 
 
-def heatmap_loss_sums(logp: torch.Tensor, keypoints: torch.Tensor, mask, sigma: float, stride: float, terms: int = 3) -> torch.Tensor:
-    """sncal_heatmap_loss: logp (B,N+1,h,w) fp32 log-probabilities, keypoints (B,N,3) fp32 in IMAGE pixels, mask (B,N+1) fp32
-    or None -> (B,3) fp64 per-frame sums of the MSE, KL and adaptive-wing terms (0 where the term's bit is clear).
-    Asynchronous on the current stream."""
-    logp = _lib.require_device(logp, torch.float32, 'pred')
-    kp = _lib.require_device(keypoints, torch.float32, 'keypoints')
-    if logp.dim() != 4 or kp.dim() != 3 or kp.shape[2] != 3 or kp.shape[0] != logp.shape[0] or kp.shape[1] + 1 != logp.shape[1]:
-        raise _lib.SncalError(f'pred {tuple(logp.shape)} must be (B,N+1,h,w) for keypoints {tuple(kp.shape)} = (B,N,3)')
-    B, C, h, w = logp.shape
-    if mask is not None:
-        mask = _lib.require_device(mask, torch.float32, 'mask')
-        if tuple(mask.shape) != (B, C):
-            raise _lib.SncalError(f'mask {tuple(mask.shape)} must be (B,N+1) = {(B, C)}')
-    out = torch.zeros((B, 3), dtype=torch.float64, device=logp.device)
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _workspace(name, shape, device) -> torch.Tensor:
+    """The scratch buffer that the library's query function `name` asks for at `shape`, on `device`."""
     n = ctypes.c_size_t()
-    _lib.check(_lib.lib().sncal_heatmap_loss_workspace(B, C - 1, h, w, ctypes.byref(n)), 'sncal_heatmap_loss_workspace')
-    with torch.cuda.device(logp.device):
-        ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=logp.device)
-        _lib.check(_lib.lib().sncal_heatmap_loss(logp.data_ptr(), kp.data_ptr(), mask.data_ptr() if mask is not None else None,
-                                                 B, C - 1, h, w, float(sigma), float(stride), int(terms), out.data_ptr(),
-                                                 ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()), 'sncal_heatmap_loss')
-    return out
+    _lib.check(getattr(_lib.lib(), name)(*shape, ctypes.byref(n)), name)
+    return torch.empty(max(n.value, 16), dtype=torch.uint8, device=device)
 
 
 def _coef(coef, n):
@@ -91,11 +78,8 @@ def _grad_output(grad_output, device):
     return _lib.require_device(grad_output.detach().to(device, torch.float32).contiguous(), torch.float32, 'grad_output')
 
 
-def heatmap_loss_grad(logp: torch.Tensor, keypoints: torch.Tensor, mask, sigma: float, stride: float, coef, terms: int = 3,
-                      grad_output=None) -> torch.Tensor:
-    """sncal_heatmap_loss_grad: the arguments of heatmap_loss_sums, `coef` = (l2_w / n, kldiv_w / B, awing_w / n) with n the
-    number of elements, and `grad_output` a one-element fp32 tensor on the device or None (= 1) -> the gradient of
-    sum_k coef_k * term_k with respect to logp, fp32, shaped like logp.  Asynchronous on the current stream."""
+def _heatmap_inputs(logp, keypoints, mask):
+    """The tensors of heatmap_loss_sums / heatmap_loss_grad, checked -> (logp, keypoints, mask, (B, N+1, h, w))."""
     logp = _lib.require_device(logp, torch.float32, 'pred')
     kp = _lib.require_device(keypoints, torch.float32, 'keypoints')
     if logp.dim() != 4 or kp.dim() != 3 or kp.shape[2] != 3 or kp.shape[0] != logp.shape[0] or kp.shape[1] + 1 != logp.shape[1]:
@@ -105,17 +89,37 @@ def heatmap_loss_grad(logp: torch.Tensor, keypoints: torch.Tensor, mask, sigma: 
         mask = _lib.require_device(mask, torch.float32, 'mask')
         if tuple(mask.shape) != (B, C):
             raise _lib.SncalError(f'mask {tuple(mask.shape)} must be (B,N+1) = {(B, C)}')
+    return logp, kp, mask, (B, C, h, w)
+
+
+def heatmap_loss_sums(logp: torch.Tensor, keypoints: torch.Tensor, mask, sigma: float, stride: float, terms: int = 3) -> torch.Tensor:
+    """sncal_heatmap_loss: logp (B,N+1,h,w) fp32 log-probabilities, keypoints (B,N,3) fp32 in IMAGE pixels, mask (B,N+1) fp32
+    or None -> (B,3) fp64 per-frame sums of the MSE, KL and adaptive-wing terms (0 where the term's bit is clear).
+    Asynchronous on the current stream."""
+    logp, kp, mask, (B, C, h, w) = _heatmap_inputs(logp, keypoints, mask)
+    out = torch.zeros((B, 3), dtype=torch.float64, device=logp.device)
+    with torch.cuda.device(logp.device):
+        ws = _workspace('sncal_heatmap_loss_workspace', (B, C - 1, h, w), logp.device)
+        _lib.check(_lib.lib().sncal_heatmap_loss(logp.data_ptr(), kp.data_ptr(), _ptr(mask), B, C - 1, h, w, float(sigma), float(stride),
+                                                 int(terms), out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
+                   'sncal_heatmap_loss')
+    return out
+
+
+def heatmap_loss_grad(logp: torch.Tensor, keypoints: torch.Tensor, mask, sigma: float, stride: float, coef, terms: int = 3,
+                      grad_output=None) -> torch.Tensor:
+    """sncal_heatmap_loss_grad: the arguments of heatmap_loss_sums, `coef` = (l2_w / n, kldiv_w / B, awing_w / n) with n the
+    number of elements, and `grad_output` a one-element fp32 tensor on the device or None (= 1) -> the gradient of
+    sum_k coef_k * term_k with respect to logp, fp32, shaped like logp.  Asynchronous on the current stream."""
+    logp, kp, mask, (B, C, h, w) = _heatmap_inputs(logp, keypoints, mask)
     cf = _coef(coef, 3)
     gout = _grad_output(grad_output, logp.device)
-    n = ctypes.c_size_t()
-    _lib.check(_lib.lib().sncal_heatmap_loss_workspace(B, C - 1, h, w, ctypes.byref(n)), 'sncal_heatmap_loss_workspace')
     with torch.cuda.device(logp.device):
         grad = torch.empty_like(logp)
-        ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=logp.device)
-        _lib.check(_lib.lib().sncal_heatmap_loss_grad(logp.data_ptr(), kp.data_ptr(), mask.data_ptr() if mask is not None else None,
-                                                      B, C - 1, h, w, float(sigma), float(stride), int(terms), cf,
-                                                      gout.data_ptr() if gout is not None else None, grad.data_ptr(),
-                                                      ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()), 'sncal_heatmap_loss_grad')
+        ws = _workspace('sncal_heatmap_loss_workspace', (B, C - 1, h, w), logp.device)
+        _lib.check(_lib.lib().sncal_heatmap_loss_grad(logp.data_ptr(), kp.data_ptr(), _ptr(mask), B, C - 1, h, w, float(sigma),
+                                                      float(stride), int(terms), cf, _ptr(gout), grad.data_ptr(), ws.data_ptr(),
+                                                      ws.numel(), _lib.current_stream_ptr()), 'sncal_heatmap_loss_grad')
     return grad
 
 
@@ -244,11 +248,8 @@ def create_keypoint_maps(keypoints: torch.Tensor, sigma: float = 1.0, stride: fl
 TERM_GMSE, TERM_LINE_AWING = 1, 2
 
 
-def line_loss_sums(pred: torch.Tensor, target=None, keypoints=None, target_sigma: float = 1.0, stride: float = 4.0,
-                   gmse_sigma: float = 4.0, terms: int = 3) -> torch.Tensor:
-    """sncal_line_loss: pred (B,C,h,w) fp32 softmax output; exactly one of target (B,C,h,w) fp32 maps and keypoints (B,C,2,3) fp32
-    endpoints in image pixels (the target is then rebuilt, never written) -> (B,2) fp64 per-frame sums of the GMSE and
-    adaptive-wing terms (0 where the term's bit is clear).  Asynchronous on the current stream."""
+def _line_inputs(pred, target, keypoints):
+    """The tensors of line_loss_sums / line_loss_grad, checked -> (pred, target, keypoints, (B, C, h, w))."""
     pred = _lib.require_device(pred, torch.float32, 'pred')
     if (target is None) == (keypoints is None):
         raise _lib.SncalError('exactly one of target and keypoints must be given')
@@ -263,15 +264,21 @@ def line_loss_sums(pred: torch.Tensor, target=None, keypoints=None, target_sigma
         keypoints = _lib.require_device(keypoints, torch.float32, 'keypoints')
         if tuple(keypoints.shape) != (B, C, 2, 3):
             raise _lib.SncalError(f'keypoints {tuple(keypoints.shape)} must be (B,C,2,3) = {(B, C, 2, 3)}')
+    return pred, target, keypoints, (B, C, h, w)
+
+
+def line_loss_sums(pred: torch.Tensor, target=None, keypoints=None, target_sigma: float = 1.0, stride: float = 4.0,
+                   gmse_sigma: float = 4.0, terms: int = 3) -> torch.Tensor:
+    """sncal_line_loss: pred (B,C,h,w) fp32 softmax output; exactly one of target (B,C,h,w) fp32 maps and keypoints (B,C,2,3) fp32
+    endpoints in image pixels (the target is then rebuilt, never written) -> (B,2) fp64 per-frame sums of the GMSE and
+    adaptive-wing terms (0 where the term's bit is clear).  Asynchronous on the current stream."""
+    pred, target, keypoints, (B, C, h, w) = _line_inputs(pred, target, keypoints)
     out = torch.zeros((B, 2), dtype=torch.float64, device=pred.device)
-    n = ctypes.c_size_t()
-    _lib.check(_lib.lib().sncal_line_loss_workspace(B, C, h, w, ctypes.byref(n)), 'sncal_line_loss_workspace')
     with torch.cuda.device(pred.device):
-        ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=pred.device)
-        _lib.check(_lib.lib().sncal_line_loss(pred.data_ptr(), target.data_ptr() if target is not None else None,
-                                              keypoints.data_ptr() if keypoints is not None else None, B, C, h, w,
-                                              float(target_sigma), float(stride), float(gmse_sigma), int(terms), out.data_ptr(),
-                                              ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()), 'sncal_line_loss')
+        ws = _workspace('sncal_line_loss_workspace', (B, C, h, w), pred.device)
+        _lib.check(_lib.lib().sncal_line_loss(pred.data_ptr(), _ptr(target), _ptr(keypoints), B, C, h, w, float(target_sigma),
+                                              float(stride), float(gmse_sigma), int(terms), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                              _lib.current_stream_ptr()), 'sncal_line_loss')
     return out
 
 
@@ -280,31 +287,14 @@ def line_loss_grad(pred: torch.Tensor, target=None, keypoints=None, target_sigma
     """sncal_ehm_loss_grad: the arguments of line_loss_sums, `coef` = (gmse_w / n, awing_w / n) with n the number of elements, and
     `grad_output` a one-element fp32 tensor on the device or None (= 1) -> the gradient of sum_k coef_k * term_k with respect to
     pred, fp32, shaped like pred.  Asynchronous on the current stream."""
-    pred = _lib.require_device(pred, torch.float32, 'pred')
-    if (target is None) == (keypoints is None):
-        raise _lib.SncalError('exactly one of target and keypoints must be given')
-    if pred.dim() != 4:
-        raise _lib.SncalError(f'pred {tuple(pred.shape)} must be (B,C,h,w)')
-    B, C, h, w = pred.shape
-    if target is not None:
-        target = _lib.require_device(target, torch.float32, 'target')
-        if target.shape != pred.shape:
-            raise _lib.SncalError(f'target {tuple(target.shape)} must have the shape of pred {tuple(pred.shape)}')
-    else:
-        keypoints = _lib.require_device(keypoints, torch.float32, 'keypoints')
-        if tuple(keypoints.shape) != (B, C, 2, 3):
-            raise _lib.SncalError(f'keypoints {tuple(keypoints.shape)} must be (B,C,2,3) = {(B, C, 2, 3)}')
+    pred, target, keypoints, (B, C, h, w) = _line_inputs(pred, target, keypoints)
     cf = _coef(coef, 2)
     gout = _grad_output(grad_output, pred.device)
-    n = ctypes.c_size_t()
-    _lib.check(_lib.lib().sncal_line_loss_workspace(B, C, h, w, ctypes.byref(n)), 'sncal_line_loss_workspace')
     with torch.cuda.device(pred.device):
         grad = torch.empty_like(pred)
-        ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=pred.device)
-        _lib.check(_lib.lib().sncal_ehm_loss_grad(pred.data_ptr(), target.data_ptr() if target is not None else None,
-                                                   keypoints.data_ptr() if keypoints is not None else None, B, C, h, w,
-                                                   float(target_sigma), float(stride), float(gmse_sigma), int(terms), cf,
-                                                   gout.data_ptr() if gout is not None else None, grad.data_ptr(),
+        ws = _workspace('sncal_line_loss_workspace', (B, C, h, w), pred.device)
+        _lib.check(_lib.lib().sncal_ehm_loss_grad(pred.data_ptr(), _ptr(target), _ptr(keypoints), B, C, h, w, float(target_sigma),
+                                                   float(stride), float(gmse_sigma), int(terms), cf, _ptr(gout), grad.data_ptr(),
                                                    ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()), 'sncal_ehm_loss_grad')
     return grad
 

@@ -154,6 +154,42 @@ def test_scalar_path_on_an_unaligned_base_and_an_odd_width(sncal, cuda, gold):
                 _check_against_fp64(name, c, gold, got, exact)
 
 
+@pytest.mark.parametrize('B,C,h,w', [(2, 1, 1, 1), (1, 2, 5, 6), (1, 2, 17, 8), (1, 64, 9, 66), (1, 64, 9, 68)])
+def test_sums_on_more_shapes(sncal, cuda, B, C, h, w):
+    """What the capture's cases leave out of the sums kernel: one channel on a 1 x 1 map, maps smaller than a tile on a width that
+    cannot take the 16-byte path and on one that does (waves without rows, lanes past the width), and 64 channels -- all that the
+    row tables in LDS hold -- on both kinds of width.  Both forms, each term alone and both: per frame and per term against the fp64
+    evaluation on the device's own maps, and the two forms with the same bits.
+    Bound: the floor of the bound above, 4 * 2^-23, for every shape (no capture exists, d_ref counts as 0, as for `big`), as the
+    keypoint loss's test of more shapes holds its own 1 x 1 case."""
+    rng = np.random.default_rng(60 + C + w)
+    stride, t_sigma, g_sigma = 4.0, 1.5, 4.0
+    kp = np.zeros((B, C, 2, 3), dtype=np.float32)
+    kp[..., :2] = -1
+    for b in range(B):
+        for ch in range(C):
+            if ch % 3 != 2:
+                kp[b, ch] = [(rng.uniform(-4, w * stride + 4), rng.uniform(-4, h * stride + 4), 1), (rng.uniform(0, w * stride), rng.uniform(0, h * stride), ch % 5 != 0)]
+    d_kp = torch.from_numpy(kp).to(cuda)
+    own = sncal.loss.create_keypoint_maps(d_kp, t_sigma, stride, (h, w))
+    p_np = rng.uniform(0, 1, (B, C, h, w)).astype(np.float32) ** 4 + np.float32(2.0 ** -10)
+    pred = torch.from_numpy(p_np).to(cuda)
+    exact = vr.loss_terms64(p_np, own.cpu().numpy(), g_sigma)
+    bound = 4 * vr.EPS32
+    for terms in (1, 2, 3):
+        a = sncal.loss.line_loss_sums(pred, keypoints=d_kp, target_sigma=t_sigma, stride=stride, gmse_sigma=g_sigma, terms=terms)
+        b = sncal.loss.line_loss_sums(pred, target=own, gmse_sigma=g_sigma, terms=terms)
+        assert torch.equal(a, b), terms
+        got = a.cpu().numpy()
+        for k in range(2):
+            if (terms >> k) & 1:
+                rel = np.abs(got[:, k] - exact[:, k]) / np.abs(exact[:, k])
+                print((B, C, h, w), 'terms', terms, 'term', k, 'largest relative distance', rel.max(), 'bound', bound)
+                assert (rel <= bound).all(), ((B, C, h, w), terms, k, rel)
+            else:
+                assert not got[:, k].any()
+
+
 def test_short_workspace_and_bad_arguments(sncal, cuda):
     E = sncal._lib.SncalError
     L = sncal._lib.lib()
