@@ -20,6 +20,10 @@ mis-scaled channel is two orders of magnitude above it.
 Between the launches (producer_reader_identity, run by every case on the same taps): a launch recomputed from the operands it READ is
 correct on clobbered operands too, so the tap of every tensor and twin at its producing op must equal, byte for byte, the tap of the same
 tensor at every later op that reads it.
+
+The operand a reduced-precision launch reads is a TWIN (e4m3 codes, [16 hi | 16 lo] split codes), and the references above are built from
+the twin itself; twin_value_identity (every case, same taps) holds each twin to the dense tensor it stands for, bit for bit: the helpers
+of quant.hip that make twins in front of a launch, and the epilogues that write a twin beside the dense output.
 """
 import json
 import os
@@ -168,16 +172,19 @@ BF16_ULP = 2.0 ** -7          # largest ulp / |y| of a bf16 value
 E4M3_ULP = 2.0 ** -3
 
 
-def run_case(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, want_heat=True):
-    """One forward with every op tapped; returns (ops, tensors dict (op idx, tensor id) -> torch tensor, net)."""
+def run_case(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, want_heat=True, net=None):
+    """One forward with every op tapped; returns (ops, tensors dict (op idx, tensor id) -> torch tensor, net).  `net`: a loaded (fp8:
+    calibrated) network to run instead of a fresh one (tests/test_handoff_gpu.py: the state a re-calibration left behind)."""
     global X3_T
     global X3_SLACK
     X3_T = torch.float16 if sncal._lib.lib().sncal_x3_name() == b'fp16x3' else torch.bfloat16
     X3_SLACK = 2e-6 if X3_T == torch.float16 else 3e-5
-    net = sncal.HRNetHeatmap(cfg, dtype=dtype, device=cuda)
-    net.load_state_dict(sd)
+    if net is None:
+        net = sncal.HRNetHeatmap(cfg, dtype=dtype, device=cuda)
+        net.load_state_dict(sd)
+        if dtype == 'fp8':
+            net.calibrate_fp8(x)
     if dtype == 'fp8':
-        net.calibrate_fp8(x)
         net.set_fp8_layers(fp8_layers or 'all')
     net.set_profiling(1)                                    # labels: which kernel served which op
     net.forward(x, want_heat=want_heat, decode_size=(540, 960) if net.cfg.get('head', 'logsoftmax') == 'logsoftmax' else None)
@@ -203,8 +210,8 @@ def run_case(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, want_heat=True):
     return ops, taps, net
 
 
-def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag=''):
-    ops, taps, net = run_case(sncal, cuda, cfg, sd, x, dtype, fp8_layers)
+def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag='', net=None):
+    ops, taps, net = run_case(sncal, cuda, cfg, sd, x, dtype, fp8_layers, net=net)
     W = Weights(net, sd, cuda)
     f32_engine = dtype in ('fp32', 'fp16x3')
     act_round = (lambda t: t) if f32_engine else bf16r
@@ -385,8 +392,9 @@ def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag=''):
             ref = torch.softmax(lg, dim=1) if net.cfg.get('head') == 'softmax' else torch.log_softmax(lg, dim=1)
             check('softmax head', got, ref, 1e-5, 1e-5, stats, 'softmax_nchw')
     pairs, skipped = producer_reader_identity(net, ops, taps, dtype)
+    twins = twin_value_identity(net, ops, taps, dtype, stats, skipped)
     stats['_case'] = dict(tag=tag, dtype=dtype, fp8_layers=fp8_layers, frames=int(B), input=list(x.shape[2:]),
-                          reader_pairs=pairs, lds_intermediates=len(skipped))
+                          reader_pairs=pairs, lds_intermediates=len(skipped), **twins)
     return stats
 
 
@@ -496,6 +504,107 @@ def producer_reader_identity(net, ops, taps, dtype):
     return pairs, skipped
 
 
+# ---- a twin is the conversion of the dense tensor it stands for, bit for bit ------------------------------------------------
+TWIN_ROWS = {('fp8', 'front'): 'quantize_fp8 in front', ('x3', 'front'): 'split_f32 in front',
+             ('fp8', 'both'): 'e4m3 twin = q(dense)', ('x3', 'both'): 'split twin = split(dense)'}
+QUANTIZE_GRID_ELEMENTS = 2048 * 256 * 8          # quant.hip: elements one trip of quantize_fp8_kernel's capped grid covers; a larger tensor
+                                                 # takes the grid-stride loop round a second time (split_f32_kernel: 4096 * 256 * 8)
+
+
+def twin_plan(net, ops, dtype, skipped):
+    """From the plan alone (no taps): [(kind 'fp8' | 'x3', where 'front' | 'both', op, tensor id, twin id)].
+    'front': the launch of `op` reads a twin its producer did not write, so quantize_fp8_kernel / split_f32_kernel makes it from the
+    dense tensor in front of that launch (hrnet.cpp run_tt / run_bblockx3).  'both': `op` writes its output AND the output's twin
+    (hrnet_schedule.cpp tt_outputs, writes_twin: the twin when a reduced-precision convolution reads it, the dense form when anybody else
+    does).  The intermediates of the fused pairs (`skipped`) live in LDS and have neither form."""
+    act = [o for o in ops if o['active'] and o['type'] != 'decode']
+    producers = {}
+    for o in act:
+        if o['out'] is not None and o['out'] >= 0:
+            producers.setdefault(o['out'], []).append(o)
+    plan = []
+    for o in act:
+        if o['type'] == 'conv' and (o['fp8'] or o.get('x3')) and o['in'] >= 0:
+            tw = net.plan_tensor(o['in'])['twin']
+            if tw in skipped or o['in'] in skipped:
+                continue
+            assert tw >= 0 and net.plan_tensor(tw)['alive'], (o['idx'], o['in'], tw)
+            if not _twin_by_producer(net, producers[o['in']][0], dtype):
+                plan.append(('fp8' if o['fp8'] else 'x3', 'front', o, o['in'], tw))
+    for t, ps in producers.items():
+        to = net.plan_tensor(t)
+        tw = to['twin']
+        if tw < 0 or not net.plan_tensor(tw)['alive'] or t in skipped or tw in skipped or len(ps) != 1:
+            continue
+        p = ps[0]
+        if _twin_by_producer(net, p, dtype) and to['alive'] and _bf16_written(net, ops, p):
+            plan.append(('fp8' if p['type'] == 'conv' and p['fp8'] else 'x3', 'both', p, t, tw))
+    return plan
+
+
+def twin_value_identity(net, ops, taps, dtype, stats, skipped=()):
+    """producer_reader_identity shows that a twin did not change between its writer and its readers, and the per-launch checks recompute a
+    launch from the twin it read: a helper or an epilogue that makes a self-consistent WRONG twin passes both.  So every twin is held to
+    the dense tensor tapped at the same op, with no tolerance (tests/handoff_ref.py, pinned on the CPU by tests/test_handoff_host.py):
+
+        split twin   codes == split16(dense fp32): xc = clamp(x, +-65504) (fp16 build), hi = rne16(xc), lo = rne16(xc - hi), [16 hi | 16 lo]
+        e4m3 twin    decode(codes) == e4m3_rne(clamp(float(dense bf16) * (1.0f / scale), +-448)), as floats (+0 == -0)
+
+    for the twins the helpers of quant.hip make in front of a launch, and for the twins an epilogue writes beside the dense output it also
+    writes: conv_tt's x3 and fp8 epilogues, bblockx3, the generic convolution and upsample_add with a twin output all convert the very
+    value they store (the fp8 epilogue the ROUNDED bf16 value), and x3.hpp's fused v_fma_mix spelling gives the bits of the plain one.
+    The seams of layer1 (bneckx3.hip) write no twin at all (hrnet_schedule.cpp fuses_bneck_seam requires that nobody is owed one), and a
+    producer that writes ONLY the twin (inside a BasicBlock chain) leaves no dense form to compare with: its twin stays with the per-launch
+    tolerance.  How many pairs there are comes from the plan (twin_plan); exactly that many are compared.  Rows of `stats`, for the engine
+    that has twins: the four of TWIN_ROWS (ops = pairs, sites = pairs per kernel label).  Returns the counts for stats['_case'], with the
+    largest tensor a helper converted in front of a launch (its capped grid-stride loop, QUANTIZE_GRID_ELEMENTS)."""
+    import handoff_ref as hr
+    plan = twin_plan(net, ops, dtype, skipped)
+    largest = {'fp8': 0, 'x3': 0}
+    rows = {}
+    labels = {o['launch']: o['kernel'] for o in ops if o['active'] and o['kernel']}      # (grouped / fused members carry no label of their own)
+    for kind, where, op, t, tw in plan:
+        assert (op['idx'], t) in taps and (op['idx'], tw) in taps, f"op {op['idx']}: tensor {t} / twin {tw} not tapped"
+        dense, twin = taps[(op['idx'], t)], taps[(op['idx'], tw)]
+        what = f"{TWIN_ROWS[(kind, where)]}: op {op['idx']} ({op['name'] or op['type']}), tensor {t} {tuple(dense.shape)}, twin {tw}"
+        if kind == 'x3':
+            assert dense.dtype == torch.float32 and twin.shape == dense.shape, what
+            got, want = hr.split_codes_of_twin(twin), hr.split16(dense, X3_T)
+            show = lambda v: f'0x{int(v) & 0xffff:04x}'
+        else:
+            scale = net.plan_tensor(tw)['scale']
+            assert dense.dtype == torch.bfloat16 and twin.dtype == torch.uint8 and twin.shape == dense.shape and scale > 0, what
+            got, want = hr.e4m3_values(twin), hr.e4m3_values(hr.e4m3_codes(dense, scale))
+            what += f', scale {scale!r}'
+            show = float
+        bad = got != want
+        if bad.any():
+            idx = tuple(int(v) for v in torch.nonzero(bad)[0])
+            src = idx if kind == 'fp8' else idx[:3] + (idx[3] // 32 * 16 + idx[3] % 16,)
+            raise AssertionError(f'{what}: {int(bad.sum())} of {bad.numel()} twin elements are not the conversion of the dense tensor; first at '
+                                 f'{list(idx)} ({"hi" if kind == "x3" and idx[3] % 32 < 16 else "lo" if kind == "x3" else "code"}): twin holds '
+                                 f'{show(got[idx])}, dense {float(dense[src])!r} converts to {show(want[idx])}')
+        row = rows.setdefault((kind, where), dict(ops=0, elements=0, worst_err_over_tol=0.0, max_abs_err=0.0, worst_op=''))
+        row['ops'] += 1
+        row['elements'] += int(dense.numel())
+        site = labels.get(op['launch'], op['type'])                 # which kernel's launch read (front) / wrote (both) the pair
+        row.setdefault('sites', {})[site] = row.get('sites', {}).get(site, 0) + 1
+        if where == 'front':
+            largest[kind] = max(largest[kind], int(dense.numel()))
+    expected = {}
+    for kind, where, *_ in plan:
+        expected[(kind, where)] = expected.get((kind, where), 0) + 1
+    engine = 'fp8' if dtype == 'fp8' else 'x3' if dtype in X3_ENGINES else None
+    for key, name in TWIN_ROWS.items():
+        n = rows.get(key, {'ops': 0})['ops']
+        assert n == expected.get(key, 0), (name, n, expected.get(key, 0))
+        assert key[0] == engine or n == 0, (name, dtype, n)
+        if key[0] == engine:
+            stats[name] = rows.get(key, dict(ops=0, elements=0, worst_err_over_tol=0.0, max_abs_err=0.0, worst_op=''))
+    return dict(twin_pairs_expected=len(plan), twin_pairs_compared=sum(r['ops'] for r in rows.values()),
+                largest_quantize_in_front=largest['fp8'], largest_split_in_front=largest['x3'])
+
+
 def _split_twin_value(raw):
     """(N,H,W,C) fp32-typed storage of a split twin -> (N,C,H,W) fp32: hi + lo."""
     pr = raw.view(X3_T).reshape(raw.shape[0], raw.shape[1], raw.shape[2], raw.shape[3] // 16, 2, 16).to(torch.float32)
@@ -580,6 +689,22 @@ def _report(stats, name):
         pass
 
 
+def _twin_rows(stats, *rows):
+    """The twin checks of this case were not vacuous: as many pairs compared as the plan holds, each named row at least once."""
+    c = stats['_case']
+    assert c['twin_pairs_compared'] == c['twin_pairs_expected'] > 0, c
+    for r in rows:
+        assert r in stats and stats[r]['ops'] >= 1, (r, c, {k: stats[k]['ops'] for k in TWIN_ROWS.values() if k in stats})
+
+
+FP8_TWIN_ROWS = ('quantize_fp8 in front', 'e4m3 twin = q(dense)')
+# The split engine's producers -- the two-team and generic convolutions, bblockx3, the fuse sums -- write every twin a stock network
+# (W18 / W32 / W48, line network; 140p .. 1080p) reads, so NO launch of such a plan has split_f32_kernel in front (twin_plan finds none,
+# and producer_reader_identity would fail on a twin the plan held for producer-written that a helper made later): the row is reported,
+# with compared == expected == 0, and nothing is asserted about a path the engine does not take.
+X3_TWIN_ROWS = ('split twin = split(dense)',)
+
+
 def _frames(B, H, W, seed, dev):
     g = torch.Generator().manual_seed(seed)
     return torch.rand((B, 3, H, W), generator=g, dtype=torch.float32).to(dev)
@@ -625,6 +750,8 @@ def test_every_launch_with_partial_head_tiles_in_both_directions(sncal, cuda, dt
     stats = verify_plan(sncal, cuda, 'hrnet_w48', sd, _frames(2, 140, 240, 24, cuda), dtype, tag='w48 140x240 ' + dtype)
     _report(stats, dtype + '_w48_140x240')
     assert ('head_fused' if dtype == 'bf16' else 'headx3_fused') in stats, list(stats)      # not some other head path
+    if dtype != 'bf16':
+        _twin_rows(stats, *X3_TWIN_ROWS)
 
 
 @pytest.mark.parametrize('layers', ['all', 'stage4,c192,c384'])
@@ -641,6 +768,7 @@ def test_every_launch_of_the_fp8_engine_w48_540p(sncal, cuda, layers):
     if layers == 'all':
         assert stats[k]['ops'] + stats[k + ' e4m3 out']['ops'] >= 144          # every one of the 144 wide convolutions checked on at least one output
         assert stats[k + ' e4m3 out']['ops'] >= 120                            # all but the last convolution of each chain hand an e4m3 twin on
+    _twin_rows(stats, *FP8_TWIN_ROWS)
 
 
 def test_every_launch_of_the_fp8_engine_w48_1080p(sncal, cuda):
@@ -648,6 +776,9 @@ def test_every_launch_of_the_fp8_engine_w48_1080p(sncal, cuda):
     stats = verify_plan(sncal, cuda, 'hrnet_w48', sd, _frames(2, 1080, 1920, 15, cuda), 'fp8', fp8_layers='all', tag='w48 1080p fp8')
     _report(stats, 'fp8_w48_1080p')
     assert 'conv_tt<fp8,k3,s1,8x32x96>' in stats
+    _twin_rows(stats, *FP8_TWIN_ROWS)
+    # two frames of the 135x240x96 branch are 6.2 M elements: quantize_fp8_kernel's capped grid goes round its loop a second time
+    assert stats['_case']['largest_quantize_in_front'] > QUANTIZE_GRID_ELEMENTS, stats['_case']
 
 
 def test_every_launch_of_the_line_network_bf16(sncal, cuda):
@@ -686,6 +817,7 @@ def test_every_launch_of_the_fp16x3_engine_w48_540p(sncal, cuda, monkeypatch, sm
     # layer1 (bneckx3.hip): block 0's conv3 with its downsample branch inside, and the seams conv3 + next conv1 of blocks 1 | 2 and 2 | 3
     # (two checks each: the 256-channel block output and the next block's 64-channel conv1 output)
     assert n('bneck_tail_ds_x3') == 1 and n('bneck_seam_x3') == 4, {k: v.get('ops') for k, v in stats.items()}
+    _twin_rows(stats, *X3_TWIN_ROWS)
 
 
 def test_every_launch_of_the_fp16x3_engine_w32_270p(sncal, cuda):
@@ -698,6 +830,7 @@ def test_every_launch_of_the_fp16x3_engine_w32_270p(sncal, cuda):
     n = lambda key: stats.get(key, {'ops': 0})['ops']
     assert n(k48) + n(k48 + ' split out') >= 200, {k: v['ops'] for k, v in stats.items()}
     assert any(k.startswith('conv<fp16x3,k3,s2') for k in stats) and any(k.startswith('conv<fp16x3,k1,s1') for k in stats)
+    _twin_rows(stats, *X3_TWIN_ROWS)
 
 
 def test_every_launch_of_the_fp16x3_engine_w48_1080p_and_odd_sizes(sncal, cuda):
@@ -706,9 +839,11 @@ def test_every_launch_of_the_fp16x3_engine_w48_1080p_and_odd_sizes(sncal, cuda):
     stats = verify_plan(sncal, cuda, 'hrnet_w48', sd, _frames(2, 1080, 1920, 20, cuda), 'fp16x3', tag='w48 1080p fp16x3')
     _report(stats, 'fp16x3_w48_1080p')
     assert 'conv_tt<fp16x3,k3,s1,8x32x96> split out' in stats and stats['bblockx3_fused split out']['ops'] >= 24 and stats['bblockx3_fused']['ops'] >= 8
+    _twin_rows(stats, *X3_TWIN_ROWS)
     stats = verify_plan(sncal, cuda, 'hrnet_w48', sd, _frames(5, 270, 500, 21, cuda), 'fp16x3', tag='w48 270x500 fp16x3')
     _report(stats, 'fp16x3_w48_270x500')
     assert 'conv_tt<fp16x3,k3,s1,8x32x96> split out' in stats and stats['bblockx3_fused split out']['ops'] >= 24
+    _twin_rows(stats, *X3_TWIN_ROWS)
 
 
 def test_every_launch_of_the_fp16x3_engine_w18_and_line_net(sncal, cuda):
@@ -723,3 +858,4 @@ def test_every_launch_of_the_fp16x3_engine_w18_and_line_net(sncal, cuda):
     sd = _weights('line_hrnet_w48')
     stats = verify_plan(sncal, cuda, 'line_hrnet_w48', sd, _frames(2, 540, 960, 23, cuda), 'fp16x3', tag='line w48 540p fp16x3')
     _report(stats, 'fp16x3_line_w48_540p')
+    _twin_rows(stats, *X3_TWIN_ROWS)
