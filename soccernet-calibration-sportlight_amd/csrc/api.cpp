@@ -1,5 +1,6 @@
-// libsncal.so: version + thread-local error string.
+// libsncal.so: version + thread-local error string; the host half of persist.hpp.
 #include "common.hpp"
+#include "persist.hpp"
 #include "x3.hpp"
 #include <cstring>
 #include <vector>
@@ -14,19 +15,23 @@ void set_error(const char* fmt, ...) {
 }
 LaunchEvents& launch_events() { static thread_local LaunchEvents e; return e; }
 
-unsigned long long* trace_arm(size_t n, hipStream_t stream) {
-    unsigned long long* d = nullptr;
-    if (hipMalloc(&d, n * 8) != hipSuccess) return nullptr;
-    (void)hipMemsetAsync(d, 0, n * 8, stream);
-    return d;
+// ---- host half of persist.hpp
+bool opt_in_lds_kernel(const void* kernel, int bytes) {
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %d) failed: %s", bytes, hipGetErrorString(e));
+    return e == hipSuccess;
 }
-void trace_dump(unsigned long long* d_trace, size_t n, const char* file, hipStream_t stream) {
-    if (!d_trace) return;
-    std::vector<unsigned long long> h(n);
-    (void)hipStreamSynchronize(stream);
-    (void)hipMemcpy(h.data(), d_trace, n * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d_trace);
-    if (FILE* f = fopen(file, "wb")) { fwrite(h.data(), 8, n, f); fclose(f); }
+TraceScope::TraceScope(const char* file, size_t n, hipStream_t stream) : file_(file), n_(n), stream_(stream) {
+    if (!file || hipMalloc(&words, n * 8) != hipSuccess) { words = nullptr; return; }
+    (void)hipMemsetAsync(words, 0, n * 8, stream);
+}
+TraceScope::~TraceScope() {
+    if (!words) return;
+    std::vector<unsigned long long> h(n_);
+    (void)hipStreamSynchronize(stream_);
+    (void)hipMemcpy(h.data(), words, n_ * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(words);
+    if (FILE* f = fopen(file_, "wb")) { fwrite(h.data(), 8, n_, f); fclose(f); }
 }
 }  // namespace sncal
 

@@ -18,7 +18,7 @@
 //            counts loads and stores together) never waits for a store
 // LDS 84 + 40 + 31.5 = 155.5 KB -> one workgroup per CU; two barriers per tile.
 #include "bblock.hpp"
-#include "common.hpp"
+#include "persist.hpp"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -41,7 +41,6 @@ constexpr int BB_XROW = 2048;                    // LDS bytes per halo row: two 
 constexpr int BB_XBYTES = BB_XH * BB_XROW;
 constexpr int BB_MIDBYTES = BB_MH * BB_MW * BB_PS;
 constexpr int BB_LDS = 4 * BB_WBYTES + BB_XBYTES + BB_MIDBYTES;
-constexpr int BB_PF = 1;                         // operand prefetch distance in k-steps
 constexpr int BB_NW = 8;                         // waves per workgroup: two per SIMD
 constexpr int BB_J1 = (BB_MH + BB_NW - 1) / BB_NW, BB_J2 = BB_TH / BB_NW;      // pixel fragments (tile rows) per wave: conv1 (at most), conv2
 static_assert(BB_TH % BB_NW == 0 && BB_J1 == BB_J2 + 1 && BB_LDS + 16 <= 160 * 1024, "tile rows split evenly over the waves; one workgroup per CU");
@@ -52,19 +51,7 @@ static_assert(BB_TH % BB_NW == 0 && BB_J1 == BB_J2 + 1 && BB_LDS + 16 <= 160 * 1
 // per tile): a workgroup spent 80 % of its life outside its MFMA phases.  Now a tile costs its x halo (one DMA round that lands
 // under the previous tile's conv2), two barriers and its MFMAs.  Same packed weights, same K order, same bf16 rounding of
 // mid as the two-kernel path -> bit-identical results (tested).
-// One LDS-DMA piece (64 lanes x 16 bytes -> 1 KB at LDS byte address `lds_addr`) as inline assembly.  The builtin form makes hipcc's
-// wait-count pass treat every later ds_read as a possible reader of the DMA's destination: it put `s_waitcnt vmcnt(0)` in front of
-// conv2's first fragment reads -- i.e. waited for the NEXT tile's halo to land before multiplying -- and, because the loop-top wait
-// is inline assembly it cannot see, `vmcnt(2..0)` into conv1's first k-step, which waited for the previous tile's STORES.  Together
-// ~3k of 13k clk per tile.  Ordering is explicit here (vmcnt(0) + barrier at the top of every tile).
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void dma_piece(i32x4_t rsrc, unsigned lds_addr, unsigned voff, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" : : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory", "m0");
-}
-__device__ __forceinline__ i32x4_t raw_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    return i32x4_t{(int)(unsigned)a, (int)(unsigned)((a >> 32) & 0xffffu), (int)bytes, 0x00020000};
-}
+// The x halos come by dma_piece (persist.hpp): ordering is explicit here (vmcnt(0) + barrier at the top of every tile).
 
 __global__ __launch_bounds__(64 * BB_NW, 1) void bblock48_kernel(const BBlockParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -83,15 +70,16 @@ __global__ __launch_bounds__(64 * BB_NW, 1) void bblock48_kernel(const BBlockPar
     // the multiplies); everybody reads it behind the mid barrier, where the next halo is requested.
     const int xcd = (int)blockIdx.x & 7;
     const int n_tiles = p.N * p.tiles_y * p.tiles_x;
-    const int t_lo = (int)((long)n_tiles * xcd / 8), t_hi = (int)((long)n_tiles * (xcd + 1) / 8);
+    int t_lo, t_hi;
+    xcd_share(n_tiles, xcd, t_lo, t_hi);
     unsigned* const s_next = reinterpret_cast<unsigned*>(smem + BB_LDS);        // [2]: the next tile, by parity of the tile count
     if (tid == 0) s_next[0] = (unsigned)t_lo + atomicAdd(p.ticket + xcd, 1u);
     __syncthreads();
     int t = __builtin_amdgcn_readfirstlane((int)s_next[0]);
 
     const size_t img_bytes = (size_t)p.H * p.W * 48 * 2;
-    const __amdgpu_buffer_rsrc_t rs_w1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w1), 0, 2 * BB_WBYTES, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w2), 0, 2 * BB_WBYTES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w1 = buf_rsrc(p.w1, 2 * BB_WBYTES);
+    const __amdgpu_buffer_rsrc_t rs_w2 = buf_rsrc(p.w2, 2 * BB_WBYTES);
     for (int i = wave; i < 2 * BB_NKS * BB_MI; i += BB_NW) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w1, (lds_void*)(s_w + i * 1024), 16, (unsigned)(lane * 16), (unsigned)(i * 1024), 0, 0);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w2, (lds_void*)(s_w + 2 * BB_WBYTES + i * 1024), 16, (unsigned)(lane * 16), (unsigned)(i * 1024), 0, 0);
@@ -110,19 +98,19 @@ __global__ __launch_bounds__(64 * BB_NW, 1) void bblock48_kernel(const BBlockPar
         xlane[k] = px * 96u + cg * 16u;
     }
     i32x4_t xrs = raw_rsrc(p.x, (unsigned)img_bytes);       // state of the halo request in flight: image descriptor, lane offsets, first row
-    unsigned xv[2] = {0x80000000u, 0x80000000u};
+    unsigned xv[2] = {BUF_OOB, BUF_OOB};
     int xoy = 0;
     auto prepare_x = [&](int n, int oy0, int ox0) {
         xrs = raw_rsrc(reinterpret_cast<const char*>(p.x) + (size_t)n * img_bytes, (unsigned)img_bytes);
         xoy = oy0 - 2;
 #pragma unroll
         for (int k = 0; k < 2; ++k)
-            xv[k] = (unsigned)(ox0 - 2 + xpx[k]) < (unsigned)p.W ? xlane[k] + (unsigned)((ox0 - 2) * 96) : 0x80000000u;
+            xv[k] = (unsigned)(ox0 - 2 + xpx[k]) < (unsigned)p.W ? xlane[k] + (unsigned)((ox0 - 2) * 96) : BUF_OOB;
     };
     auto piece_x = [&](int j) {                  // piece j = half (j & 1) of halo row j >> 1
         const int iy = xoy + (j >> 1);
         const bool rowok = (unsigned)iy < (unsigned)p.H;
-        const unsigned voff = rowok ? ((j & 1) ? xv[1] : xv[0]) : 0x80000000u;
+        const unsigned voff = rowok ? ((j & 1) ? xv[1] : xv[0]) : BUF_OOB;
         dma_piece(xrs, x_lds + (unsigned)j * 1024u, voff, rowok ? (unsigned)(iy * p.W * 96) : 0u);
     };
     auto issue_x = [&](int n, int oy0, int ox0, int first, int stride) {
@@ -221,14 +209,12 @@ __global__ __launch_bounds__(64 * BB_NW, 1) void bblock48_kernel(const BBlockPar
 
     // tuning aid (SNCAL_BB_TRACE=<file>): per wave, clocks spent in [0] halo wait + opening barrier, [1] conv1, [2] residual read
     // + mid write + barrier + next halo request, [3] conv2, [4] epilogue arithmetic, [5] tiles
-    unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
-    const bool tracing = p.trace != nullptr;
-    auto lap = [&](int k) { if (tracing) { const unsigned long long now = __builtin_amdgcn_s_memtime(); tsum[k] += now - tprev; tprev = now; } };
+    PhaseClock clk(p.trace);
 
     auto nohook = [](int) {};
     int t_next = t_hi;
     for (unsigned ti = 0; t < t_hi; ++ti, t = t_next) {
-        if (tracing) tprev = __builtin_amdgcn_s_memtime();
+        clk.start();
         const int n = tn, oy0 = ty * BB_TH, ox0 = tx * BB_TW;
         init_acc(bias1);
         __builtin_amdgcn_s_waitcnt(0x0F70);                   // vmcnt(0), as a builtin so that hipcc's wait-count pass sees it: my pieces
@@ -236,7 +222,7 @@ __global__ __launch_bounds__(64 * BB_NW, 1) void bblock48_kernel(const BBlockPar
         asm volatile("s_barrier" ::: "memory");               // ... then everyone's, and everyone is past the old mid
         unsigned tk_next = 0;
         if (tid == 0) tk_next = atomicAdd(p.ticket + xcd, 1u);                // (in flight under conv1)
-        lap(0);
+        clk.lap(0);
         // the previous tile's outputs are stored between conv1's two K-chunks: behind the opening wait (whose vmcnt(0) they would
         // otherwise prolong) and while the SIMD's other wave keeps the matrix pipe busy
         if (wave + BB_NW * (BB_J1 - 1) < BB_MH) {             // the first waves own one mid row more than the others
@@ -248,7 +234,7 @@ __global__ __launch_bounds__(64 * BB_NW, 1) void bblock48_kernel(const BBlockPar
             if (pending && !(p.dbg & 1)) flush();
             mma_chunk(s_w + BB_WBYTES, s_x, boff1, BB_XROW, 1, std::integral_constant<int, BB_J1 - 1>{}, nohook);
         }
-        lap(1);
+        clk.lap(1);
         // residual = centre of the x halo -> registers: the halo region takes the NEXT tile's halo while conv2 runs
         bf16x4 rx[BB_J2][BB_MI];
 #pragma unroll
@@ -278,70 +264,58 @@ __global__ __launch_bounds__(64 * BB_NW, 1) void bblock48_kernel(const BBlockPar
         init_acc(bias2);
         if (tid == 0) s_next[(ti + 1u) & 1u] = (unsigned)t_lo + tk_next;      // (slot of tile ti + 1: last read behind tile ti - 1's mid barrier)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // my mid rows are written, my residual is in registers
-        lap(2);
+        clk.lap(2);
         asm volatile("s_barrier" ::: "memory");               // ... everyone's: mid is complete, nobody reads this x halo any more
         t_next = __builtin_amdgcn_readfirstlane((int)s_next[(ti + 1u) & 1u]);
         tx = t_next % p.tiles_x; ty = (t_next / p.tiles_x) % p.tiles_y; tn = t_next / (p.tiles_x * p.tiles_y);
-        lap(6);
+        clk.lap(6);
         // The next tile's halo lands under conv2.  The four YOUNGER waves (4..7) request it, ten pieces each, before their conv2: the
         // matrix pipe favours the older wave of a SIMD, so waves 0..3 go straight into conv2 (per-wave phase trace, tools/bb_trace.py:
         // requested by all eight waves it cost ~0.9k clk per tile between the barrier and the first conv2 MFMA; spread between the
         // younger waves' k-steps the last pieces were requested too late and the next tile waited for them).
         if (!(p.dbg & 2) && t_next < t_hi && wave >= BB_NW / 2) issue_x(tn, ty * BB_TH, tx * BB_TW, wave - BB_NW / 2, BB_NW / 2);
-        lap(7);
+        clk.lap(7);
         mma_chunk(s_w + 2 * BB_WBYTES, s_mid, boff2, BB_MW * BB_PS, 0, std::integral_constant<int, BB_J2>{}, nohook);
         mma_chunk(s_w + 3 * BB_WBYTES, s_mid, boff2, BB_MW * BB_PS, 1, std::integral_constant<int, BB_J2>{}, nohook);
 
         if ((p.dbg & 2) && t_next < t_hi) issue_x(tn, ty * BB_TH, tx * BB_TW, wave, BB_NW);
-        lap(3);
+        clk.lap(3);
         // epilogue: + x, ReLU -> packed bf16 in registers (4 channels = 8 bytes per lane and fragment); stored by `flush`
-        rs_out = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(p.out) + (size_t)n * img_bytes, 0, (int)img_bytes, 0x00020000);
+        rs_out = buf_rsrc(reinterpret_cast<char*>(p.out) + (size_t)n * img_bytes, (int)img_bytes);
 #pragma unroll
         for (int j = 0; j < BB_J2; ++j) {
             const int r = wave + BB_NW * j, oy = oy0 + r, ox = ox0 + ln;
-            ovoff[j] = (ln < BB_TW && oy < p.H && ox < p.W) ? (unsigned)(((oy * p.W + ox) * 48 + g * 4) * 2) : 0x80000000u;
+            ovoff[j] = (ln < BB_TW && oy < p.H && ox < p.W) ? (unsigned)(((oy * p.W + ox) * 48 + g * 4) * 2) : BUF_OOB;
 #pragma unroll
             for (int mi = 0; mi < BB_MI; ++mi)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) oq[j][mi][e] = (__bf16)fmaxf(acc[mi][j][e] + (float)rx[j][mi][e], 0.f);
         }
         pending = true;
-        lap(4);
-        tsum[5] += 1;
+        clk.lap(4);
+        clk.sum[5] += 1;
     }
     if (pending) flush();
     // every workgroup holds exactly one failing ticket when it leaves; the last one re-arms the counters for the next launch on this stream
-    if (tid == 0 && atomicAdd(p.ticket + 8, 1u) == gridDim.x - 1u) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) p.ticket[i] = 0u;
-        __threadfence();
-    }
-    if (tracing && lane == 0)
-        for (int k = 0; k < 8; ++k) p.trace[((size_t)blockIdx.x * BB_NW + wave) * 8 + k] = tsum[k];
+    if (tid == 0) ticket_leave(p.ticket, 9, 1u);
+    if (clk.on && lane == 0)
+        for (int k = 0; k < 8; ++k) p.trace[((size_t)blockIdx.x * BB_NW + wave) * 8 + k] = clk.sum[k];
 }
 
-int launch_bblock48(const BBlockParams& p0, hipStream_t s) {
+int launch_bblock48(const BBlockParams& p0, int n_cus, hipStream_t s) {
     BBlockParams p = p0;
     p.tiles_x = (p.W + BB_TW - 1) / BB_TW;
     p.tiles_y = (p.H + BB_TH - 1) / BB_TH;
-    p.trace = nullptr;
     static const int dbg = env_int("SNCAL_BB_DBG", 0);
     p.dbg = dbg;
-    static int n_wgs = 0;
-    if (!n_wgs) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bblock48_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        int dev = 0, cus = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        n_wgs = cus >= 8 ? cus / 8 * 8 : 256;                 // one workgroup per CU, a multiple of the 8 XCDs
-    }
+    if (!opt_in_lds<&bblock48_kernel>(160 * 1024)) return SNCAL_ERR_HIP;
+    const int n_wgs = persistent_grid(n_cus);
     static const char* trace_file = getenv("SNCAL_BB_TRACE");
-    const size_t n_trace = (size_t)n_wgs * BB_NW * 8;
-    if (trace_file) p.trace = trace_arm(n_trace, s);
+    TraceScope trace(trace_file, (size_t)n_wgs * BB_NW * 8, s);
+    p.trace = trace.words;
     if (!p.ticket) { set_error("launch_bblock48: no ticket words"); return SNCAL_ERR_ARG; }
     SNCAL_LAUNCH(bblock48_kernel, dim3((unsigned)n_wgs), dim3(64 * BB_NW), (size_t)BB_LDS + 16, s, p);
     SNCAL_CHECK_LAUNCH();
-    trace_dump(p.trace, n_trace, trace_file, s);      // every launch overwrites the dump: the file holds the last fused block of the run
     return SNCAL_OK;
 }
 

@@ -18,6 +18,7 @@ struct BBlockParams {
     unsigned* ticket;       // nine zeroed device words owned by the caller's stream: tile tickets per XCD [0..8), workgroups that ran dry [8] (re-armed by the kernel)
 };
 
-int launch_bblock48(const BBlockParams& p, hipStream_t s);
+// n_cus: compute units of the device (one workgroup per CU: persistent_grid, persist.hpp)
+int launch_bblock48(const BBlockParams& p, int n_cus, hipStream_t s);
 
 }  // namespace sncal

@@ -31,7 +31,7 @@
 // Arithmetic: hi = rne16(v), lo = rne16(v - hi); mid is split exactly like a tensor that conv_tt would have written, so the block
 // equals conv1 -> twin -> conv2 of the two-kernel path up to the summation order inside the matrix unit.
 #include "bblockx3.hpp"
-#include "common.hpp"
+#include "persist.hpp"
 #include "x3.hpp"
 #include <cstdio>
 #include <cstdlib>
@@ -46,7 +46,6 @@ typedef x3h4 h16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
 #define BBX_MFMA(a, b, c) X3_MFMA_16x16x32(a, b, c)
 
 constexpr int TH = 16, TW = 14;                     // output tile
@@ -72,24 +71,12 @@ constexpr unsigned TILE_CONT = 0x40000000u;         // flag in a tile word: the 
 // A continuing tile keeps what it shares with the tile above: x halo rows 16..19 become rows 0..3 (LDS slots 0..383 of either plane, whole
 // 1 KB pieces; the piece that straddles rows 3 | 4 is simply fetched again) and mid rows 16, 17 become rows 0, 1.
 constexpr int KEEP_XROWS = 4, KEEP_PIECES = KEEP_XROWS * XW * 6 / 64, KEEP_SRC = (XH - KEEP_XROWS) * X_PITCH;
-constexpr unsigned OOB = 0xfffffe00u;               // a buffer offset beyond any tensor the launcher accepts (reads return zero, stores are dropped)
+constexpr unsigned OOB = BUF_OOB_WIDE;              // a buffer offset beyond any tensor the launcher accepts (reads return zero, stores are dropped)
 constexpr int RUN_MAX = 8;                          // longest run of vertically adjacent tiles a workgroup takes with one ticket
 static_assert(KEEP_PIECES == 6 && KEEP_SRC + KEEP_PIECES * 1024 <= XH * X_PITCH && KEEP_PIECES * 1024 <= KEEP_XROWS * X_PITCH, "kept halo rows");
 
-// One LDS-DMA piece (64 lanes x 16 bytes -> 1 KB at LDS byte address `lds_addr`) as inline assembly: hipcc's wait-count pass does not
-// see it, so the loader's counter polls are not preceded by vmcnt(0); every wait of this kernel is explicit.
-__device__ __forceinline__ void dma_piece(i32x4_t rsrc, unsigned lds_addr, unsigned voff, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" : : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory", "m0");
-}
-__device__ __forceinline__ i32x4_t raw_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    return i32x4_t{(int)(unsigned)a, (int)(unsigned)((a >> 32) & 0xffffu), (int)bytes, 0x00020000};
-}
-__device__ __forceinline__ unsigned poll(unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void spin_until(unsigned* p, unsigned target) {
-    while ((int)(poll(p) - target) < 0) __builtin_amdgcn_s_sleep(1);
-    asm volatile("" ::: "memory");
-}
+// The loader waves request by dma_piece (persist.hpp: hipcc's wait-count pass does not see it, so their counter polls are not preceded by
+// vmcnt(0)); every wait of this kernel is explicit.
 
 __global__ __launch_bounds__(64 * (NW + 2)) void bblockx3_kernel(const BBlockX3Params p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -118,7 +105,8 @@ __global__ __launch_bounds__(64 * (NW + 2)) void bblockx3_kernel(const BBlockX3P
     const int xcd = (int)blockIdx.x & 7;
     const int h1 = p.H + 1, rows_s = p.N * h1;                     // stacked rows (the last separator is never reached by a valid pixel)
     const int tiles_ys = (rows_s - 1 + TH - 1) / TH;
-    const int y_lo = (int)((long)tiles_ys * xcd / 8), y_hi = (int)((long)tiles_ys * (xcd + 1) / 8);
+    int y_lo, y_hi;
+    xcd_share(tiles_ys, xcd, y_lo, y_hi);
     const unsigned lds0 = (unsigned)(__UINTPTR_TYPE__)(__attribute__((address_space(3))) char*)smem;
     const unsigned img_twin = (unsigned)(p.H * p.W * 192);
     // stacked row v -> (frame, row in frame): v / h1 by multiplication (exact for v h1 < 2^32: the launcher bounds N)
@@ -135,7 +123,8 @@ __global__ __launch_bounds__(64 * (NW + 2)) void bblockx3_kernel(const BBlockX3P
         // tile rows for eight XCDs, one of them with two rounds of tiles) -- the row-major tile list is cut into eight equal shares instead
         const bool flat = tiles_ys < 64;
         const int n_tiles = tiles_ys * p.tiles_x;
-        const int t_lo = (int)((long)n_tiles * xcd / 8), t_hi = (int)((long)n_tiles * (xcd + 1) / 8);
+        int t_lo, t_hi;
+        xcd_share(n_tiles, xcd, t_lo, t_hi);
         // phases of the XCD's deal: rows_of[k] tile rows in runs of RUN_MAX >> k tiles
         int rows_of[4];
         {
@@ -199,11 +188,7 @@ __global__ __launch_bounds__(64 * (NW + 2)) void bblockx3_kernel(const BBlockX3P
                 prev_cont = false;
             }
             if (dry) {
-                if (lane == 0 && atomicAdd(p.ticket + 8, 1u) == gridDim.x - 1u) {     // every workgroup holds its one failing ticket
-#pragma unroll
-                    for (int i = 0; i < 9; ++i) p.ticket[i] = 0u;
-                    __threadfence();
-                }
+                if (lane == 0) ticket_leave(p.ticket, 9, 1u);
                 break;
             }
             const int oy0 = (row0 + k) * TH - 2, ox0 = strip * TW - 2;
@@ -361,10 +346,8 @@ __global__ __launch_bounds__(64 * (NW + 2)) void bblockx3_kernel(const BBlockX3P
         }
     };
 
-    unsigned long long tsum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tprev = 0;
-    const bool tracing = p.trace != nullptr;
+    PhaseClock clk(p.trace);                           // (tuning aid, SNCAL_BBX_TRACE; slots: tools/bbx_trace.py)
     float amax = 0.f;                                  // range tracker of the mid and output splits (x3.hpp)
-    auto lap = [&](int k) { if (tracing) { const unsigned long long now = __builtin_amdgcn_s_memtime(); tsum[k] += now - tprev; tprev = now; } };
 
     bool at_cont = false;
     unsigned n_cont = 0;                               // continuing tiles so far
@@ -377,10 +360,10 @@ __global__ __launch_bounds__(64 * (NW + 2)) void bblockx3_kernel(const BBlockX3P
         const int tx = t % p.tiles_x, ys = t / p.tiles_x;
         const int oy0 = ys * TH, ox0 = tx * TW;                       // (oy0: stacked row)
         const unsigned gs = (unsigned)ti * 2u * BBX_STEPS;
-        if (tracing) tprev = __builtin_amdgcn_s_memtime();
+        clk.start();
         init_acc(0);
         spin_until(ctrl + C_XREADY, (unsigned)ti + 1u);                   // this tile's halo has landed
-        lap(0);
+        clk.lap(0);
         // conv1.  First tile of a run: mid rows f = wave + 8 j of all 18 (waves 0 and 1 own three, the others two); continuing tile: rows
         // 0, 1 are the tile above's rows 16, 17 (copied below), f = 2 + wave + 8 j of the 16 new ones
         const int f0 = cont ? 2 : 0;
@@ -398,7 +381,7 @@ __global__ __launch_bounds__(64 * (NW + 2)) void bblockx3_kernel(const BBlockX3P
             conv(std::integral_constant<int, J1>{}, std::integral_constant<int, X_PITCH>{}, std::integral_constant<int, 0>{}, bc1, bh1, gs);
         else
             conv(std::integral_constant<int, J1 - 1>{}, std::integral_constant<int, X_PITCH>{}, std::integral_constant<int, 0>{}, bc1, bh1, gs);
-        lap(1);
+        clk.lap(1);
         // residual = centre of the x halo -> registers (hi + lo), then the halo region is free for the next tile
         f32x4 res[J2][3];
 #pragma unroll
@@ -437,18 +420,16 @@ __global__ __launch_bounds__(64 * (NW + 2)) void bblockx3_kernel(const BBlockX3P
         }
         signal(C_MID);
         init_acc(1);
-        lap(2);
+        clk.lap(2);
         spin_until(ctrl + C_MID, (unsigned)NW * ((unsigned)ti + 1u));     // everyone's mid rows are written
-        lap(3);
+        clk.lap(3);
         conv(std::integral_constant<int, J2>{}, std::integral_constant<int, M_PITCH>{}, std::integral_constant<int, BBX_STEPS % RING_SLOTS>{}, bc2, bh2, gs + BBX_STEPS);
-        lap(4);
+        clk.lap(4);
         // epilogue: + x, ReLU -> split twin (8 + 8 bytes per lane and block: the four lanes of a pixel complete 32-byte halves) and / or fp32
         const bool has_tw = p.out_twin != nullptr, has_f = p.out != nullptr;
         const unsigned img_f32 = (unsigned)(p.H * p.W * p.out_cstride * 4);
-        const __amdgpu_buffer_rsrc_t rs_tw = __builtin_amdgcn_make_buffer_rsrc(has_tw ? p.out_twin : const_cast<void*>(p.x), 0,
-                                                                                 has_tw && !(p.dbg & 1) ? (int)((unsigned)p.N * img_twin) : 0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_f = __builtin_amdgcn_make_buffer_rsrc(has_f ? static_cast<void*>(p.out) : const_cast<void*>(p.x), 0,
-                                                                                has_f && !(p.dbg & 1) ? (int)((unsigned)p.N * img_f32) : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_tw = buf_rsrc(has_tw ? p.out_twin : p.x, has_tw && !(p.dbg & 1) ? (int)((unsigned)p.N * img_twin) : 0);
+        const __amdgpu_buffer_rsrc_t rs_f = buf_rsrc(has_f ? static_cast<const void*>(p.out) : p.x, has_f && !(p.dbg & 1) ? (int)((unsigned)p.N * img_f32) : 0);
 #pragma unroll
         for (int j = 0; j < J2; ++j) {
             const int vs = oy0 + wave + NW * j, ox = ox0 + ln;
@@ -478,17 +459,17 @@ __global__ __launch_bounds__(64 * (NW + 2)) void bblockx3_kernel(const BBlockX3P
                 }
             }
         }
-        lap(5);
-        tsum[7] += 1;
+        clk.lap(5);
+        clk.sum[7] += 1;
     }
     x3_report(amax, p.range);
-    if (tracing && lane == 0)
-        for (int k = 0; k < 8; ++k) p.trace[((size_t)blockIdx.x * NW + wave) * 8 + k] = tsum[k];
+    if (clk.on && lane == 0)
+        for (int k = 0; k < 8; ++k) p.trace[((size_t)blockIdx.x * NW + wave) * 8 + k] = clk.sum[k];
 }
 
 }  // namespace
 
-int launch_bblockx3(const BBlockX3Params& p0, hipStream_t s) {
+int launch_bblockx3(const BBlockX3Params& p0, int n_cus, hipStream_t s) {
     BBlockX3Params p = p0;
     // one launch addresses its tensors with 32-bit buffer offsets: more frames than fit go in several launches
     const size_t img = (size_t)p.H * p.W * (size_t)(p.out && p.out_cstride * 4 > 192 ? p.out_cstride * 4 : 192);
@@ -506,7 +487,7 @@ int launch_bblockx3(const BBlockX3Params& p0, hipStream_t s) {
             q.x = static_cast<const char*>(p0.x) + (size_t)n0 * p.H * p.W * 192;
             if (p0.out_twin) q.out_twin = static_cast<char*>(p0.out_twin) + (size_t)n0 * p.H * p.W * 192;
             if (p0.out) q.out = p0.out + (size_t)n0 * p.H * p.W * p.out_cstride;
-            const int rc = launch_bblockx3(q, s);
+            const int rc = launch_bblockx3(q, n_cus, s);
             if (rc) return rc;
         }
         return SNCAL_OK;
@@ -516,24 +497,16 @@ int launch_bblockx3(const BBlockX3Params& p0, hipStream_t s) {
     p.h1_magic = (unsigned)((((unsigned long long)1 << 32) / (unsigned)(p.H + 1)) + 1ull);
     static const int run_max = env_int("SNCAL_BBX_RUNS", RUN_MAX);
     p.run_max = run_max < 1 ? 1 : run_max;
-    p.trace = nullptr;
     static const int dbg = env_int("SNCAL_BBX_DBG", 0);
     p.dbg = dbg;
-    static int n_wgs = 0;
-    if (!n_wgs) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bblockx3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        int dev = 0, cus = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        n_wgs = cus >= 8 ? cus / 8 * 8 : 256;                 // one workgroup per CU, a multiple of the 8 XCDs
-    }
+    if (!opt_in_lds<&bblockx3_kernel>(160 * 1024)) return SNCAL_ERR_HIP;
+    const int n_wgs = persistent_grid(n_cus);
     static const char* trace_file = getenv("SNCAL_BBX_TRACE");
-    const size_t n_trace = (size_t)n_wgs * NW * 8;
-    if (trace_file) p.trace = trace_arm(n_trace, s);
+    TraceScope trace(trace_file, (size_t)n_wgs * NW * 8, s);
+    p.trace = trace.words;
     if (!p.ticket) { set_error("launch_bblockx3: no ticket words"); return SNCAL_ERR_ARG; }
     SNCAL_LAUNCH(bblockx3_kernel, dim3((unsigned)n_wgs), dim3(64 * (NW + 2)), (size_t)LDS_BYTES, s, p);
     SNCAL_CHECK_LAUNCH();
-    trace_dump(p.trace, n_trace, trace_file, s);      // every launch overwrites the dump: the file holds the last fused block of the run
     return SNCAL_OK;
 }
 

@@ -29,7 +29,8 @@ struct BBlockX3Params {
     unsigned* ticket;       // nine zeroed device words owned by the caller's stream: tile tickets per XCD [0..8), workgroups that ran dry [8] (re-armed by the kernel)
 };
 
-int launch_bblockx3(const BBlockX3Params& p, hipStream_t s);
+// n_cus: compute units of the device (one workgroup per CU: persistent_grid, persist.hpp)
+int launch_bblockx3(const BBlockX3Params& p, int n_cus, hipStream_t s);
 
 // Pair-step order of the K loop (shared by the kernel and the packing).  Unit = (tap (dy, dx), 16-channel group g); step s multiplies
 // units u0(s) and u1(s): the two cross terms of each on its own (w_hi.x_lo + w_lo.x_hi in ONE K = 32 MFMA) and the two main terms

@@ -19,7 +19,7 @@
 // 192 MFMAs per group = 0.16 ms of matrix-pipe time per seam chip-wide: the kernel is a memory stream (per pixel 256 + 1024 B read,
 // 1024 + 256 B written), the residual of the next block is requested before the current one is multiplied.  All 128 KB of split
 // weights stay in LDS (one workgroup of 8 wavefronts per CU, persistent).
-#include "common.hpp"
+#include "persist.hpp"
 #include "bneckx3.hpp"
 #include "x3.hpp"
 #include <algorithm>
@@ -179,10 +179,7 @@ __global__ __launch_bounds__(64 * NW, 1) void bneck_pair_kernel(const BneckPairP
         }
     }
     x3_report(amax, p.range);
-    if (lane == 0 && atomicAdd(p.ticket + 1, 1u) == gridDim.x * NW - 1u) {      // every wave holds its one failing ticket: nobody touches the counter any more
-        p.ticket[0] = 0u; p.ticket[1] = 0u;
-        __threadfence();
-    }
+    if (lane == 0) ticket_leave(p.ticket, 2, NW);      // every WAVE holds its one failing ticket
 }
 
 }  // namespace
@@ -192,12 +189,7 @@ int launch_bneck_pair_x3(const BneckPairParams& p, int n_cus, hipStream_t s) {
     const bool ds = p.wds != nullptr;
     if (!p.ticket) { set_error("launch_bneck_pair_x3: no ticket words"); return SNCAL_ERR_ARG; }
     if (ds == (p.w1 != nullptr)) { set_error("launch_bneck_pair_x3: exactly one of the next block's conv1 and the downsample branch"); return SNCAL_ERR_ARG; }
-    static bool attr_done = false;
-    if (!attr_done) {
-        SNCAL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bneck_pair_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, BNP_LDS));
-        SNCAL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&bneck_pair_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, BNP_LDS));
-        attr_done = true;
-    }
+    if (!opt_in_lds<&bneck_pair_kernel<false, true>, &bneck_pair_kernel<true, false>>(BNP_LDS)) return SNCAL_ERR_HIP;
     const long long G = (p.P + 31) / 32;
     const unsigned blocks = (unsigned)std::min<long long>((G + NW - 1) / NW, n_cus > 0 ? n_cus : 256);
     if (ds) SNCAL_LAUNCH((bneck_pair_kernel<true, false>), dim3(blocks), dim3(64 * NW), (size_t)BNP_LDS, s, p);

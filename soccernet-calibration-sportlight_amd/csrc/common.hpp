@@ -30,11 +30,6 @@ static inline int env_int(const char* name, int dflt) {
     return v ? atoi(v) : dflt;
 }
 
-// Phase traces of the tuning aids (SNCAL_*_TRACE): trace_arm gives a kernel n zeroed 64-bit words on `stream` (null when the
-// allocation fails); after the launch trace_dump synchronises the stream, writes the words to `file` and frees them (no-op on null)
-unsigned long long* trace_arm(size_t n, hipStream_t stream);
-void trace_dump(unsigned long long* d_trace, size_t n, const char* file, hipStream_t stream);
-
 // solve.hip: release the scratch block(s) sncal_calibrate keeps per (device, stream) -- one stream's, or all of them
 int release_solve_scratch(hipStream_t st, bool all);
 

@@ -49,7 +49,7 @@
 #include "x3.hpp"
 #include <hip/hip_runtime.h>
 #include <cstdint>
-#include "common.hpp"
+#include "persist.hpp"
 
 namespace sncal {
 
@@ -222,9 +222,8 @@ __device__ __forceinline__ void conv_body(const ConvParams& p, const unsigned w)
 
     // buffer descriptors: one image of the input (so that ranges stay < 2 GB), the packed weights
     const size_t img_bytes = (size_t)p.Hin * p.Win * p.Cin * ESIZE;
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<char*>(reinterpret_cast<const char*>(p.in)) + (size_t)n * img_bytes, 0, (int)img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w), 0, (int)p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = buf_rsrc(reinterpret_cast<const char*>(p.in) + (size_t)n * img_bytes, (int)img_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(p.w, (int)p.w_bytes);
     const int n_halo_instr = halo_bytes / 1024;
 
     // LDS: [weight chunk][halo tile]
@@ -257,7 +256,7 @@ __device__ __forceinline__ void conv_body(const ConvParams& p, const unsigned w)
         const int iy = oy00 * STRIDE - PAD + (int)hy, ix = ix0 + (int)hx;
         const bool ok = (cg < (unsigned)G) & (pix < (unsigned)npix) & ((unsigned)iy < (unsigned)p.Hin) &
                         ((unsigned)ix < (unsigned)p.Win) & ((int)(c_lo + cg) < cin_groups);
-        return ok ? (unsigned)(((iy * p.Win + ix) * p.Cin) * ESIZE + cg * 16) : 0x80000000u;
+        return ok ? (unsigned)(((iy * p.Win + ix) * p.Cin) * ESIZE + cg * 16) : BUF_OOB;
     };
     unsigned hv[MAXH];
     if (HOIST) {
@@ -276,7 +275,7 @@ __device__ __forceinline__ void conv_body(const ConvParams& p, const unsigned w)
                 const int j = wave + 4 * jj;
                 if (j < n_halo_instr) {
                     unsigned voff = hv[jj];
-                    if (tail) { const int slot = j * 64 + lane; if (c * G + slot % SLOTS >= cin_groups) voff = 0x80000000u; }
+                    if (tail) { const int slot = j * 64 + lane; if (c * G + slot % SLOTS >= cin_groups) voff = BUF_OOB; }
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_void*)(si + j * 1024), 16, voff, cbase, 0, 0);
                 }
             }
@@ -314,15 +313,16 @@ __device__ __forceinline__ void conv_body(const ConvParams& p, const unsigned w)
         const int ox = ox0 + fx * 16 + px;
         const int co = nb * EPI_CO + grp * 8;
         const bool ok = (id < EPI_ITEMS) & (oy < p.Hout) & (ox < p.Wout) & (co < p.cout);
-        return ok ? (unsigned)(((oy * p.Wout + ox) * p.out_cstride + p.out_coff + co) * 2) : 0x80000000u;      // bytes inside the image; out of range = nothing
+        return ok ? (unsigned)(((oy * p.Wout + ox) * p.out_cstride + p.out_coff + co) * 2) : BUF_OOB;      // bytes inside the image; out of range = nothing
     };
     // branch-free residual loads / output stores of epilogue A: per-image buffer descriptors, a missing residual is a zero-sized one
     // (loads return zeros), an item outside the image carries an out-of-range offset (epilogue F has the measurements)
     typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
     const int img_b16 = p.Hout * p.Wout * p.out_cstride * 2;
+    // (the descriptors chosen by a ?: spell the builtin out: through buf_rsrc the selects come out in another order)
     const __amdgpu_buffer_rsrc_t rs_res16 = __builtin_amdgcn_make_buffer_rsrc(
         p.res ? const_cast<char*>(reinterpret_cast<const char*>(p.res)) + img_out * 2 : const_cast<char*>(reinterpret_cast<const char*>(p.in)), 0,
-        p.res ? img_b16 : 0, 0x00020000);
+        p.res ? img_b16 : 0, BUF_FLAGS);
     if constexpr (GE == 8 && RES_PF) {
         if (epi_a) {
 #pragma unroll
@@ -465,7 +465,7 @@ __device__ __forceinline__ void conv_body(const ConvParams& p, const unsigned w)
             constexpr int JB = conv_epi_frags(KS, NI, MI, G);                              // fragments staged at a time
             float* stg = reinterpret_cast<float*>(smem) + wave * (JB * 16 * PITCH);
             constexpr int GROUPS = EPI_GROUPS, EITERS = EPI_ITERS;
-            const __amdgpu_buffer_rsrc_t rs_out16 = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(p.out) + img_out * 2, 0, img_b16, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rs_out16 = buf_rsrc(reinterpret_cast<char*>(p.out) + img_out * 2, img_b16);
             // item offsets: kept from the prologue when the residual was prefetched; otherwise computed here and the
             // residual is requested for ALL fragments first -- the fragment registers of the main loop are dead --
             // so its latency is paid once, not once per staged block
@@ -555,12 +555,12 @@ __device__ __forceinline__ void conv_body(const ConvParams& p, const unsigned w)
             const int img_b = p.Hout * p.Wout * p.out_cstride * 4;              // bytes of one image of the output tensor (< 2 GB)
             char* const in_c = const_cast<char*>(reinterpret_cast<const char*>(p.in));
             const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc(
-                p.res ? const_cast<char*>(reinterpret_cast<const char*>(p.res)) + img_out * 4 : in_c, 0, p.res ? img_b : 0, 0x00020000);
+                p.res ? const_cast<char*>(reinterpret_cast<const char*>(p.res)) + img_out * 4 : in_c, 0, p.res ? img_b : 0, BUF_FLAGS);
             const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(
-                p.out ? reinterpret_cast<char*>(p.out) + img_out * 4 : in_c, 0, p.out ? img_b : 0, 0x00020000);
+                p.out ? reinterpret_cast<char*>(p.out) + img_out * 4 : in_c, 0, p.out ? img_b : 0, BUF_FLAGS);
             const bool has_twin = Elem<T>::X3 && p.out_twin != nullptr;         // dense output (out_coff 0, stride = cout): same image size
             const __amdgpu_buffer_rsrc_t rs_tw = __builtin_amdgcn_make_buffer_rsrc(
-                has_twin ? reinterpret_cast<char*>(p.out_twin) + img_out * 4 : in_c, 0, has_twin ? img_b : 0, 0x00020000);
+                has_twin ? reinterpret_cast<char*>(p.out_twin) + img_out * 4 : in_c, 0, has_twin ? img_b : 0, BUF_FLAGS);
             // item offsets + residuals: for ALL fragments up front when the registers allow (the latency is paid once), else one
             // fragment ahead
             constexpr int NR = PRE_ALL ? NI : 2 * JB;
@@ -577,7 +577,7 @@ __device__ __forceinline__ void conv_body(const ConvParams& p, const unsigned w)
                     const int ox = ox0 + fx * 16 + px;
                     const int co = nb * CO + grp * 4;
                     const bool ok = (oy < p.Hout) & (ox < p.Wout) & (co < p.cout);
-                    off[slot][it] = ok ? (unsigned)(((oy * p.Wout + ox) * p.out_cstride + p.out_coff + co) * 4) : 0x80000000u;
+                    off[slot][it] = ok ? (unsigned)(((oy * p.Wout + ox) * p.out_cstride + p.out_coff + co) * 4) : BUF_OOB;
                     rr[slot][it] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, off[slot][it], 0, 0);
                 }
             };
@@ -629,7 +629,7 @@ __device__ __forceinline__ void conv_body(const ConvParams& p, const unsigned w)
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) X3_SPLIT1(v[e], th[e], tl[e]);
                                 const unsigned c16 = (unsigned)(grp * 4) & 15u;          // (nb * CO is a multiple of 16)
-                                const unsigned toff = o == 0x80000000u ? o : o - c16 * 2;  // byte offset of the group's hi half + this lane's 8 bytes
+                                const unsigned toff = o == BUF_OOB ? o : o - c16 * 2;  // byte offset of the group's hi half + this lane's 8 bytes
                                 u32x2 t0 = __builtin_bit_cast(u32x2, th), t1 = __builtin_bit_cast(u32x2, tl);
                                 asm volatile("" : "+v"(t0), "+v"(t1), "+v"(ov));
                                 __builtin_amdgcn_raw_buffer_store_b64(t0, rs_tw, toff, 0, 0);
@@ -790,23 +790,13 @@ struct ConvVariant {
 
 template <typename T, int KS, int STRIDE, int NI, int MI, int G>
 void conv_launch(const ConvParams& p, dim3 grid, size_t lds, hipStream_t s) {
-    static bool attr_done = false;
-    if (!attr_done) {   // > 64 KB dynamic LDS needs the opt-in attribute
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_kernel<T, KS, STRIDE, NI, MI, G>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done = true;
-    }
+    opt_in_lds<&conv_kernel<T, KS, STRIDE, NI, MI, G>>(160 * 1024);
     SNCAL_LAUNCH((conv_kernel<T, KS, STRIDE, NI, MI, G>), grid, dim3(256), lds, s, p);
 }
 
 template <typename T, int KS, int STRIDE, int NI, int MI, int G>
 void conv_group_launch(const ConvGroupParams& gp, dim3 grid, size_t lds, hipStream_t s) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_group_kernel<T, KS, STRIDE, NI, MI, G>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done = true;
-    }
+    opt_in_lds<&conv_group_kernel<T, KS, STRIDE, NI, MI, G>>(160 * 1024);
     SNCAL_LAUNCH((conv_group_kernel<T, KS, STRIDE, NI, MI, G>), grid, dim3(256), lds, s, gp);
 }
 

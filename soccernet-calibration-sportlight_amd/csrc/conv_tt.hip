@@ -33,7 +33,7 @@
 // rotation is applied on the DMA's per-lane SOURCE address, the LDS destination stays lane-linear.
 // Work items (tile x 96-channel block, cost = Cin / 32 stages) of up to three member convolutions are dealt to the
 // 2 x 256 teams on the host (conv_tt_plan in hrnet.cpp): contiguous slices per XCD, longest-processing-time first.
-#include "common.hpp"
+#include "persist.hpp"
 #include "conv_tt.hpp"
 #include "x3.hpp"
 #include <cstddef>
@@ -95,15 +95,7 @@ __device__ __forceinline__ TTMember load_member(int m) {
 #undef TT_CFG_NB
 
 void launch_conv_tt(const TTParams& p, int n_wgs, int mode, hipStream_t s, int cfg) {
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&c32::conv_tt_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&c32::conv_tt_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&c32::conv_tt_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&c23::conv_tt_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&c31::conv_tt_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_done = true;
-    }
+    opt_in_lds<&c32::conv_tt_kernel<0>, &c32::conv_tt_kernel<1>, &c32::conv_tt_kernel<2>, &c23::conv_tt_kernel<2>, &c31::conv_tt_kernel<2>>(160 * 1024);
     if (cfg == 2) {                                    // 96 output channels x 4 rows x 32 columns (split arithmetic, small launches)
         const size_t lds = (size_t)2 * c31::TEAM_BYTES + 64 + 2 * TT_TABLE_MAX * 4;
         SNCAL_LAUNCH(c31::conv_tt_kernel<2>, dim3((unsigned)n_wgs), dim3(512), lds, s, p);

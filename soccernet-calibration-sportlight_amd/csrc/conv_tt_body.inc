@@ -103,7 +103,7 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
         const int y = s - (int)f * (M.H + 1);
         const int x = col0 - 1 + (int)hcol;
         const bool ok = (hrow < (unsigned)HROWS) & (hcol < 34u) & (s >= 0) & ((int)f < M.N) & (y < M.H) & ((unsigned)x < (unsigned)M.W);
-        return ok ? (unsigned)((((int)f * M.H + y) * M.W + x) * M.Cin * (FP8 ? 1 : 2)) + cg * 16u : 0x80000000u;
+        return ok ? (unsigned)((((int)f * M.H + y) * M.W + x) * M.Cin * (FP8 ? 1 : 2)) + cg * 16u : BUF_OOB;
     };
 
     // (bf16x3: called AFTER the first stage's DMA wait, so that the accumulator registers are free while the residual loads are in flight)
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
         int lane_l = lane;                 // laundered: hipcc would hoist the lane-only parts out of the stage loop and spill them
         asm volatile("" : "+v"(lane_l));
 #pragma unroll
-        for (int jj = 0; jj < HV; ++jj) hv[jj] = tw + 4 * jj < HALO_PIECES ? halo_voff(tw + 4 * jj, lane_l) : 0x80000000u;
+        for (int jj = 0; jj < HV; ++jj) hv[jj] = tw + 4 * jj < HALO_PIECES ? halo_voff(tw + 4 * jj, lane_l) : BUF_OOB;
     };
     auto setup_item = [&](const TTItem I) {
         M = load_member(I.member);
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
         const int coff = rs ? 0 : M.out_coff;
         const int lane_ch = rs ? hi * 4 : hi * 8;                 // in 4-byte units inside the 16-channel group
         const unsigned second = rs ? 32u : 16u;
-        const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(M.res), 0, (int)(unsigned)(M.N * M.H * M.W * cstr * 4), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_res = buf_rsrc(M.res, (int)(unsigned)(M.N * M.H * M.W * cstr * 4));
         const unsigned lane_off = (unsigned)((l31 * cstr + lane_ch) * 4);
 #pragma unroll
         for (int jr = 0; jr < (X3 ? NB : 1); ++jr) {
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
 #pragma unroll
             for (int u = 0; u < (X3 ? NU : 1); ++u) {
                 const bool live = nb * COUT_BLK + u * 16 < M.cout;        // wave-uniform: padded groups of a narrow layer
-                const unsigned v = (px_ok & live) ? lane_off + (unsigned)(u * 64) : 0x80000000u;
+                const unsigned v = (px_ok & live) ? lane_off + (unsigned)(u * 64) : BUF_OOB;
                 rres[jr][u][0] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, v, soff, 0);
                 rres[jr][u][1] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, v, soff + second, 0);
             }
@@ -233,8 +233,8 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
 
     auto setup_done_stamp = [&]() { if (eix > 192) estamp(); };
     auto issue_stage = [&](int cc) {
-        const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(M.in), 0, (int)M.in_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(M.w), 0, (int)M.w_bytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_in = buf_rsrc(M.in, (int)M.in_bytes);
+        const __amdgpu_buffer_rsrc_t rs_w = buf_rsrc(M.w, (int)M.w_bytes);
         // (weights first: requesting the halo pieces first -- they come from HBM / the Infinity Cache, the weights from L2 -- was measured
         // 1.3 % slower on the fp16x3 step, round 4)
         const unsigned wbase = (unsigned)((nb * M.chunks + cc) * W_BYTES);
@@ -257,11 +257,11 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
         // fp32 in, fp32 out: (+ residual) (ReLU), 8 channels = 32 bytes per lane and item = two b128 accesses each way; channel blocks
         // beyond the layer's width (a 48-channel layer runs as one 96-channel item with zero weights above 48) are not stored
         const unsigned out_bytes = (unsigned)(M.N * M.H * M.W * M.out_cstride * 4);
-        const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(M.out ? M.out : const_cast<void*>(M.in), 0, M.out ? (int)out_bytes : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_out = buf_rsrc(M.out ? M.out : M.in, M.out ? (int)out_bytes : 0);
         // split twin of the output for the next bf16x3 convolution ([16 hi | 16 lo] bf16 per 16-channel group: 4 bytes per element like
         // the fp32 tensor; written here the consumer needs no separate split pass).  Twin tensors are dense: stride = the layer's width.
         const unsigned twin_bytes = (unsigned)(M.N * M.H * M.W * M.cout * 4);
-        const __amdgpu_buffer_rsrc_t rs_tw = __builtin_amdgcn_make_buffer_rsrc(M.out8 ? M.out8 : const_cast<void*>(M.in), 0, M.out8 ? (int)twin_bytes : 0, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_tw = buf_rsrc(M.out8 ? M.out8 : M.in, M.out8 ? (int)twin_bytes : 0);
         const bool has_twin = M.out8 != nullptr;
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         const bool narrow48 = COUT_BLK == 64 && M.cout - nb * COUT_BLK == 48;        // wave-uniform
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
                     for (int k = 0; k < 8; ++k) v[k] = acc[mb][jr][8 * pq + k];
                     u32x4 t0, t1;
                     x3_split8(v, lob, t0, t1, amax);        // (ReLU is the split's lower clamp bound)
-                    const unsigned vt = px_ok ? (unsigned)(l31 * M.cout * 4 + u * 64 + hi * 16) : 0x80000000u;
+                    const unsigned vt = px_ok ? (unsigned)(l31 * M.cout * 4 + u * 64 + hi * 16) : BUF_OOB;
                     asm volatile("" : "+v"(t0), "+v"(t1));
                     __builtin_amdgcn_raw_buffer_store_b128(t0, rs_tw, vt, soff_tw, 0);
                     __builtin_amdgcn_raw_buffer_store_b128(t1, rs_tw, vt, soff_tw + 32u, 0);
@@ -319,11 +319,11 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
                 const int id = e * 64 + lane_l;
                 const int px = narrow48 ? id / 6 : id / EPI_GROUPS, grp = id - px * (narrow48 ? 6 : EPI_GROUPS);
                 const bool ok = row_ok & (px < M.W - col0) & (nb * COUT_BLK + grp * 8 < M.cout);
-                const unsigned voff = ok ? (unsigned)((px * M.out_cstride + grp * 8) * 4) : 0x80000000u;
+                const unsigned voff = ok ? (unsigned)((px * M.out_cstride + grp * 8) * 4) : BUF_OOB;
                 const float* sp = stg + px * EPI_PITCH + grp * 8;
                 const float4 lo = *reinterpret_cast<const float4*>(sp), hi4 = *reinterpret_cast<const float4*>(sp + 4);
                 float v[8] = {lo.x, lo.y, lo.z, lo.w, hi4.x, hi4.y, hi4.z, hi4.w};
-                const unsigned voff_tw = ok ? (unsigned)(px * M.cout * 4 + (grp >> 1) * 64 + (grp & 1) * 16) : 0x80000000u;
+                const unsigned voff_tw = ok ? (unsigned)(px * M.cout * 4 + (grp >> 1) * 64 + (grp & 1) * 16) : BUF_OOB;
                 if (M.relu) {
 #pragma unroll
                     for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
@@ -357,12 +357,9 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
         if (P.ablate & 1) return;
         if constexpr (X3) { epilogue_x3(); return; }
         const unsigned out_bytes = (unsigned)(M.N * M.H * M.W * M.out_cstride * 2);
-        const __amdgpu_buffer_rsrc_t rs_out8 = __builtin_amdgcn_make_buffer_rsrc(FP8 && M.out8 ? M.out8 : const_cast<void*>(M.in), 0,
-                                                                                   FP8 && M.out8 ? (int)(out_bytes / 2) : 0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_res = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(M.res ? M.res : M.in), 0,
-                                                                                  M.res ? (int)out_bytes : 0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(M.out ? M.out : const_cast<void*>(M.in), 0,
-                                                                                  M.out ? (int)out_bytes : 0, 0x00020000);     // no bf16 output: zero-sized
+        const __amdgpu_buffer_rsrc_t rs_out8 = buf_rsrc(FP8 && M.out8 ? M.out8 : M.in, FP8 && M.out8 ? (int)(out_bytes / 2) : 0);
+        const __amdgpu_buffer_rsrc_t rs_res = buf_rsrc(M.res ? M.res : M.in, M.res ? (int)out_bytes : 0);
+        const __amdgpu_buffer_rsrc_t rs_out = buf_rsrc(M.out ? M.out : M.in, M.out ? (int)out_bytes : 0);     // no bf16 output: zero-sized
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         const bool has_res = M.res != nullptr;      // the first conv of a BasicBlock has none: no loads, no unpack / add (a VALU
         estamp();                                   // instruction beside a multiplying partner costs ~8 clk, a load ~160)
@@ -390,7 +387,7 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
             soff[jr] = row_ok ? (unsigned)(((((int)f * M.H + y) * M.W + col0) * M.out_cstride + M.out_coff + nb * COUT_BLK) * 2) : 0u;
 #pragma unroll
             for (int e = 0; e < EPI_ITERS; ++e) {
-                voff[jr][e] = (row_ok & (px_e[e] < M.W - col0)) ? lane_off[e] : 0x80000000u;      // out of range: loads 0, stores nothing
+                voff[jr][e] = (row_ok & (px_e[e] < M.W - col0)) ? lane_off[e] : BUF_OOB;      // out of range: loads 0, stores nothing
                 rr[jr][e] = u32x4{0u, 0u, 0u, 0u};
                 if (has_res) rr[jr][e] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, voff[jr][e], soff[jr], 0);     // wave-uniform branch
             }
@@ -446,7 +443,7 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
                     int p1 = __builtin_amdgcn_cvt_pk_fp8_f32(w8[4], w8[5], 0, false);
                     p1 = __builtin_amdgcn_cvt_pk_fp8_f32(w8[6], w8[7], p1, true);
                     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-                    const unsigned v8 = voff[jr][e] == 0x80000000u ? 0x80000000u : voff[jr][e] >> 1;
+                    const unsigned v8 = voff[jr][e] == BUF_OOB ? BUF_OOB : voff[jr][e] >> 1;
                     u32x4 qd = __builtin_bit_cast(u32x4, q);
                     u32x2 pd = u32x2{(unsigned)p0, (unsigned)p1};
                     asm volatile("" : "+v"(qd), "+v"(pd));      // both packs are complete, in registers of their own, before either store
@@ -622,11 +619,6 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
         }
     }
     __syncthreads();
-    auto poll = [&](unsigned* p) -> unsigned { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
-    auto spin_until = [&](unsigned* p, unsigned target) {
-        while ((int)(poll(p) - target) < 0) __builtin_amdgcn_s_sleep(1);
-        asm volatile("" ::: "memory");
-    };
     // The next item's descriptor is fetched ahead (a load that misses every cache: 2-3k clk if waited for on the spot) and published
     // right behind the first stage's own DMA wait (`q_advance`): picking it up at the tile boundary instead meant
     // s_waitcnt vmcnt(0) there -- gfx9 counts stores in vmcnt -- i.e. a full drain of the finished tile's stores in front of the set-up.
@@ -834,6 +826,7 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
     if (st > 0) epilogue();
     if constexpr (X3) x3_report(amax, P.range);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // (wave 0: its last ticket has come back as well)
+    // the per-XCD form of ticket_leave (persist.hpp), at agent scope:
     // the leavers are counted per XCD (32 atomics on an address at the end of a launch, not 512); the last workgroup of an XCD re-arms that
     // XCD's two words for the next launch on this stream: every grabber of the XCD holds its failing tickets and has left the queue
     const unsigned q_wgs = (gridDim.x - q_xcd + 7u) / 8u;         // (only team 0's wave 0 draws tickets: workgroups are counted)

@@ -18,7 +18,7 @@
 // of the threshold.
 // Pinned by tests/test_evaluate_edges_gpu.py on hand-built tables (every boundary above with a closed-form answer) and
 // on cameras a metre above the grass / zoomed 3x against the oracle, the launch above 64 KiB of LDS included.
-#include "common.hpp"
+#include "persist.hpp"
 #include "../../include/sncal.h"
 
 namespace {
@@ -211,13 +211,9 @@ extern "C" int sncal_evaluate_cameras_detail(const sncal_camera* d_cams, int B, 
     SNCAL_CHECK_HIP(hipStreamSynchronize(sncal::as_stream(stream)));
     SNCAL_CHECK_ARG(n_pts > 0 && n_pts <= 2048, "sncal_evaluate_cameras: %d pitch samples", n_pts);
     const size_t lds = (size_t)n_pts * 16 + (size_t)(2 * n_pts + 2 * n_cls) * 16 + (size_t)n_pts * 4;
-    // Tables above 64 KiB of dynamic LDS (n_pts > 1244 at 26 classes) need the opt-in.  attr_done is per PROCESS, not per
+    // Tables above 64 KiB of dynamic LDS (n_pts > 1244 at 26 classes) need the opt-in.  It is made once per PROCESS, not per
     // device: a second device used from the same process may never get the attribute (untested: needs two GPUs).
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&evaluate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);   // + 896 B static
-        attr_done = true;
-    }
+    if (!sncal::opt_in_lds<&evaluate_kernel>(159 * 1024)) return SNCAL_ERR_HIP;      // + 896 B static
     hipLaunchKernelGGL(evaluate_kernel, dim3(B), dim3(256), lds, sncal::as_stream(stream), d_cams, B, d_field, d_class_start, d_mirror,
                        n_cls, n_pts, d_gt, d_gt_cnt, d_gt_extra, max_gt, threshold, img_w, img_h, img_w / 2.0, img_h / 2.0, d_out, d_err, d_class_conf);
     SNCAL_CHECK_LAUNCH();

@@ -25,7 +25,7 @@
 // lane that owns output (pixel, channels 8g..8g+7) in the stage-1 accumulators is exactly the lane that must
 // hold the same 8 k-values in the stage-2 B fragment: the hand-off between the two GEMMs is a register
 // repack -- no LDS round trip, no shuffles.  One barrier per 32-channel slice orders the source-box DMA.
-#include "common.hpp"
+#include "persist.hpp"
 #include "head.hpp"
 #include "softmax_px.hpp"
 
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256, 5) void head_fused_kernel(const HeadParams p) 
     unsigned dma_voff[HEAD_MAX_DMA];
     int dma_src[HEAD_MAX_DMA], dma_lds[HEAD_MAX_DMA];
 #pragma unroll
-    for (int k = 0; k < HEAD_MAX_DMA; ++k) { dma_voff[k] = 0x80000000u; dma_src[k] = -1; dma_lds[k] = 0; }
+    for (int k = 0; k < HEAD_MAX_DMA; ++k) { dma_voff[k] = BUF_OOB; dma_src[k] = -1; dma_lds[k] = 0; }
     {
         int cursor = 0;     // running instruction index over all sources (block-uniform)
 #pragma unroll
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(256, 5) void head_fused_kernel(const HeadParams p) 
                 const int slot = i * 64 + lane, pi = slot >> 2, piece = slot & 3;
                 const int ly = (pi * ((65536 / bw[s]) + 1)) >> 16, lx = pi - ly * bw[s];     // pi < 64, bw <= 64: exact; bw[s] is
                                                                                              // block-uniform, its reciprocal is scalar work
-                const unsigned v = pi < npx ? (unsigned)((((by0[s] + ly) * p.Ws[s] + bx0[s] + lx) * p.HP) * 2 + piece * 16) : 0x80000000u;
+                const unsigned v = pi < npx ? (unsigned)((((by0[s] + ly) * p.Ws[s] + bx0[s] + lx) * p.HP) * 2 + piece * 16) : BUF_OOB;
 #pragma unroll
                 for (int kk = 0; kk < HEAD_MAX_DMA; ++kk)
                     if (kk == k) { dma_voff[kk] = v; dma_src[kk] = s; dma_lds[kk] = s * HEAD_SRC_LDS + i * 1024; }
@@ -89,9 +89,9 @@ __global__ __launch_bounds__(256, 5) void head_fused_kernel(const HeadParams p) 
     }
     // everything the slice loop consumes comes through LDS-DMA: an ordinary global load inside the loop would
     // make hipcc wait vmcnt(0) at its first use and drain the prefetch every iteration
-    const __amdgpu_buffer_rsrc_t rs_w0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w0), 0, p.NQ * 2 * KS1 * 1024, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w1), 0, p.NQ * M2 * 1024, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias0), 0, p.HP * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w0 = buf_rsrc(p.w0, p.NQ * 2 * KS1 * 1024);
+    const __amdgpu_buffer_rsrc_t rs_w1 = buf_rsrc(p.w1, p.NQ * M2 * 1024);
+    const __amdgpu_buffer_rsrc_t rs_b0 = buf_rsrc(p.bias0, p.HP * 4);
     auto issue_slice = [&](int q) {
         char* const base = smem;
 #pragma unroll
@@ -101,8 +101,7 @@ __global__ __launch_bounds__(256, 5) void head_fused_kernel(const HeadParams p) 
                 if (dma_src[k] == s) {
                     // one image of source s (ranges stay < 2 GB); building the descriptor is 4 scalar moves
                     const size_t img = (size_t)p.Hs[s] * p.Ws[s] * p.HP * 2;
-                    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                        const_cast<char*>(reinterpret_cast<const char*>(p.src[s])) + (size_t)n * img, 0, (int)img, 0x00020000);
+                    const __amdgpu_buffer_rsrc_t rs = buf_rsrc(reinterpret_cast<const char*>(p.src[s]) + (size_t)n * img, (int)img);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(base + dma_lds[k]), 16,
                                                              dma_voff[k], (unsigned)(q * 64), 0, 0);
                 }
@@ -118,7 +117,7 @@ __global__ __launch_bounds__(256, 5) void head_fused_kernel(const HeadParams p) 
                                                      (unsigned)((q * M2 + wave) * 1024), 0, 0);
         if (wave == 3)      // 32 shift values = 128 B; the other lanes read out of range
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b0, (lds_void*)(base + OFF_B0), 16,
-                                                     lane < 8 ? (unsigned)(lane * 16) : 0x80000000u, (unsigned)(q * 128), 0, 0);
+                                                     lane < 8 ? (unsigned)(lane * 16) : BUF_OOB, (unsigned)(q * 128), 0, 0);
     };
     issue_slice(0);
 

@@ -14,7 +14,7 @@
 // The hand-off between the two GEMMs is still a register repack: MFMA row r of a 32-row block carries channel
 // h32_row_channel(r) (head.hpp), so registers 8 h .. 8 h + 7 of a lane's accumulator are the channels 16 h + 8 (lane >> 5) + 0..7
 // of its pixel -- exactly the 8 k-values that lane must supply to stage 2's K = 16 step h.
-#include "common.hpp"
+#include "persist.hpp"
 #include "head.hpp"
 #include "softmax_px.hpp"
 
@@ -57,14 +57,14 @@ __global__ __launch_bounds__(256, 4) void head32_kernel(const HeadParams p) {
 
     // everything the slice loop consumes comes through LDS-DMA (an ordinary global load inside the loop would make hipcc wait
     // vmcnt(0) at its first use and drain the prefetch every iteration)
-    const __amdgpu_buffer_rsrc_t rs_w0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w0_32), 0, p.NQ * KS * 1024, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w1_32), 0, p.NQ * RB * 2 * 1024, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_b0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias0), 0, p.HP * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_w0 = buf_rsrc(p.w0_32, p.NQ * KS * 1024);
+    const __amdgpu_buffer_rsrc_t rs_w1 = buf_rsrc(p.w1_32, p.NQ * RB * 2 * 1024);
+    const __amdgpu_buffer_rsrc_t rs_b0 = buf_rsrc(p.bias0, p.HP * 4);
     __amdgpu_buffer_rsrc_t rs_src[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const size_t img = (size_t)p.Hs[s] * p.Ws[s] * p.HP * 2;      // one image of source s (ranges stay < 2 GB)
-        rs_src[s] = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.src[s])) + (size_t)n * img, 0, (int)img, 0x00020000);
+        rs_src[s] = buf_rsrc(reinterpret_cast<const char*>(p.src[s]) + (size_t)n * img, (int)img);
     }
     auto issue_slice = [&](int q) {
         char* const base = smem;
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256, 4) void head32_kernel(const HeadParams p) {
                                                      (unsigned)((q * RB * 2 + wave) * 1024), 0, 0);
         if (wave == 3)      // 32 shift values = 128 B; the other lanes read out of range
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b0, (lds_void*)(base + OFF_B0), 16,
-                                                     lane < 8 ? (unsigned)(lane * 16) : 0x80000000u, (unsigned)(q * 128), 0, 0);
+                                                     lane < 8 ? (unsigned)(lane * 16) : BUF_OOB, (unsigned)(q * 128), 0, 0);
     };
     issue_slice(0);
 
@@ -128,6 +128,7 @@ __global__ __launch_bounds__(256, 4) void head32_kernel(const HeadParams p) {
     const int tch = h32_row_channel(l31);         // hidden channel (within a slice) of this lane's row of a transposed box fragment
 
     // tuning aid: clocks of wave 0 in [0] wait + barrier, [1] nothing (no request ahead: the few clocks between two stamps; tools/head_trace.py keeps the slot), [2] stage 1, [3] gather, [4] ReLU + stage 2, [5] prologue
+    // (a clock of the kernel's own, not persist.hpp's PhaseClock: with that hipcc lays the slice loop out differently)
     unsigned long long tsum[6] = {0, 0, 0, 0, 0, 0}, tprev = 0;
     const bool tracing = p.trace != nullptr;
     auto lap = [&](int k) { if (tracing) { const unsigned long long now = __builtin_amdgcn_s_memtime(); tsum[k] += now - tprev; tprev = now; } };
@@ -207,14 +208,13 @@ bool launch_head32(const HeadParams& p, hipStream_t s) {
     const unsigned blocks = head_set_tiling(q, 32, 4);
     const int rb = (p.LC + 31) / 32;
     static const char* trace_file = getenv("SNCAL_HEAD_TRACE");
-    const size_t n_tr = (size_t)(blocks / 97 + 1) * 8;
-    q.trace = trace_file ? trace_arm(n_tr, s) : nullptr;
+    TraceScope trace(trace_file, (size_t)(blocks / 97 + 1) * 8, s);
+    q.trace = trace.words;
     const size_t lds = (size_t)(H32_SRC + (13 + rb * 2 + 1) * 1024);
     if (p.dec_row && p.dec_col && rb == 2)       // decode-fused form: 32 KB of LDS for the tile's log-probabilities
         SNCAL_LAUNCH((head32_kernel<2, 13, 1>), dim3(blocks), dim3(256), (size_t)32 * 1024, s, q);
     else if (rb == 2) SNCAL_LAUNCH((head32_kernel<2, 13, 0>), dim3(blocks), dim3(256), lds, s, q);
     else SNCAL_LAUNCH((head32_kernel<1, 13, 0>), dim3(blocks), dim3(256), lds, s, q);
-    trace_dump(q.trace, n_tr, trace_file, s);
     return true;
 }
 

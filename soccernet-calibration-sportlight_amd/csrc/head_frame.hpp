@@ -6,6 +6,7 @@
 // for bit, so this header deliberately does not include it.
 #pragma once
 #include "head.hpp"
+#include "persist.hpp"
 
 namespace sncal {
 
@@ -57,7 +58,7 @@ __device__ __forceinline__ HeadBoxTaps head_box32(const HeadParams& p, int s, in
     for (int j = 0; j < NPIECE; ++j) {
         const int slot = j * 64 + lane, pi = slot >> (ESZ == 2 ? 2 : 3), part = slot & (2 * ESZ - 1);      // 2 * ESZ lanes of 16 B per box pixel
         const int ly = pi >= bw ? 1 : 0, lx = pi - ly * bw;
-        dma_voff[j] = pi < npx ? (unsigned)((((by0 + ly) * p.Ws[s] + bx0 + lx) * p.HP) * ESZ + part * 16) : 0x80000000u;
+        dma_voff[j] = pi < npx ? (unsigned)((((by0 + ly) * p.Ws[s] + bx0 + lx) * p.HP) * ESZ + part * 16) : BUF_OOB;
     }
     const HeadTapAxis tx = head_tap_axis(p.sx[s], p.Ws[s], xc);
     const float ly1 = ty.l1, lx1 = tx.l1;

@@ -16,7 +16,7 @@
 // and column maxima of the tile) are head32.hip's.  Slice pipeline (round 4): the kernel's 232 VGPRs allow two workgroups per CU, so a
 // workgroup takes 78 KB of LDS: stage-1 weights double-buffered and requested a slice ahead, stage-2 weights requested at the top of their
 // slice (they land under stage 1 + gather), a wave's gather boxes requested as soon as the wave has read the current ones.
-#include "common.hpp"
+#include "persist.hpp"
 #include "head.hpp"
 #include "softmax_px.hpp"
 #include "x3.hpp"
@@ -37,17 +37,7 @@ constexpr int W0_BUF = 2 * KS * 1024 + 1024;        // [W0 hi 13 KB][W0 lo 13 KB
 constexpr int OFF_W0 = X_SRC, OFF_W1H = OFF_W0 + 2 * W0_BUF, OFF_W1L = OFF_W1H + RB * 2 * 1024, X_LDS = OFF_W1L + RB * 2 * 1024;      // 79872 B
 static_assert(2 * X_LDS <= 160 * 1024, "two workgroups per CU");
 
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-// One LDS-DMA piece as inline assembly (64 lanes x 16 bytes -> 1 KB at LDS byte address `lds_addr`): hipcc's wait-count pass would put
-// vmcnt(0) in front of every fragment read behind a DMA builtin, i.e. wait for the NEXT slice's pieces; every wait here is explicit.
-__device__ __forceinline__ void dma_piece(i32x4_t rsrc, unsigned lds_addr, unsigned voff, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" : : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory", "m0");
-}
-__device__ __forceinline__ i32x4_t raw_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    return i32x4_t{(int)(unsigned)a, (int)(unsigned)((a >> 32) & 0xffffu), (int)bytes, 0x00020000};
-}
-
+// The slices' pieces come by dma_piece (persist.hpp): every wait here is explicit.
 __device__ __forceinline__ void split8(const float (&v)[8], bf16x8& h, bf16x8& l) {
     x3u4 hu, lu;
     x3_split8(v, x3_lower(false), hu, lu);
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(256, 2) void headx3_kernel(const HeadParams p) {
                 dma_piece(rs_w0h, base + (wave + 4 * i) * 1024, (unsigned)(lane * 16), (unsigned)((q * KS + wave + 4 * i) * 1024));
                 dma_piece(rs_w0l, base + KS * 1024 + (wave + 4 * i) * 1024, (unsigned)(lane * 16), (unsigned)((q * KS + wave + 4 * i) * 1024));
             }
-        if (wave == 3) dma_piece(rs_b0, base + 2 * KS * 1024, lane < 8 ? (unsigned)(lane * 16) : 0x80000000u, (unsigned)(q * 128));
+        if (wave == 3) dma_piece(rs_b0, base + 2 * KS * 1024, lane < 8 ? (unsigned)(lane * 16) : BUF_OOB, (unsigned)(q * 128));
     };
     auto issue_w1 = [&](int q) {       // RB * 2 = 4 pieces each: one per wave
         dma_piece(rs_w1h, lds0 + OFF_W1H + wave * 1024, (unsigned)(lane * 16), (unsigned)((q * RB * 2 + wave) * 1024));
@@ -155,7 +145,7 @@ __global__ __launch_bounds__(256, 2) void headx3_kernel(const HeadParams p) {
                 for (int i = wave; i < npieces; i += 4) {
                     const unsigned o = (unsigned)((i * 64 + lane) * 16);
                     const unsigned row = (o >= rowb ? 1u : 0u) + (o >= 2u * rowb ? 1u : 0u) + (o >= 3u * rowb ? 1u : 0u);      // (<= 4 rows: launcher)
-                    const unsigned voff = o < total ? (unsigned)(((iy0 + (int)row) * p.Wf[f] + ix0) * p.Cf[f] * 4) + (o - row * rowb) : 0x80000000u;
+                    const unsigned voff = o < total ? (unsigned)(((iy0 + (int)row) * p.Wf[f] + ix0) * p.Cf[f] * 4) + (o - row * rowb) : BUF_OOB;
                     dma_piece(rs_f, lds_f + (unsigned)(i * 1024), voff, 0u);
                 }
                 f_iy0[f] = iy0; f_ix0[f] = ix0; f_bw[f] = bw; f_off[f] = off;
@@ -236,6 +226,7 @@ __global__ __launch_bounds__(256, 2) void headx3_kernel(const HeadParams p) {
 
     // tuning aid (SNCAL_HEAD_TRACE=<file>, tools/head_trace.py): clocks of wave 0 in [0] barriers + wait, [1] requests, [2] stage 1,
     // [3] gather, [4] ReLU + stage 2, [5] prologue
+    // (a clock of the kernel's own, not persist.hpp's PhaseClock: with that hipcc lays the slice loop out differently)
     unsigned long long tsum[6] = {0, 0, 0, 0, 0, 0}, tprev = 0;
     const bool tracing = p.trace != nullptr;
     auto lap = [&](int k) { if (tracing) { const unsigned long long now = __builtin_amdgcn_s_memtime(); tsum[k] += now - tprev; tprev = now; } };
@@ -330,12 +321,7 @@ bool headx3_applies(const HeadParams& p) {
 
 bool launch_headx3(const HeadParams& p, hipStream_t s) {
     if (!headx3_applies(p)) return false;
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&headx3_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&headx3_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, X_LDS);
-        attr_done = true;
-    }
+    opt_in_lds<&headx3_kernel<0>, &headx3_kernel<1>>(X_LDS);
     HeadParams q = p;
     // the folded branches' boxes through LDS (kernel prologue): at most four source rows per tile, both boxes within one stage-1 weight buffer
     static const int stage = env_int("SNCAL_HEAD_STAGE", 1);
@@ -351,11 +337,10 @@ bool launch_headx3(const HeadParams& p, hipStream_t s) {
     }
     const unsigned blocks = head_set_tiling(q, 32, 4);
     static const char* trace_file = getenv("SNCAL_HEAD_TRACE");
-    const size_t n_tr = (size_t)(blocks / 97 + 1) * 8;
-    q.trace = trace_file ? trace_arm(n_tr, s) : nullptr;
+    TraceScope trace(trace_file, (size_t)(blocks / 97 + 1) * 8, s);
+    q.trace = trace.words;
     if (p.dec_row && p.dec_col) SNCAL_LAUNCH((headx3_kernel<1>), dim3(blocks), dim3(256), (size_t)X_LDS, s, q);
     else SNCAL_LAUNCH((headx3_kernel<0>), dim3(blocks), dim3(256), (size_t)X_LDS, s, q);
-    trace_dump(q.trace, n_tr, trace_file, s);
     return true;
 }
 

@@ -149,14 +149,11 @@ int run_conv(const sncal_hrnet& net, const Launch& e, const Call& c) {
     conv_params(net, op, c.sb, c.ws, e.m[0], p);
     // tuning aid: SNCAL_CONV_TRACE=<layer name> dumps per-workgroup phase timestamps of that layer's last launch to conv_trace.bin
     static const char* trace_name = getenv("SNCAL_CONV_TRACE");
-    unsigned long long* d_trace = nullptr; size_t n_trace = 0;
-    if (trace_name && net.layers[op.conv].name == trace_name) {
-        n_trace = (size_t)8 * ((p.n_work + 7) / 8) * 16;
-        p.trace = d_trace = trace_arm(n_trace, c.stream);
-    }
+    const bool traced = trace_name && net.layers[op.conv].name == trace_name;
+    TraceScope trace(traced ? "conv_trace.bin" : nullptr, (size_t)8 * ((p.n_work + 7) / 8) * 16, c.stream);
+    p.trace = trace.words;
     e.m[0].v->launch(p, dim3(8 * p.per_xcd), e.m[0].lds, c.stream);
     SNCAL_CHECK_LAUNCH();
-    trace_dump(d_trace, n_trace, "conv_trace.bin", c.stream);
     return SNCAL_OK;
 }
 
@@ -169,9 +166,8 @@ int run_tt(sncal_hrnet& net, Launch& e, const Call& c) {
     memset(&tp, 0, sizeof(tp));
     tp.range = net.d_range;
     const bool fp8 = net.layers[ops[0].conv].fp8_on, x3 = net.layers[ops[0].conv].x3_on;
-    const sncal::LaunchEvents armed = sncal::launch_events();        // the profiling event pair belongs to the convolution launch,
-    sncal::launch_events() = sncal::LaunchEvents{};                  // not to the calibration / quantisation helpers in front of it
     for (int i = 0; i < n; ++i) {
+        LaunchEventsHold hold;       // the profiling event pair belongs to the convolution launch, not to the calibration / quantisation helpers in front of it
         const Tensor& ti = net.tensors[ops[i].in];
         if (net.calibrating && ti.twin >= 0) {        // C5 calibration: max |x| of every candidate input tensor
             const int rc = launch_absmax_bf16(c.ws + ti.offset, (size_t)sb * ti.H * ti.W * ti.C, net.d_amax + ops[i].in, stream);
@@ -187,7 +183,6 @@ int run_tt(sncal_hrnet& net, Launch& e, const Call& c) {
         }
         tt_member(net, ops[i], sb, c.ws, tp.m[i]);
     }
-    sncal::launch_events() = armed;
     if (!e.plan.n_wgs) {       // static per layout: uploaded by the first launch
         const int rc = tt_build_plan(net, tp.m, n, e.plan, stream);
         if (rc) return rc;
@@ -200,13 +195,12 @@ int run_tt(sncal_hrnet& net, Launch& e, const Call& c) {
     static const bool trace_cfg64 = getenv("SNCAL_TT_TRACE_CFG64") && atoi(getenv("SNCAL_TT_TRACE_CFG64")) != 0;
     static const int trace_nth = env_int("SNCAL_TT_TRACE_NTH", -1);      // only the n-th such launch of the process
     static int trace_seen = 0;
-    unsigned long long* d_trace = nullptr;
-    const size_t n_trace = (size_t)e.plan.n_wgs * 2 * 256;
-    if (trace_file && (trace_cfg64 ? e.plan.cfg == 1 : n == 3) && (trace_nth < 0 || trace_seen++ == trace_nth)) tp.trace = d_trace = trace_arm(n_trace, stream);
+    const bool traced = trace_file && (trace_cfg64 ? e.plan.cfg == 1 : n == 3) && (trace_nth < 0 || trace_seen++ == trace_nth);
+    TraceScope trace(traced ? trace_file : nullptr, (size_t)e.plan.n_wgs * 2 * 256, stream);
+    tp.trace = trace.words;
     { static const int abl = env_int("SNCAL_TT_ABLATE", 0); tp.ablate = abl; }
     launch_conv_tt(tp, e.plan.n_wgs, fp8 ? 1 : x3 ? 2 : 0, stream, e.plan.cfg);
     SNCAL_CHECK_LAUNCH();
-    trace_dump(d_trace, n_trace, trace_file, stream);
     return SNCAL_OK;
 }
 
@@ -294,11 +288,9 @@ int run_bblockx3(const sncal_hrnet& net, const Launch& e, const Call& c) {
     const Tensor& ti = net.tensors[a.in];
     const Tensor& to = net.tensors[b.out];
     if (e.split_in) {         // (a helper in front of the launch: not what the profiling events time)
-        const sncal::LaunchEvents armed = sncal::launch_events();
-        sncal::launch_events() = sncal::LaunchEvents{};
+        LaunchEventsHold hold;
         const int rc = launch_split_f32(c.ws + ti.offset, c.ws + net.tensors[ti.twin].offset, (size_t)c.sb * ti.H * ti.W * ti.C, c.stream, net.d_range);
         if (rc) return rc;
-        sncal::launch_events() = armed;
     }
     BBlockX3Params bp;
     memset(&bp, 0, sizeof(bp));
@@ -310,7 +302,7 @@ int run_bblockx3(const sncal_hrnet& net, const Launch& e, const Call& c) {
     bp.w2 = net.layers[b.conv].d_w_bbx; bp.b2 = net.layers[b.conv].d_bias;
     bp.N = c.sb; bp.H = ti.H; bp.W = ti.W; bp.out_cstride = to.C; bp.out_coff = b.out_coff;
     bp.ticket = net.d_tickets + TICKET_BBX3;
-    return launch_bblockx3(bp, c.stream);
+    return launch_bblockx3(bp, net.n_cus, c.stream);
 }
 
 int run_bblock48(const sncal_hrnet& net, const Launch& e, const Call& c) {
@@ -323,7 +315,7 @@ int run_bblock48(const sncal_hrnet& net, const Launch& e, const Call& c) {
     bp.w2 = net.layers[b.conv].d_w; bp.b2 = net.layers[b.conv].d_bias;
     bp.N = c.sb; bp.H = ti.H; bp.W = ti.W; bp.tiles_x = bp.tiles_y = 0; bp.trace = nullptr;
     bp.ticket = net.d_tickets + TICKET_BB48;
-    return launch_bblock48(bp, c.stream);
+    return launch_bblock48(bp, net.n_cus, c.stream);
 }
 
 int run_upadd(const sncal_hrnet& net, const Launch& e, const Call& c) {

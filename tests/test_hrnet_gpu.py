@@ -352,3 +352,32 @@ def test_fused_block_in_several_launches_gives_the_same_bytes(sncal, cuda, monke
     monkeypatch.setenv('SNCAL_BBX_MAX_BYTES', str(3 * 68 * 120 * 192 + 1000))      # (the 48-channel branch of a 270x480 input: 68 x 120 x 192 B per frame)
     heat, kp = net.forward(x, want_heat=True, decode_size=(540, 960))
     assert torch.equal(heat, heat0) and torch.equal(kp, kp0)
+
+
+@pytest.mark.parametrize('dtype', ['bf16', 'fp16x3'])
+def test_persistent_kernels_rearm_between_forwards(sncal, cuda, dtype):
+    """The persistent kernels draw their work from ticket words that the last workgroup (wave, for the layer1 seam) to leave zeroes for
+    the next launch on the stream (ticket_leave, persist.hpp; conv_tt's per-XCD form).  A re-arm that fails shows only in the SECOND
+    launch, which then starts from used tickets and skips or repeats tiles: three forwards of one batch on one handle and stream must
+    give the same bytes, and so must a fourth with profiling on, whose rows show that the fused BasicBlock, the two-team convolution
+    and (split engine) the seam kernel did run, not a fallback path.  Three frames of 64x96: the 48-channel branch is 16x24, 2x2 tiles
+    of 16x14 with partial columns per frame in the bf16 kernel, and in the split engine's stack of 3 x 17 rows tiles that straddle
+    frames."""
+    cfg = hr.load_config('hrnet_w48')
+    net = sncal.HRNetHeatmap('hrnet_w48', dtype=dtype, device=cuda)
+    net.load_state_dict(hr.seeded_state_dict(cfg, 41, 4.0))
+    x = hr.seeded_input(3, 64, 96, 42).to(cuda)
+    outs = []
+    for rep in range(4):
+        if rep == 3:
+            net.set_profiling(True)
+        heat, kp = net.forward(x, want_heat=True, decode_size=(540, 960))
+        outs.append((heat.clone(), kp.clone()))
+    for rep in (1, 2, 3):
+        assert torch.equal(outs[rep][0], outs[0][0]) and torch.equal(outs[rep][1], outs[0][1]), rep
+    assert float(outs[0][0].abs().max()) > 0.0
+    kernels = {p['kernel'] for p in net.get_profile()}
+    assert ('bblock48_fused' if dtype == 'bf16' else 'bblockx3_fused') in kernels, kernels
+    assert any(k.startswith('conv_tt<' + dtype + ',') for k in kernels), kernels
+    if dtype != 'bf16':
+        assert 'bneck_seam_x3' in kernels, kernels
