@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <vector>
+#include "pack.hpp"
+#include "x3.hpp"        // x3_split_host
 
 namespace sncal {
 
@@ -49,13 +51,13 @@ constexpr BbxUnit bbx_unit(int s, int which) {
     return which == 0 ? BbxUnit{2, 2, 2} : BbxUnit{0, 0, -1};
 }
 
-// A fragments of v_mfma_f32_16x16x32_{bf16,f16} for one convolution (w: [48][48][3][3] folded weights): per step and unit three 1 KB
-// fragments (16 output channels each); lane l holds output channel 16 cb + (l & 15) and K octet l >> 4: octets 0, 1 = hi parts of
-// input channels 16 g + 0..7 / 8..15 of the tap, octets 2, 3 = their lo parts.  (The main-term fragment [w_hi(u0) | w_hi(u1)] is read
-// out of the two units' fragments with a per-lane address, it is not stored.)  split(w, &hi, &lo) yields the two 16-bit codes.
-template <class Split>
-inline void bbx3_pack_weights(const float* w, const float* scale, Split split, std::vector<uint16_t>& out) {
-    out.assign((size_t)BBX_W_BYTES / 2, 0);
+// A fragments of v_mfma_f32_16x16x32_{bf16,f16} for one convolution (W: the folded weights of a 48 -> 48 3x3 layer): per step and unit three
+// 1 KB fragments (16 output channels each); lane l holds output channel 16 cb + (l & 15) and K octet l >> 4: octets 0, 1 = hi parts of
+// input channels 16 g + 0..7 / 8..15 of the tap, octets 2, 3 = their lo parts (x3.hpp).  (The main-term fragment [w_hi(u0) | w_hi(u1)] is
+// read out of the two units' fragments with a per-lane address, it is not stored.)
+inline size_t bbx3_packed_bytes() { return BBX_W_BYTES; }
+inline void bbx3_pack_weights(Folded W, std::vector<uint16_t>& out) {
+    out.assign(bbx3_packed_bytes() / 2, 0);
     for (int s = 0; s < BBX_STEPS; ++s)
         for (int which = 0; which < 2; ++which) {
             const BbxUnit u = bbx_unit(s, which);
@@ -65,10 +67,8 @@ inline void bbx3_pack_weights(const float* w, const float* scale, Split split, s
                     const int co = cb * 16 + (lane & 15), o = lane >> 4;
                     uint16_t* dst = out.data() + ((size_t)s * BBX_STEP_BYTES + (size_t)which * 3072 + (size_t)cb * 1024 + (size_t)lane * 16) / 2;
                     for (int e = 0; e < 8; ++e) {
-                        const int ci = u.g * 16 + (o & 1) * 8 + e;
-                        const float v = w[(((size_t)co * 48 + ci) * 3 + u.dy) * 3 + u.dx] * scale[co];
                         uint16_t hi, lo;
-                        split(v, &hi, &lo);
+                        x3_split_host(W.tap<3>(co, u.g * 16 + (o & 1) * 8 + e, u.dy * 3 + u.dx), &hi, &lo);
                         dst[e] = o < 2 ? hi : lo;
                     }
                 }

@@ -4,7 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <vector>
-#include "head.hpp"      // h32_row_channel
+#include "pack.hpp"      // h32_row_channel
+#include "x3.hpp"        // x3_split_host
 
 namespace sncal {
 
@@ -31,24 +32,24 @@ struct BneckPairParams {
 
 int launch_bneck_pair_x3(const BneckPairParams& p, int n_cus, hipStream_t s);
 
-// A fragments of v_mfma_f32_32x32x16_{bf16,f16} for a 1x1 layer (w: [cout][cin] folded weights): [cout / 32][cin / 16][hi | lo][64 lanes][8];
-// lane l, row l & 31 carries output channel 32 mb + h32_row_channel(l & 31) (head.hpp: a lane's accumulator registers 8 h .. 8 h + 7 are
+// A fragments of v_mfma_f32_32x32x16_{bf16,f16} for a 1x1 layer (W: its folded weights): [cout / 32][cin / 16][hi | lo][64 lanes][8];
+// lane l, row l & 31 carries output channel 32 mb + h32_row_channel(l & 31) (pack.hpp: a lane's accumulator registers 8 h .. 8 h + 7 are
 // then the eight consecutive channels 32 mb + 16 h + 8 (l >> 5) + 0..7 -- at once the layout of a 32-byte store and of the next
-// layer's B fragment), K octet l >> 5 = input channels 16 ks + 8 (l >> 5) + 0..7.  split(w, &hi, &lo) yields the two 16-bit codes.
-template <class Split>
-inline void bnp_pack_weights(const float* w, const float* scale, int cout, int cin, Split split, std::vector<uint16_t>& out) {
-    const int MB = cout / 32, KS = cin / 16;
-    out.assign((size_t)MB * KS * 2 * 64 * 8, 0);
+// layer's B fragment), K octet l >> 5 = input channels 16 ks + 8 (l >> 5) + 0..7; hi / lo: the two 16-bit codes of x3.hpp.
+inline bool bnp_shape_ok(int k, int stride, int cin, int cout) {
+    return k == 1 && stride == 1 && ((cin == BNP_MID && cout == BNP_WIDE) || (cin == BNP_WIDE && cout == BNP_MID));
+}
+inline size_t bnp_packed_bytes(int cin, int cout) { return (size_t)(cout / 32) * (cin / 16) * 2 * 1024; }
+inline void bnp_pack_weights(Folded W, std::vector<uint16_t>& out) {
+    const int MB = W.cout / 32, KS = W.cin / 16;
+    out.assign(bnp_packed_bytes(W.cin, W.cout) / 2, 0);
     for (int mb = 0; mb < MB; ++mb)
         for (int ks = 0; ks < KS; ++ks)
             for (int lane = 0; lane < 64; ++lane) {
                 const int co = 32 * mb + h32_row_channel(lane & 31);
                 uint16_t* hi = out.data() + ((((size_t)mb * KS + ks) * 2 + 0) * 64 + lane) * 8;
                 uint16_t* lo = out.data() + ((((size_t)mb * KS + ks) * 2 + 1) * 64 + lane) * 8;
-                for (int e = 0; e < 8; ++e) {
-                    const int ci = 16 * ks + 8 * (lane >> 5) + e;
-                    split(w[(size_t)co * cin + ci] * scale[co], &hi[e], &lo[e]);
-                }
+                for (int e = 0; e < 8; ++e) x3_split_host(W.tap<1>(co, 16 * ks + 8 * (lane >> 5) + e), &hi[e], &lo[e]);
             }
 }
 

@@ -49,6 +49,8 @@
 #include "x3.hpp"
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <vector>
+#include "pack.hpp"
 #include "persist.hpp"
 
 namespace sncal {
@@ -161,6 +163,52 @@ inline size_t conv_stage_bytes(int KS, int S, int NI, int MI, int G, int twf) {
     const int hh = (th - 1) * S + KS, hw = (16 * twf - 1) * S + KS;
     const size_t halo = ((size_t)hh * hw * halo_pitch(G, S) + 1023) / 1024 * 1024;   // DMA writes whole KBs
     return (size_t)conv_nks(KS, G) * MI * 1024 + halo;
+}
+
+// ---- the packed-weight format of the kernels below (host; pack.hpp) -------------------------------------------------------------
+// [nblk][chunk][k-step][mi][lane 64] x 16 B: lane l of fragment mi holds output channel (nb * MI + mi) * 16 + (l & 15) and k-group
+// 4 s + (l >> 4) of the chunk, i.e. tap kg / G and the GE input channels (c * G + kg % G) * GE + 0..GE-1 (zeros beyond the taps, Cout and
+// Cin).  Three element forms of the 16 bytes: 8 bf16, 4 fp32, or [4 hi | 4 lo] of the split engine (struct x3_t above).
+enum ConvForm { CONV_PACK_BF16, CONV_PACK_F32, CONV_PACK_X3 };
+struct ConvPackShape {
+    int cin, cin_phys, cout, ks, ge, mi, g;      // cin_phys: channels of the input TENSOR (>= cin); ge: elements per k-group
+    int nblk() const { return ((cout + 15) / 16 + mi - 1) / mi; }
+    int chunks() const { return (cin_phys + g * ge - 1) / (g * ge); }
+};
+inline size_t conv_packed_bytes(const ConvPackShape& s) { return (size_t)s.nblk() * s.chunks() * conv_nks(s.ks, s.g) * s.mi * 1024; }
+
+// ... and the bias vector that goes with it: the folded-BN shift, padded to nblk * mi * 16
+inline void conv_pack_weights(Folded W, const float* shift, ConvPackShape s, ConvForm form, std::vector<uint8_t>& out,
+                              std::vector<float>& bias) {
+    const int KS = s.ks, G = s.g, MI = s.mi, nblk = s.nblk(), chunks = s.chunks(), nks = conv_nks(KS, G);
+    out.assign(conv_packed_bytes(s), 0);
+    uint8_t* const base = out.data();
+    for (int nb = 0; nb < nblk; ++nb)
+        for (int c = 0; c < chunks; ++c)
+            for (int st = 0; st < nks; ++st)
+                for (int mi = 0; mi < MI; ++mi)
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int m = lane & 15, g = lane >> 4;
+                        const int kg = 4 * st + g;
+                        const int tap = kg / G, cgi = kg % G;
+                        const int co = (nb * MI + mi) * 16 + m;
+                        uint8_t* dst = base + ((((size_t)(nb * chunks + c) * nks + st) * MI + mi) * 64 + lane) * 16;
+                        if (tap >= KS * KS || co >= s.cout) continue;
+                        for (int e = 0; e < s.ge; ++e) {
+                            const int ci = (c * G + cgi) * s.ge + e;
+                            if (ci >= s.cin) continue;
+                            const float v = W(co, ci, tap / KS, tap % KS);
+                            if (form == CONV_PACK_BF16) { const uint16_t b = f2bf(v); memcpy(dst + e * 2, &b, 2); }
+                            else if (form == CONV_PACK_X3) {      // hi = rne16(w), lo = rne16(w - hi) (x3.hpp)
+                                uint16_t h, l;
+                                x3_split_host(v, &h, &l);
+                                memcpy(dst + e * 2, &h, 2); memcpy(dst + 8 + e * 2, &l, 2);
+                            }
+                            else memcpy(dst + e * 4, &v, 4);
+                        }
+                    }
+    bias.assign((size_t)nblk * MI * 16, 0.f);
+    for (int co = 0; co < s.cout; ++co) bias[co] = shift[co];
 }
 
 

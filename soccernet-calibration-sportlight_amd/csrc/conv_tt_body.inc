@@ -19,9 +19,16 @@ static_assert(wp_first(4) == NKS * MI && 32 * EPI_PITCH * 4 <= (NKS * MI / 4) * 
               "a wave's epilogue staging must fit its own block of the weight region; two teams fit the CU's LDS");
 
 // bf16x3: channel (inside its 32-channel block) of the first of the 4 accumulator registers of quad q in lane half hi.  The natural MFMA
-// order is 8 q + 4 hi; the x3 weights are packed with rows permuted (tt_x3_row_channel, conv_tt.hpp) so that it is 16 (q / 2) + 8 hi +
+// order is 8 q + 4 hi; the x3 weights are packed with rows permuted (ttx3_pack_weights, conv_tt.hpp) so that it is 16 (q / 2) + 8 hi +
 // 4 (q % 2): registers 8 p .. 8 p + 7 of a lane are then channels 16 p + 8 hi + 0..7 -- one 16-byte half of a split-twin group.
 __device__ __host__ constexpr int x3_quad_channel(int q, int hi) { return 16 * (q >> 1) + 8 * hi + 4 * (q & 1); }
+static_assert([] {
+    for (int q = 0; q < 4; ++q)
+        for (int hi = 0; hi < 2; ++hi)
+            for (int j = 0; j < 4; ++j)
+                if (h32_row_channel(8 * q + 4 * hi + j) != x3_quad_channel(q, hi) + j) return false;
+    return true;
+}(), "the epilogue's channel of an accumulator register is the packer's channel of that MFMA row (h32_row_channel, pack.hpp)");
 
 // FP8 = false: bf16 operands, v_mfma_f32_32x32x16_bf16, stages of 32 input channels.
 // FP8 = true (BASELINE config C5): OCP e4m3 operands -- the input is the e4m3 twin of the activation tensor (per-tensor scale),

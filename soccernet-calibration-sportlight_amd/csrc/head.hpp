@@ -1,6 +1,10 @@
 // Parameters / launchers of the fused head kernels (head.hip, head32.hip, headx3.hip; their shared device pieces: head_frame.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <vector>
+#include "pack.hpp"      // h32_row_channel: the row order of head32.hip's and headx3.hip's 32-row blocks
+#include "x3.hpp"        // x3_split_host
 
 namespace sncal {
 
@@ -18,8 +22,8 @@ struct HeadParams {
     const void* w0;                // stage-1 A fragments [NQ][2][ks1][64 lanes] x 16 B (rows permuted, BN scale folded)
     const float* bias0;            // [HP] folded BN shift of last_layer.0 (zero on the padding)
     const void* w1;                // stage-2 A fragments [NQ][M2][64 lanes] x 16 B
-    const void* w0_32;             // head32.hip: stage-1 A fragments of v_mfma_f32_32x32x16 [NQ][ks16][64 lanes] x 16 B (rows in tt_row_channel order), or null
-    const void* w1_32;             // head32.hip: stage-2 A fragments [NQ][ceil(LC / 32)][2][64 lanes] x 16 B (class rows in tt_row_channel order)
+    const void* w0_32;             // head32.hip: stage-1 A fragments of v_mfma_f32_32x32x16 [NQ][ks16][64 lanes] x 16 B (rows in h32_row_channel order), or null
+    const void* w1_32;             // head32.hip: stage-2 A fragments [NQ][ceil(LC / 32)][2][64 lanes] x 16 B (class rows in h32_row_channel order)
     const void* w0_32_lo;          // headx3.hip (fp16x3 engine): the lo parts of the split weights, same layouts (w0_32 / w1_32 hold the hi parts)
     const void* w1_32_lo;
     int ks16;                      // (Cd + sum Cf) / 16 when that is exact, else 0
@@ -43,11 +47,6 @@ struct HeadParams {
     unsigned long long* trace;     // head32.hip / headx3.hip tuning aid (SNCAL_HEAD_TRACE=<file>): 8 phase sums per workgroup, or null
 };
 
-// head32.hip: row order of a 32-row block of A fragments.  The D registers of v_mfma_f32_32x32x16 give lane l rows 8 q + 4 (l >> 5) + j
-// (q, j = 0..3) of column l & 31; MFMA row r carries channel h32_row_channel(r) of the block, so that the registers 8 h .. 8 h + 7 of a
-// lane are the eight consecutive channels 16 h + 8 (l >> 5) + 0..7.
-constexpr int h32_row_channel(int r) { return 16 * (r >> 4) + 8 * ((r >> 2) & 1) + 4 * ((r >> 3) & 1) + (r & 3); }
-
 int launch_head_fused(const HeadParams& p, int m2, hipStream_t s);
 bool launch_head32(const HeadParams& p, hipStream_t s);      // head32.hip; false = does not apply, nothing launched
 bool head32_applies(const HeadParams& p);                  // the same test without launching
@@ -69,5 +68,98 @@ inline unsigned head_set_tiling(HeadParams& q, int tile_w, int tile_h) {
 // 32-wide kernels: the worst-case box of a gather source at horizontal scale sx for one output row x 32 columns (2 rows x
 // (int)(31 sx) + 3 columns) fits the 16 pixels of one DMA piece / K step
 inline bool head_boxes_fit(float sx) { return 2 * ((int)(sx * 31) + 3) <= 16; }
+
+// ---- the packed-weight formats of the fused heads (host; pack.hpp) ------------------------------------------------------------------
+// W0 = last_layer.0 (1x1, BN scale folded), W1 = last_layer.3.  Stage 1 multiplies the first K1 concat columns from column coff of W0 on
+// (the direct tensor's Cd channels + the folded branches); HP = padded hidden width (NQ = HP / 32 slices), M2 = 16-class fragments.
+struct HeadPackShape {
+    int HP, M2, Cd, coff, K1, KS1;
+    int NQ() const { return HP / 32; }
+    int KS16() const { return K1 / 16; }                 // 32x32x16 packing: k-steps of stage 1 (exists when K1 % 16 == 0)
+    int RB() const { return (M2 * 16 + 31) / 32; }       // ... 32-row class blocks of stage 2
+};
+inline bool head_shape_ok(const HeadPackShape& s) { return s.Cd <= 64 && s.M2 <= 4 && s.K1 <= s.KS1 * 32; }      // else no fused head
+
+// head.hip (bf16): the 16x16x32 fragments.  w0 [NQ][2][KS1][64 lanes] x 8 bf16: lane l of fragment f holds hidden channel
+// q * 32 + (m >> 2) * 8 + f * 4 + (m & 3), m = l & 15 (row permutation, see head.hip), k = ks * 32 + (l >> 4) * 8 + 0..7 (zeros from K1
+// on); w1 [NQ][M2][64 lanes] x 8: class mi * 16 + (l & 15), hidden channel q * 32 + (l >> 4) * 8 + 0..7.
+inline size_t head_w0_packed_bytes(const HeadPackShape& s) { return (size_t)s.NQ() * 2 * s.KS1 * 1024; }
+inline size_t head_w1_packed_bytes(const HeadPackShape& s) { return (size_t)s.NQ() * s.M2 * 1024; }
+inline void head_pack_weights(Folded W0, Folded W1, HeadPackShape s, std::vector<uint16_t>& w0, std::vector<uint16_t>& w1) {
+    const int NQ = s.NQ(), KS1 = s.KS1, M2 = s.M2;
+    w0.assign(head_w0_packed_bytes(s) / 2, 0);
+    w1.assign(head_w1_packed_bytes(s) / 2, 0);
+    for (int q = 0; q < NQ; ++q)
+        for (int f = 0; f < 2; ++f)
+            for (int ks = 0; ks < KS1; ++ks)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int m = lane & 15, gk = lane >> 4;
+                    const int ch = q * 32 + (m >> 2) * 8 + f * 4 + (m & 3);
+                    if (ch >= W0.cout) continue;
+                    uint16_t* dst = w0.data() + ((((size_t)(q * 2 + f) * KS1 + ks) * 64) + lane) * 8;
+                    for (int e = 0; e < 8; ++e) {
+                        const int k = ks * 32 + gk * 8 + e;
+                        if (k < s.K1) dst[e] = f2bf(W0.tap<1>(ch, s.coff + k));
+                    }
+                }
+    for (int q = 0; q < NQ; ++q)
+        for (int mi = 0; mi < M2; ++mi)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int cls = mi * 16 + (lane & 15), gk = lane >> 4;
+                if (cls >= W1.cout) continue;
+                uint16_t* dst = w1.data() + (((size_t)(q * M2 + mi) * 64) + lane) * 8;
+                for (int e = 0; e < 8; ++e) {
+                    const int k = q * 32 + gk * 8 + e;
+                    if (k < W1.cin) dst[e] = f2bf(W1.tap<1>(cls, k));
+                }
+            }
+}
+
+// head32.hip (bf16) / headx3.hip (split engines): the 32x32x16 fragments, K1 a multiple of 16.  w0 [NQ][KS16][64 lanes] x 8: lane l holds
+// row h32_row_channel(l & 31) of the 32-row block, k = 16 ks + 8 (l >> 5) + 0..7; w1 [NQ][RB][2][64 lanes] x 8: class rb * 32 + row,
+// hidden channel q * 32 + h * 16 + 8 (l >> 5) + 0..7.  split = false: bf16 in w0 / w1, the lo vectors stay empty; split = true: every
+// weight as hi + lo (x3.hpp), the lo parts in w0_lo / w1_lo in the same layout.
+inline size_t head32_w0_packed_bytes(const HeadPackShape& s) { return (size_t)s.NQ() * s.KS16() * 1024; }
+inline size_t head32_w1_packed_bytes(const HeadPackShape& s) { return (size_t)s.NQ() * s.RB() * 2 * 1024; }
+inline void head32_pack_weights(Folded W0, Folded W1, HeadPackShape s, bool split, std::vector<uint16_t>& w0,
+                                std::vector<uint16_t>& w1, std::vector<uint16_t>& w0_lo, std::vector<uint16_t>& w1_lo) {
+    const int NQ = s.NQ(), KS16 = s.KS16(), RB = s.RB();
+    w0.assign(head32_w0_packed_bytes(s) / 2, 0);
+    w1.assign(head32_w1_packed_bytes(s) / 2, 0);
+    w0_lo.assign(split ? w0.size() : 0, 0);
+    w1_lo.assign(split ? w1.size() : 0, 0);
+    auto put = [&](std::vector<uint16_t>& hi, std::vector<uint16_t>& lo, size_t o, float w) {
+        if (split) x3_split_host(w, &hi[o], &lo[o]); else hi[o] = f2bf(w);
+    };
+    for (int q = 0; q < NQ; ++q)
+        for (int lane = 0; lane < 64; ++lane) {
+            const int row = h32_row_channel(lane & 31), kb = (lane >> 5) * 8;
+            const int ch = q * 32 + row;
+            for (int ks = 0; ks < KS16 && ch < W0.cout; ++ks) {
+                const size_t o = (((size_t)q * KS16 + ks) * 64 + lane) * 8;
+                for (int e = 0; e < 8; ++e) put(w0, w0_lo, o + e, W0.tap<1>(ch, s.coff + ks * 16 + kb + e));
+            }
+            for (int rb = 0; rb < RB; ++rb)
+                for (int h = 0; h < 2; ++h) {
+                    const int cls = rb * 32 + row;
+                    if (cls >= W1.cout) continue;
+                    const size_t o = ((((size_t)q * RB + rb) * 2 + h) * 64 + lane) * 8;
+                    for (int e = 0; e < 8; ++e) {
+                        const int k = q * 32 + h * 16 + kb + e;
+                        if (k < W1.cin) put(w1, w1_lo, o + e, W1.tap<1>(cls, k));
+                    }
+                }
+        }
+}
+
+// the two bias vectors of every form: b0 [HP] folded-BN shift of last_layer.0, b1 the bias of last_layer.3 -- at least 64 slots: head32's
+// decode epilogue reads 64 whatever the class count
+inline void head_pack_bias(const float* shift0, int cout0, const float* shift1, int cout1, HeadPackShape s, std::vector<float>& b0,
+                           std::vector<float>& b1) {
+    b0.assign(s.HP, 0.f);
+    b1.assign((size_t)std::max(s.M2 * 16, 64), 0.f);
+    for (int co = 0; co < cout0; ++co) b0[co] = shift0[co];
+    for (int c = 0; c < cout1; ++c) b1[c] = shift1[c];
+}
 
 }  // namespace sncal

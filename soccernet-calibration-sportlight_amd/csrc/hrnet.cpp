@@ -31,7 +31,7 @@ void conv_params(const sncal_hrnet& net, const Op& op, int sb, char* ws, const M
     p.out = m.f32 ? ws + to.offset : nullptr;
     p.out_twin = m.twin ? ws + net.tensors[to.twin].offset : nullptr;
     p.res = op.res >= 0 ? ws + net.tensors[op.res].offset : nullptr;
-    p.w = L.d_w; p.bias = L.d_bias;
+    p.w = L.packed[PK_GENERIC].p; p.w_bytes = (unsigned)L.packed[PK_GENERIC].bytes; p.bias = L.d_bias;
     p.N = sb; p.Hin = ti.H; p.Win = ti.W; p.Cin = ti.C;
     p.Hout = to.H; p.Wout = to.W; p.cout_frags = L.cout_frags; p.cout = L.cout;
     p.out_cstride = to.C; p.out_coff = op.out_coff;
@@ -43,7 +43,6 @@ void conv_params(const sncal_hrnet& net, const Op& op, int sb, char* ws, const M
     p.tiles_x = m.tiles_x; p.tiles_y = m.tiles_y;
     p.epi_lds = m.epi_lds ? 1 : 0;
     { static const int abl = env_int("SNCAL_ABLATE", 0); p.ablate = abl; }
-    p.w_bytes = (unsigned)((size_t)L.nblk * L.chunks * conv_nks(L.k, L.g) * L.mi * 1024);
     p.nblk = L.nblk;
     p.n_work = (unsigned)(p.tiles_x * p.tiles_y * sb * L.nblk);
     p.per_xcd = (p.n_work + 7) / 8;
@@ -59,27 +58,24 @@ void tt_member(const sncal_hrnet& net, const Op& op, int sb, char* ws, TTMember&
     memset(&m, 0, sizeof(m));
     m.in = ws + ti.offset; m.out = out ? ws + to.offset : nullptr; m.res = op.res >= 0 ? ws + net.tensors[op.res].offset : nullptr;
     m.out8 = twin ? ws + net.tensors[to.twin].offset : nullptr;
-    m.w = L.d_w_tt; m.bias = L.d_bias;
-    m.N = sb; m.H = ti.H; m.W = ti.W; m.Cin = L.cin; m.chunks = L.cin / TT_CIN;
+    m.w = L.packed[PK_TT].p; m.w_bytes = (unsigned)L.packed[PK_TT].bytes; m.bias = L.d_bias;
+    m.N = sb; m.H = ti.H; m.W = ti.W; m.Cin = L.cin; m.chunks = tt_chunks(L.cin);
     m.cout = L.cout; m.out_cstride = to.C; m.out_coff = op.out_coff; m.relu = op.relu ? 1 : 0;
-    m.w_bytes = (unsigned)((size_t)(L.cout / TT_COUT) * m.chunks * 9 * 6 * 1024);
     m.in_bytes = (unsigned)((size_t)sb * ti.H * ti.W * ti.C * 2);
     m.hp1_magic = 0xFFFFFFFFu / (unsigned)(ti.H + 1) + 1u;
     if (L.x3_on) {           // bf16x3: split twin in (a bf16 tensor of 2 C pseudo-channels), 16-channel stages, hi / lo weights, fp32 out
         m.in = ws + net.tensors[ti.twin].offset;
         m.in_bytes = (unsigned)((size_t)sb * ti.H * ti.W * ti.C * 4);
         m.Cin = 2 * L.cin;
-        m.chunks = L.cin / 16;
-        m.w = L.d_w_x3;
-        m.w_bytes = (unsigned)((size_t)((L.cout + L.x3_blk - 1) / L.x3_blk) * m.chunks * 9 * 2 * (L.x3_blk / 32) * 1024);
+        m.chunks = ttx3_chunks(L.cin);
+        m.w = L.packed[PK_TT_X3].p; m.w_bytes = (unsigned)L.packed[PK_TT_X3].bytes;
         if (op.res_twin) { m.res = ws + net.tensors[net.tensors[op.res].twin].offset; m.res_split = 1; }
     }
     if (L.fp8_on) {          // C5: e4m3 twin in, 64-channel stages, e4m3 weights
         m.in = ws + net.tensors[ti.twin].offset;
         m.in_bytes = (unsigned)((size_t)sb * ti.H * ti.W * ti.C);
-        m.chunks = (L.cin + 63) / 64;
-        m.w = L.d_w8;
-        m.w_bytes = (unsigned)((size_t)(L.cout / TT_COUT) * m.chunks * 9 * 6 * 1024);
+        m.chunks = tt8_chunks(L.cin);
+        m.w = L.packed[PK_TT_FP8].p; m.w_bytes = (unsigned)L.packed[PK_TT_FP8].bytes;
         m.oscale = L.d_oscale;
         m.out8_inv_scale = twin && to.scale > 0.f ? 1.0f / to.scale : 1.0f;
     }
@@ -268,14 +264,14 @@ int run_bneck(const sncal_hrnet& net, const Launch& e, const Call& c) {
     bp.range = net.d_range;
     bp.h2 = reinterpret_cast<const float*>(c.ws + net.tensors[conv3.in].offset);
     bp.y = reinterpret_cast<float*>(c.ws + t_y.offset);
-    bp.w3 = net.layers[conv3.conv].d_w_bnp; bp.b3 = net.layers[conv3.conv].d_bias;
+    bp.w3 = net.layers[conv3.conv].packed[PK_BNP].p; bp.b3 = net.layers[conv3.conv].d_bias;
     if (tail) {
         bp.x0 = reinterpret_cast<const float*>(c.ws + net.tensors[a.in].offset);
-        bp.wds = net.layers[a.conv].d_w_bnp; bp.bds = net.layers[a.conv].d_bias;
+        bp.wds = net.layers[a.conv].packed[PK_BNP].p; bp.bds = net.layers[a.conv].d_bias;
     } else {
         bp.res = reinterpret_cast<const float*>(c.ws + net.tensors[a.res].offset);
         bp.h1 = reinterpret_cast<float*>(c.ws + net.tensors[b.out].offset);
-        bp.w1 = net.layers[b.conv].d_w_bnp; bp.b1 = net.layers[b.conv].d_bias;
+        bp.w1 = net.layers[b.conv].packed[PK_BNP].p; bp.b1 = net.layers[b.conv].d_bias;
     }
     bp.P = (long long)c.sb * t_y.H * t_y.W;
     bp.ticket = net.d_tickets + TICKET_SEAM;
@@ -298,8 +294,8 @@ int run_bblockx3(const sncal_hrnet& net, const Launch& e, const Call& c) {
     bp.x = c.ws + net.tensors[ti.twin].offset;
     bp.out_twin = e.m[1].twin ? c.ws + net.tensors[to.twin].offset : nullptr;
     bp.out = e.m[1].f32 ? reinterpret_cast<float*>(c.ws + to.offset) : nullptr;
-    bp.w1 = net.layers[a.conv].d_w_bbx; bp.b1 = net.layers[a.conv].d_bias;
-    bp.w2 = net.layers[b.conv].d_w_bbx; bp.b2 = net.layers[b.conv].d_bias;
+    bp.w1 = net.layers[a.conv].packed[PK_BBX3].p; bp.b1 = net.layers[a.conv].d_bias;
+    bp.w2 = net.layers[b.conv].packed[PK_BBX3].p; bp.b2 = net.layers[b.conv].d_bias;
     bp.N = c.sb; bp.H = ti.H; bp.W = ti.W; bp.out_cstride = to.C; bp.out_coff = b.out_coff;
     bp.ticket = net.d_tickets + TICKET_BBX3;
     return launch_bblockx3(bp, net.n_cus, c.stream);
@@ -311,8 +307,8 @@ int run_bblock48(const sncal_hrnet& net, const Launch& e, const Call& c) {
     const Tensor& ti = net.tensors[a.in];
     BBlockParams bp;
     bp.x = c.ws + ti.offset; bp.out = c.ws + net.tensors[b.out].offset;
-    bp.w1 = net.layers[a.conv].d_w; bp.b1 = net.layers[a.conv].d_bias;
-    bp.w2 = net.layers[b.conv].d_w; bp.b2 = net.layers[b.conv].d_bias;
+    bp.w1 = net.layers[a.conv].packed[PK_GENERIC].p; bp.b1 = net.layers[a.conv].d_bias;
+    bp.w2 = net.layers[b.conv].packed[PK_GENERIC].p; bp.b2 = net.layers[b.conv].d_bias;
     bp.N = c.sb; bp.H = ti.H; bp.W = ti.W; bp.tiles_x = bp.tiles_y = 0; bp.trace = nullptr;
     bp.ticket = net.d_tickets + TICKET_BB48;
     return launch_bblock48(bp, net.n_cus, c.stream);
@@ -708,7 +704,7 @@ extern "C" int sncal_hrnet_calibrate_fp8(sncal_hrnet* net, const float* d_x, int
     for (const Op& op : net->ops) {
         if (op.type != OP_CONV) continue;
         ConvLayer& L = net->layers[op.conv];
-        if (!L.d_w8 || net->tensors[op.in].twin < 0) continue;
+        if (!L.packed[PK_TT_FP8].p || net->tensors[op.in].twin < 0) continue;
         std::vector<float> os(L.cout);
         for (int co = 0; co < L.cout; ++co) os[co] = net->tensors[op.in].scale * L.wscale[co];
         SNCAL_CHECK_HIP(hipMemcpy(L.d_oscale, os.data(), os.size() * 4, hipMemcpyHostToDevice));

@@ -20,8 +20,8 @@ int sncal::layout(sncal_hrnet& net, int sb, int H, int W) {
         auto half = [](int v) { return (v + 2 - 3) / 2 + 1; };
         const int sh = half(H), sw = half(W), bh = half(sh), bw = half(sw);
         const bool dims_ok = net.desc.upscale == 1 || (sh == bh * net.desc.upscale && sw == bw * net.desc.upscale);
-        net.use_fused = net.fused_enabled && net.dtype == SNCAL_BF16 && dims_ok && net.d_hw0 != nullptr;
-        if (net.x3 && net.fused_enabled && dims_ok && net.desc.upscale == 2 && net.d_hw0_32l && net.head_ks16 == 13 && net.head_m2 == 4 &&
+        net.use_fused = net.fused_enabled && net.dtype == SNCAL_BF16 && dims_ok && net.head_packed[HPK_W0].p != nullptr;
+        if (net.x3 && net.fused_enabled && dims_ok && net.desc.upscale == 2 && net.head_packed[HPK_W0_32_LO].p && net.head_ks16 == 13 && net.head_m2 == 4 &&
             headx3_enabled()) {
             // fp16x3: the fused split-arithmetic head (headx3.hip) when its gather boxes fit: branches 2 and 3 against the head's width
             // (the scales head_params will hand headx3_applies, before the tensors have their shapes)
@@ -58,11 +58,11 @@ int sncal::layout(sncal_hrnet& net, int sb, int H, int W) {
     for (const Op& op : net.ops) {
         if (op.type != OP_CONV || !op_active(net, op)) continue;
         ConvLayer& L = net.layers[op.conv];
-        L.x3_on = net.x3 && L.d_w_x3 != nullptr && T[op.in].twin >= 0 && tt_eligible(net, op, sb);
+        L.x3_on = net.x3 && L.packed[PK_TT_X3].p != nullptr && T[op.in].twin >= 0 && tt_eligible(net, op, sb);
         bool w_ok = net.fp8_widths.empty();
         for (int w : net.fp8_widths) w_ok = w_ok || w == L.cout;
         const bool s_ok = net.fp8_stages == 0 || ((net.fp8_stages >> L.stage) & 1u);
-        L.fp8_on = net.fp8 && net.fp8_calibrated && !net.calibrating && L.d_w8 != nullptr && w_ok && s_ok && L.stage >= 2 &&
+        L.fp8_on = net.fp8 && net.fp8_calibrated && !net.calibrating && L.packed[PK_TT_FP8].p != nullptr && w_ok && s_ok && L.stage >= 2 &&
                    T[op.in].twin >= 0 && tt_eligible(net, op, sb);
     }
     for (Tensor& t : T) { t.first = -1; t.last = -1; }

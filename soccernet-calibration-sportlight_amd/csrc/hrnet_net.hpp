@@ -21,6 +21,27 @@
 
 namespace sncal {
 
+// A packed-weight buffer on the device and its size: the size the packer's ..._packed_bytes() gave (pack.hpp), the range of the
+// buffer descriptor through which the kernel reads it, and what tt_eligible bounds by 2^31
+struct DevBuf { void* p = nullptr; size_t bytes = 0; };
+
+enum LayerPacking {      // one per kernel that may read a layer; each format is owned by that kernel's header
+    PK_GENERIC,          // conv.hpp: every layer, fragment order of the layer's (MI, G)
+    PK_TT,               // conv_tt.hpp, bf16: wide 3x3 stride-1 layers
+    PK_TT_FP8,           // conv_tt.hpp, C5 path: e4m3 weights of the same layers, one scale per output channel (wscale); the launch scales by
+                         // d_oscale = (calibrated scale of the layer's input tensor) x wscale
+    PK_TT_X3,            // conv_tt.hpp, split engine: hi / lo weights in 16-channel stages, output-channel blocks of x3_blk
+    PK_BBX3,             // bblockx3.hpp, split engine: pair-step packing of the 48 -> 48 3x3 layers of the fused BasicBlock
+    PK_BNP,              // bneckx3.hpp, split engines: layer1's 1x1 layers (64 -> 256, 256 -> 64) for the fused Bottleneck seam
+    PK_COUNT
+};
+enum HeadPacking {       // head.hpp; layout() picks the head variant from which of these exist and from head_ks16
+    HPK_W0, HPK_W1,              // head.hip, bf16: 16x16x32 fragments
+    HPK_W0_32, HPK_W1_32,        // head32.hip / headx3.hip: 32x32x16 fragments (K1 a multiple of 16); split engines: the hi parts
+    HPK_W0_32_LO, HPK_W1_32_LO,  // headx3.hip: the lo parts of the split weights
+    HPK_COUNT
+};
+
 struct ConvLayer {
     std::string name, bn;
     int cin, cout, k, stride;
@@ -30,25 +51,19 @@ struct ConvLayer {
     bool is_set = false;
     // packing / dispatch
     int cin_phys = 0, mi = 0, g = 0, chunks = 0, nblk = 0, cout_frags = 0;
-    void* d_w = nullptr;
+    DevBuf packed[PK_COUNT];    // null = the layer's shape (or the engine) has no use for that kernel
     float* d_bias = nullptr;
-    void* d_w_tt = nullptr;     // second packing, for the two-team kernel (conv_tt.hip): 32 x 32 x 16 MFMA fragment order
-    // C5 path: e4m3 weights of the same layer for conv_tt_kernel<true> (one scale per output channel), the scales, and
-    // oscale = (calibrated scale of the layer's input tensor) x (weight scale of the channel)
-    void* d_w8 = nullptr;
     std::vector<float> wscale;
-    float* d_oscale = nullptr;
+    float* d_oscale = nullptr;  // allocated with PK_TT_FP8, filled by sncal_hrnet_calibrate_fp8
     int stage = 0;              // 2..4 for model.stageN.* layers, 0 otherwise
     bool fp8_on = false;
-    void* d_w_x3 = nullptr;     // bf16x3 engine: hi / lo split weights in the two-team kernel's fragment order (16-channel stages)
-    int x3_blk = TT_COUT;       // ... packed in output-channel blocks of 96 (tile 96 x 8 x 32) or, for widths that are no multiple of 96, 64 (64 x 12 x 32)
+    int x3_blk = TT_COUT;       // PK_TT_X3: blocks of 96 (tile 96 x 8 x 32) or, for widths that are no multiple of 96, 64 (64 x 12 x 32)
     bool x3_on = false;
-    void* d_w_bbx = nullptr;    // bf16x3 engine, 48 -> 48 3x3 layers: pair-step packing of the fused BasicBlock (bblockx3.hip)
-    void* d_w_bnp = nullptr;    // split engines, layer1's 1x1 layers (64 -> 256, 256 -> 64): A fragments of the fused Bottleneck seam (bneckx3.hip)
     // internal layers of the fused head: t_i = W0[:, col_off : col_off + cin] . branch_i  (derived at finalize)
     bool derived = false;
     int col_off = 0;
     bool derived_shift = false;     // the slice that also carries last_layer.0's folded-BN shift (split head: the direct tensor's)
+    Folded folded() const { return Folded{w.data(), scale.data(), cout, cin, k}; }
 };
 
 enum OpType { OP_INPUT, OP_CONV, OP_UPADD, OP_SOFTMAX, OP_DECODE, OP_HEAD };
@@ -161,9 +176,7 @@ struct sncal_hrnet {
     bool fuse_bblock = getenv("SNCAL_FUSE_BBLOCK") ? atoi(getenv("SNCAL_FUSE_BBLOCK")) != 0 : true;   // 48-channel BasicBlocks as one kernel (bblock.hip), bf16 path
     // split engines, layer1 (bneckx3.hip): bit 0 = conv3 of a Bottleneck + conv1 of the next as one pass, bit 1 = block 0's downsample branch inside its conv3
     int fuse_bneck = sncal::env_int("SNCAL_FUSE_BNECK", 3);
-    void *d_hw0 = nullptr, *d_hw1 = nullptr;
-    void *d_hw0_32 = nullptr, *d_hw1_32 = nullptr;      // head32.hip packing (null when K1 is not a multiple of 16)
-    void *d_hw0_32l = nullptr, *d_hw1_32l = nullptr;    // fp16x3 engine (headx3.hip): lo parts of the split weights; d_hw0_32 / d_hw1_32 then hold the hi parts
+    sncal::DevBuf head_packed[sncal::HPK_COUNT];
     int head_ks16 = 0;
     float *d_hb0 = nullptr, *d_hb1 = nullptr;
     int cur_group = sncal::GRP_ALL;

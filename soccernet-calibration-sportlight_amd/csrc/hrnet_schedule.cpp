@@ -11,19 +11,19 @@ bool sncal::tt_eligible(const sncal_hrnet& net, const Op& op, int sb) {
     const Tensor& ti = net.tensors[op.in];
     const Tensor& to = net.tensors[op.out];
     if (net.x3) {                                   // bf16x3 engine: fp32 tensors, split twin in, fp32 out
-        if (net.dtype != SNCAL_F32 || !L.d_w_x3 || ti.C != L.cin || ti.twin < 0 || to.C % 8 || op.out_coff % 8) return false;
+        if (net.dtype != SNCAL_F32 || !L.packed[PK_TT_X3].p || ti.C != L.cin || ti.twin < 0 || to.C % 8 || op.out_coff % 8) return false;
         // every whole-tensor byte count the kernel forms (input twin, fp32 output, output twin, residual) stays below 2^31: its epilogue
         // relies on voffset 0x80000000 + soffset being out of range for masked lanes, which only holds for ranges below that
         const size_t in_bytes = (size_t)sb * ti.H * ti.W * ti.C * 4, out_bytes = (size_t)sb * to.H * to.W * to.C * 4;
         const size_t twin_bytes = (size_t)sb * to.H * to.W * L.cout * 4;
         return in_bytes < (1u << 31) && out_bytes < (1u << 31) && twin_bytes < (1u << 31) &&
-               (size_t)((L.cout + TT_COUT - 1) / TT_COUT) * (L.cin / 16) * 9 * 6 * 1024 < (1u << 31);
+               L.packed[PK_TT_X3].bytes < (1u << 31);
     }
     if (net.dtype != SNCAL_BF16 || op.out_f32) return false;
-    if (!L.d_w_tt || ti.C != L.cin) return false;                                   // packed at finalize for the eligible shapes
+    if (!L.packed[PK_TT].p || ti.C != L.cin) return false;                                   // packed at finalize for the eligible shapes
     if (to.C % 8 || op.out_coff % 8) return false;
     const size_t in_bytes = (size_t)sb * ti.H * ti.W * ti.C * 2, out_elems = (size_t)sb * to.H * to.W * to.C;
-    return in_bytes < (1u << 31) && out_elems < (1ull << 32) && (size_t)L.nblk * L.chunks * 9 * 6 * 1024 < (1u << 31);
+    return in_bytes < (1u << 31) && out_elems < (1ull << 32) && L.packed[PK_TT].bytes < (1u << 31) && L.packed[PK_TT_FP8].bytes < (1u << 31);
 }
 
 // does the active op that produced tensor t write its e4m3 / split twin itself?
@@ -155,10 +155,10 @@ int tt_cfg(const sncal_hrnet& net, const Op* ops, int n, int sb) {
 bool fuses_bneck_tail(const sncal_hrnet& net, size_t i, int sb) {
     const Op& op = net.ops[i];
     if (!(net.fuse_bneck & 2) || !net.x3 || op.relu || op.res >= 0 || op.out_f32 || op.out_coff != 0 || i + 1 >= net.ops.size() ||
-        !net.layers[op.conv].d_w_bnp || net.layers[op.conv].cout != BNP_WIDE || net.layers[op.conv].x3_on || op.launch_group >= 0) return false;
+        !net.layers[op.conv].packed[PK_BNP].p || net.layers[op.conv].cout != BNP_WIDE || net.layers[op.conv].x3_on || op.launch_group >= 0) return false;
     const Op& nx = net.ops[i + 1];
     return nx.type == OP_CONV && op_active(net, nx) && nx.res == op.out && nx.relu && !nx.out_f32 && nx.out_coff == 0 && nx.launch_group < 0 &&
-           net.layers[nx.conv].d_w_bnp && net.layers[nx.conv].cout == BNP_WIDE && !net.layers[nx.conv].x3_on &&
+           net.layers[nx.conv].packed[PK_BNP].p && net.layers[nx.conv].cout == BNP_WIDE && !net.layers[nx.conv].x3_on &&
            net.tensors[op.in].C == BNP_MID && net.tensors[nx.in].C == BNP_MID && net.tensors[nx.out].C == BNP_WIDE &&
            net.tensors[op.in].H == net.tensors[nx.in].H && net.tensors[op.in].W == net.tensors[nx.in].W &&
            net.tensors[op.out].last_read == (int)i + 1 &&      // nobody else reads the downsample branch
@@ -170,13 +170,13 @@ bool fuses_bneck_tail(const sncal_hrnet& net, size_t i, int sb) {
 bool fuses_bneck_seam(const sncal_hrnet& net, size_t i, int sb) {
     const Op& op = net.ops[i];
     if (!(net.fuse_bneck & 1) || !net.x3 || !op.relu || op.res < 0 || op.out_f32 || op.out_coff != 0 || i + 1 >= net.ops.size() ||
-        !net.layers[op.conv].d_w_bnp || net.layers[op.conv].cout != BNP_WIDE || net.layers[op.conv].x3_on) return false;
+        !net.layers[op.conv].packed[PK_BNP].p || net.layers[op.conv].cout != BNP_WIDE || net.layers[op.conv].x3_on) return false;
     const Op& nx = net.ops[i + 1];
     const Tensor& t_in = net.tensors[op.in];
     const Tensor& t_res = net.tensors[op.res];
     const Tensor& t_y = net.tensors[op.out];
     return nx.type == OP_CONV && op_active(net, nx) && nx.in == op.out && nx.res < 0 && nx.relu && !nx.out_f32 && nx.out_coff == 0 &&
-           nx.launch_group < 0 && net.layers[nx.conv].d_w_bnp && net.layers[nx.conv].cout == BNP_MID && !net.layers[nx.conv].x3_on &&
+           nx.launch_group < 0 && net.layers[nx.conv].packed[PK_BNP].p && net.layers[nx.conv].cout == BNP_MID && !net.layers[nx.conv].x3_on &&
            t_in.C == BNP_MID && t_res.C == BNP_WIDE && t_y.C == BNP_WIDE && net.tensors[nx.out].C == BNP_MID &&
            t_res.H == t_y.H && t_res.W == t_y.W &&
            !writes_twin(net, op.out, sb) && !writes_twin(net, nx.out, sb);      // neither output may owe somebody a split twin (they feed generic kernels)
@@ -187,10 +187,10 @@ bool fuses_bneck_seam(const sncal_hrnet& net, size_t i, int sb) {
 bool fuses_bblockx3(const sncal_hrnet& net, size_t i, int sb) {
     const Op& op = net.ops[i];
     if (!net.x3 || !op.relu || op.res >= 0 || op.out_f32 || i + 1 >= net.ops.size() || !net.layers[op.conv].x3_on ||
-        !net.layers[op.conv].d_w_bbx || !tt_eligible(net, op, sb)) return false;
+        !net.layers[op.conv].packed[PK_BBX3].p || !tt_eligible(net, op, sb)) return false;
     const Op& nx = net.ops[i + 1];
     return nx.type == OP_CONV && op_active(net, nx) && nx.in == op.out && nx.res == op.in && nx.relu && !nx.out_f32 && op.out_coff == 0 &&
-           net.layers[nx.conv].x3_on && net.layers[nx.conv].d_w_bbx && tt_eligible(net, nx, sb) && net.tensors[op.in].C == 48 &&
+           net.layers[nx.conv].x3_on && net.layers[nx.conv].packed[PK_BBX3].p && tt_eligible(net, nx, sb) && net.tensors[op.in].C == 48 &&
            net.tensors[op.in].twin >= 0 && net.tensors[net.tensors[op.in].twin].first >= 0;
 }
 
@@ -441,9 +441,9 @@ void sncal::head_params(const sncal_hrnet& net, const Op& op, int sb, HeadParams
     memset(&hp, 0, sizeof(hp));
     hp.range = net.d_range;
     hp.Cd = td.C;
-    hp.w0 = net.d_hw0; hp.bias0 = net.d_hb0; hp.w1 = net.d_hw1; hp.bias1 = net.d_hb1;
-    hp.w0_32 = net.d_hw0_32; hp.w1_32 = net.d_hw1_32; hp.ks16 = net.head_ks16;
-    hp.w0_32_lo = net.d_hw0_32l; hp.w1_32_lo = net.d_hw1_32l;
+    hp.w0 = net.head_packed[HPK_W0].p; hp.bias0 = net.d_hb0; hp.w1 = net.head_packed[HPK_W1].p; hp.bias1 = net.d_hb1;
+    hp.w0_32 = net.head_packed[HPK_W0_32].p; hp.w1_32 = net.head_packed[HPK_W1_32].p; hp.ks16 = net.head_ks16;
+    hp.w0_32_lo = net.head_packed[HPK_W0_32_LO].p; hp.w1_32_lo = net.head_packed[HPK_W1_32_LO].p;
     hp.nsrc = op.head_nsrc;
     for (int s2 = 0; s2 < op.head_nsrc; ++s2) {
         const Tensor& ts = net.tensors[op.head_src[s2]];

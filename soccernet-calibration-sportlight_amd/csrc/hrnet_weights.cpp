@@ -1,25 +1,30 @@
 // Weights of an HRNet on their way to the device: balance (equalize_blocks) and range check of the split-fp16 engine, the (MI, G)
-// choice of the generic kernel, and one packing per kernel that reads the layer.  Runs in sncal_hrnet_finalize; the packed buffers
-// are owned here (upload fills a slot, release_layer / release_head empty them all).
+// choice of the generic kernel, and per layer one packing for every kernel that may read it.  The packed formats themselves belong to
+// the kernels' headers (pack.hpp says where); this unit asks each format's predicate, calls its packer and uploads the bytes into the
+// layer's / the head's DevBuf slots, which it owns.  Runs in sncal_hrnet_finalize.
 #include "hrnet_net.hpp"
 
 using namespace sncal;
 
 namespace {
 
-void release(std::initializer_list<void**> slots) { for (void** q : slots) if (*q) { (void)hipFree(*q); *q = nullptr; } }
+void release(DevBuf& b) { if (b.p) (void)hipFree(b.p); b = DevBuf{}; }
+void release(float*& q) { if (q) (void)hipFree(q); q = nullptr; }
 
 // host vector -> the device buffer in `slot`, in place of what the slot held
-template <class P, class T> int upload(P*& slot, const std::vector<T>& host) {
-    release({reinterpret_cast<void**>(&slot)});
-    SNCAL_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&slot), host.size() * sizeof(T)));
-    SNCAL_CHECK_HIP(hipMemcpy(slot, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+template <class T> int upload(DevBuf& slot, const std::vector<T>& host) {
+    release(slot);
+    SNCAL_CHECK_HIP(hipMalloc(&slot.p, host.size() * sizeof(T)));
+    slot.bytes = host.size() * sizeof(T);
+    SNCAL_CHECK_HIP(hipMemcpy(slot.p, host.data(), slot.bytes, hipMemcpyHostToDevice));
     return SNCAL_OK;
 }
-
-// every packed buffer of a layer / of the head
-void release_layer(ConvLayer& L) { release({&L.d_w, (void**)&L.d_bias, &L.d_w_tt, &L.d_w8, (void**)&L.d_oscale, &L.d_w_x3, &L.d_w_bbx, &L.d_w_bnp}); }
-void release_head(sncal_hrnet& net) { release({&net.d_hw0, &net.d_hw1, &net.d_hw0_32, &net.d_hw1_32, &net.d_hw0_32l, &net.d_hw1_32l, (void**)&net.d_hb0, (void**)&net.d_hb1}); }
+int upload(float*& slot, const std::vector<float>& host) {
+    DevBuf b{slot, 0};
+    const int rc = upload(b, host);
+    slot = static_cast<float*>(b.p);
+    return rc;
+}
 
 // choose (MI, G) for a layer: maximise useful/padded work x operand reuse among the instantiated variants
 void choose_packing(sncal_hrnet& net, ConvLayer& L) {
@@ -33,10 +38,10 @@ void choose_packing(sncal_hrnet& net, ConvLayer& L) {
           if (force_mi_s2 && L.k == 3 && L.stride == 2 && L.cin_phys >= 48 && V.mi != force_mi_s2 && cout_frags % force_mi_s2 == 0) continue; }
         { static const int force_g_s2 = env_int("SNCAL_FORCE_G_S2", 0);
           if (force_g_s2 && L.k == 3 && L.stride == 2 && L.cin_phys >= 48 && V.g != force_g_s2) continue; }
-        const int chunks = (L.cin_phys + V.g * ge - 1) / (V.g * ge);
+        const ConvPackShape s{L.cin, L.cin_phys, L.cout, L.k, ge, V.mi, V.g};
+        const int chunks = s.chunks(), nblk = s.nblk();
         const int nks = conv_nks(V.ks, V.g);
         const double k_eff = (double)(L.k * L.k * L.cin_phys / ge) / (double)(chunks * nks * 4);
-        const int nblk = (cout_frags + V.mi - 1) / V.mi;
         const double m_eff = (double)cout_frags / (nblk * V.mi);
         const double reuse = (double)(V.mi * 4) / (V.mi + 4);           // MFMAs per LDS fragment read (NI=4 nominal)
         const double per_chunk = (double)nks / (nks + 1.0);              // amortisation of the per-chunk sync/load
@@ -48,266 +53,85 @@ void choose_packing(sncal_hrnet& net, ConvLayer& L) {
         if (score > best + 1e-9) { best = score; L.mi = V.mi; L.g = V.g; }
     }
     L.cout_frags = cout_frags;
-    L.nblk = (cout_frags + L.mi - 1) / L.mi;
-    L.chunks = (L.cin_phys + L.g * ge - 1) / (L.g * ge);
+    if (L.mi == 0) return;       // no variant (pack_weights reports it): no shape to ask
+    const ConvPackShape s{L.cin, L.cin_phys, L.cout, L.k, ge, L.mi, L.g};
+    L.nblk = s.nblk();
+    L.chunks = s.chunks();
 }
 
-inline uint16_t f2bf(float f) {   // round-to-nearest-even
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
+// every packing of a layer that a kernel of this engine may read (the predicates say which), in the slots of L.packed
 int pack_layer(sncal_hrnet& net, ConvLayer& L) {
-    const int ge = net.ge, KS = L.k, G = L.g, MI = L.mi;
-    const int nks = conv_nks(KS, G);
-    const size_t n16 = (size_t)L.nblk * L.chunks * nks * MI * 64;       // 16-byte vectors
-    std::vector<uint8_t> host(n16 * 16, 0);
-    for (int nb = 0; nb < L.nblk; ++nb)
-        for (int c = 0; c < L.chunks; ++c)
-            for (int s = 0; s < nks; ++s)
-                for (int mi = 0; mi < MI; ++mi)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int m = lane & 15, g = lane >> 4;
-                        const int kg = 4 * s + g;
-                        const int tap = kg / G, cgi = kg % G;
-                        const int co = (nb * MI + mi) * 16 + m;
-                        uint8_t* dst = host.data() + ((((size_t)(nb * L.chunks + c) * nks + s) * MI + mi) * 64 + lane) * 16;
-                        if (tap >= KS * KS || co >= L.cout) continue;
-                        for (int e = 0; e < ge; ++e) {
-                            const int ci = (c * G + cgi) * ge + e;
-                            if (ci >= L.cin) continue;
-                            const float v = L.w[(((size_t)co * L.cin + ci) * KS + tap / KS) * KS + tap % KS] * L.scale[co];
-                            if (net.dtype == SNCAL_BF16) { const uint16_t b = f2bf(v); memcpy(dst + e * 2, &b, 2); }
-                            else if (net.x3) {                  // [4 hi | 4 lo]: hi = rne16(w), lo = rne16(w - hi) (x3.hpp)
-                                uint16_t h, l;
-                                x3_split_host(v, &h, &l);
-                                memcpy(dst + e * 2, &h, 2); memcpy(dst + 8 + e * 2, &l, 2);
-                            }
-                            else memcpy(dst + e * 4, &v, 4);
-                        }
-                    }
-    std::vector<float> bias((size_t)L.nblk * MI * 16, 0.f);
-    for (int co = 0; co < L.cout; ++co) bias[co] = L.shift[co];
-    if (const int rc = upload(L.d_w, host)) return rc;
-    return upload(L.d_bias, bias);
-}
-
-// Packing of a wide 3x3 stride-1 layer for the two-team kernel (conv_tt.hip): per (96-channel block nb, 32-channel chunk c)
-// one 54 KB stage [tap 9][channel half 2][32-row block 3][lane 64] x 8 bf16, the A fragments of v_mfma_f32_32x32x16_bf16:
-// lane l holds output channel nb * 96 + mb * 32 + (l & 31), input channels c * 32 + h * 16 + (l >> 5) * 8 + 0..7 of the tap.
-bool tt_shape_ok(const sncal_hrnet& net, const ConvLayer& L) {
-    return net.dtype == SNCAL_BF16 && L.k == 3 && L.stride == 1 && L.cin == L.cin_phys && L.cin % TT_CIN == 0 &&
-           L.cout % TT_COUT == 0 && L.cout <= 480;
-}
-
-// bf16x3 engine: [nb][16-channel chunk c][tap 9][part: hi, lo][32-row block 3][lane 64] x 8 bf16 -- the two-team kernel's stage layout
-// with the stage's two K = 16 steps holding the hi and the lo parts of the SAME 16 input channels: lane l holds output channel
-// nb * 96 + mb * 32 + (l & 31) (zero rows above the layer's width: a 48-channel layer runs as one padded 96-channel block), input
-// channels c * 16 + (l >> 5) * 8 + 0..7 of the tap; hi = bf16(w), lo = bf16(w - hi), w = folded weight in fp32.
-bool x3_shape_ok(const sncal_hrnet& net, const ConvLayer& L) {
-    return net.x3 && net.dtype == SNCAL_F32 && L.k == 3 && L.stride == 1 && L.stage >= 2 && L.cin == L.cin_phys && L.cin % 16 == 0 &&
-           L.cout % 16 == 0 && L.cout <= 480;
-}
-
-int pack_layer_x3(sncal_hrnet& net, ConvLayer& L) {
-    if (!x3_shape_ok(net, L)) return SNCAL_OK;
-    L.x3_blk = L.cout % TT_COUT == 0 ? TT_COUT : 64;       // 48 channels: one padded 64-channel block (25 % zero rows) instead of 96 (50 %)
-    const int MBk = L.x3_blk / 32;
-    const int chunks = L.cin / 16, nblk = (L.cout + L.x3_blk - 1) / L.x3_blk;
-    std::vector<uint16_t> host((size_t)nblk * chunks * 9 * 2 * MBk * 64 * 8, 0);
-    for (int nb = 0; nb < nblk; ++nb)
-        for (int c = 0; c < chunks; ++c)
-            for (int s = 0; s < 9; ++s)
-                for (int mb = 0; mb < MBk; ++mb)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        // MFMA row r = lane & 31 computes channel x3_row_channel(r) of its block: quads 2 p, 2 p + 1 of a lane's accumulator
-                        // registers are then 8 consecutive channels (conv_tt_body.inc x3_quad_channel, the twin-only epilogue)
-                        const int r = lane & 31, rq = r >> 3, rh = (r >> 2) & 1, ri = r & 3;
-                        const int co = nb * L.x3_blk + mb * 32 + 16 * (rq >> 1) + 8 * rh + 4 * (rq & 1) + ri;
-                        if (co >= L.cout) continue;
-                        uint16_t* hi = host.data() + ((((((size_t)nb * chunks + c) * 9 + s) * 2 + 0) * MBk + mb) * 64 + lane) * 8;
-                        uint16_t* lo = host.data() + ((((((size_t)nb * chunks + c) * 9 + s) * 2 + 1) * MBk + mb) * 64 + lane) * 8;
-                        for (int e = 0; e < 8; ++e) {
-                            const int ci = c * 16 + (lane >> 5) * 8 + e;
-                            const float w = L.w[(((size_t)co * L.cin + ci) * 3 + s / 3) * 3 + s % 3] * L.scale[co];
-                            x3_split_host(w, &hi[e], &lo[e]);
-                        }
-                    }
-    return upload(L.d_w_x3, host);
-}
-
-// bf16x3 engine: the fused 48-channel BasicBlock's own packing of a 48 -> 48 layer (bblockx3.hpp: 14 pair-steps of 6 KB)
-int pack_layer_bbx3(sncal_hrnet& net, ConvLayer& L) {
-    if (!x3_shape_ok(net, L) || L.cin != 48 || L.cout != 48) return SNCAL_OK;
-    std::vector<uint16_t> host;
-    bbx3_pack_weights(L.w.data(), L.scale.data(), [](float v, uint16_t* hi, uint16_t* lo) { x3_split_host(v, hi, lo); }, host);
-    return upload(L.d_w_bbx, host);
-}
-
-// split engines: a 1x1 layer of layer1 in the fused Bottleneck seam's fragment order (bneckx3.hpp)
-int pack_layer_bnp(sncal_hrnet& net, ConvLayer& L) {
-    const bool shape = L.k == 1 && L.stride == 1 && ((L.cin == BNP_MID && L.cout == BNP_WIDE) || (L.cin == BNP_WIDE && L.cout == BNP_MID));
-    if (!net.x3 || net.dtype != SNCAL_F32 || !shape || L.derived) return SNCAL_OK;
-    std::vector<uint16_t> host;
-    bnp_pack_weights(L.w.data(), L.scale.data(), L.cout, L.cin, [](float v, uint16_t* hi, uint16_t* lo) { x3_split_host(v, hi, lo); }, host);
-    return upload(L.d_w_bnp, host);
-}
-
-int pack_layer_tt(sncal_hrnet& net, ConvLayer& L) {
-    if (!tt_shape_ok(net, L)) return SNCAL_OK;
-    const int chunks = L.cin / TT_CIN, nblk = L.cout / TT_COUT;
-    std::vector<uint16_t> host((size_t)nblk * chunks * 9 * 2 * 3 * 64 * 8, 0);
-    for (int nb = 0; nb < nblk; ++nb)
-        for (int c = 0; c < chunks; ++c)
-            for (int s = 0; s < 9; ++s)
-                for (int h = 0; h < 2; ++h)
-                    for (int mb = 0; mb < 3; ++mb)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int co = nb * TT_COUT + mb * 32 + (lane & 31);
-                            uint16_t* dst = host.data() + ((((((size_t)nb * chunks + c) * 9 + s) * 2 + h) * 3 + mb) * 64 + lane) * 8;
-                            for (int e = 0; e < 8; ++e) {
-                                const int ci = c * TT_CIN + h * 16 + (lane >> 5) * 8 + e;
-                                dst[e] = f2bf(L.w[(((size_t)co * L.cin + ci) * 3 + s / 3) * 3 + s % 3] * L.scale[co]);
-                            }
-                        }
-    return upload(L.d_w_tt, host);
-}
-
-// float -> OCP e4m3fn (1-4-3, bias 7, max 448, no infinities), round to nearest even, saturating
-inline uint8_t f2fp8(float f) {
-    if (!(f == f)) return 0x7f;
-    const uint8_t sign = f < 0 ? 0x80 : 0;
-    float a = std::fabs(f);
-    if (a >= 448.f) return sign | 0x7e;
-    if (a < 0.0009765625f) return sign;                    // below half the smallest subnormal (2^-9 / 2): zero
-    int e;
-    float m = std::frexp(a, &e);                            // a = m * 2^e, m in [0.5, 1)
-    int E = e - 1 + 7;                                      // biased exponent of 1.xxx * 2^(e-1)
-    int q;
-    if (E >= 1) {                                           // normal: 3 mantissa bits
-        const float x = (m * 2.f - 1.f) * 8.f;
-        q = (int)std::nearbyint(x);
-        if (q == 8) { q = 0; ++E; }
-        if (E > 15 || (E == 15 && q > 6)) return sign | 0x7e;
-        return sign | (uint8_t)(E << 3) | (uint8_t)q;
+    const Folded W = L.folded();
+    {
+        std::vector<uint8_t> w;
+        std::vector<float> bias;
+        conv_pack_weights(W, L.shift.data(), ConvPackShape{L.cin, L.cin_phys, L.cout, L.k, net.ge, L.mi, L.g},
+                          net.dtype == SNCAL_BF16 ? CONV_PACK_BF16 : net.x3 ? CONV_PACK_X3 : CONV_PACK_F32, w, bias);
+        if (const int rc = upload(L.packed[PK_GENERIC], w)) return rc;
+        if (const int rc = upload(L.d_bias, bias)) return rc;
     }
-    q = (int)std::nearbyint(a * 512.f);                     // subnormal: multiples of 2^-9
-    if (q >= 8) return sign | 0x08;
-    return sign | (uint8_t)q;
-}
-
-// Packing of a wide 3x3 stride-1 layer for the fp8 variant of the two-team kernel: per (96-channel block nb, 64-channel chunk c)
-// one 54 KB stage [tap 9][32-row block 3][half 2][lane 64] x 16 e4m3, the A operand of v_mfma_scale_f32_32x32x64_f8f6f4: lane l
-// holds output channel nb * 96 + mb * 32 + (l & 31), input channels c * 64 + 32 (l >> 5) + 16 half + 0..15 of the tap (zeros
-// beyond Cin).  One scale per output channel: wscale = max |w| / 448 over the folded weights of the channel.
-int pack_layer_fp8(sncal_hrnet& net, ConvLayer& L) {
-    if (!net.fp8 || !tt_shape_ok(net, L)) return SNCAL_OK;
-    const int chunks = (L.cin + 63) / 64, nblk = L.cout / TT_COUT;
-    L.wscale.assign(L.cout, 1.f);
-    for (int co = 0; co < L.cout; ++co) {
-        float mx = 0.f;
-        for (size_t i = 0; i < (size_t)L.cin * 9; ++i) mx = std::max(mx, std::fabs(L.w[(size_t)co * L.cin * 9 + i] * L.scale[co]));
-        L.wscale[co] = mx > 0.f ? mx / 448.f : 1.f;
+    if (net.dtype == SNCAL_BF16 && tt_shape_ok(L.k, L.stride, L.cin, L.cin_phys, L.cout)) {
+        std::vector<uint16_t> w;
+        tt_pack_weights(W, w);
+        if (const int rc = upload(L.packed[PK_TT], w)) return rc;
+        if (net.fp8) {
+            std::vector<uint8_t> w8;
+            tt8_pack_weights(W, w8, L.wscale);
+            if (!L.d_oscale) SNCAL_CHECK_HIP(hipMalloc((void**)&L.d_oscale, (size_t)L.cout * 4));      // (filled by sncal_hrnet_calibrate_fp8)
+            if (const int rc = upload(L.packed[PK_TT_FP8], w8)) return rc;
+        }
     }
-    std::vector<uint8_t> host((size_t)nblk * chunks * 9 * 3 * 2 * 64 * 16, 0);
-    for (int nb = 0; nb < nblk; ++nb)
-        for (int c = 0; c < chunks; ++c)
-            for (int s = 0; s < 9; ++s)
-                for (int mb = 0; mb < 3; ++mb)
-                    for (int half = 0; half < 2; ++half)
-                        for (int lane = 0; lane < 64; ++lane) {
-                            const int co = nb * TT_COUT + mb * 32 + (lane & 31);
-                            uint8_t* dst = host.data() + (((((((size_t)nb * chunks + c) * 9 + s) * 3 + mb) * 2 + half) * 64) + lane) * 16;
-                            for (int e = 0; e < 16; ++e) {
-                                const int ci = c * 64 + 32 * (lane >> 5) + 16 * half + e;
-                                if (ci < L.cin) dst[e] = f2fp8(L.w[(((size_t)co * L.cin + ci) * 3 + s / 3) * 3 + s % 3] * L.scale[co] / L.wscale[co]);
-                            }
-                        }
-    if (!L.d_oscale) SNCAL_CHECK_HIP(hipMalloc((void**)&L.d_oscale, (size_t)L.cout * 4));      // (filled by sncal_hrnet_calibrate_fp8)
-    return upload(L.d_w8, host);
+    if (net.x3 && net.dtype == SNCAL_F32) {
+        std::vector<uint16_t> w;
+        if (x3_shape_ok(L.k, L.stride, L.stage, L.cin, L.cin_phys, L.cout)) {
+            L.x3_blk = ttx3_block(L.cout);
+            ttx3_pack_weights(W, L.x3_blk, w);
+            if (const int rc = upload(L.packed[PK_TT_X3], w)) return rc;
+            if (L.cin == 48 && L.cout == 48) {
+                bbx3_pack_weights(W, w);
+                if (const int rc = upload(L.packed[PK_BBX3], w)) return rc;
+            }
+        }
+        if (bnp_shape_ok(L.k, L.stride, L.cin, L.cout) && !L.derived) {
+            bnp_pack_weights(W, w);
+            if (const int rc = upload(L.packed[PK_BNP], w)) return rc;
+        }
+    }
+    return SNCAL_OK;
 }
 
-// A fragments + biases of the fused head: head.hip's 16 x 16 x 32 layout (bf16 engine: d_hw0 / d_hw1) and, when K1 is a multiple of 16,
-// the 32 x 32 x 16 layout of head32.hip (bf16: d_hw0_32 / d_hw1_32) and headx3.hip (split engines: every weight as hi + lo, the lo parts
-// in d_hw0_32l / d_hw1_32l).  layout() picks the head variant from which of these are non-null and from head_ks16
+// A fragments + biases of the fused head (head.hpp): head.hip's 16x16x32 packing (bf16 engine) and, when K1 is a multiple of 16, the
+// 32x32x16 packing of head32.hip (bf16) and headx3.hip (split engines: hi and lo parts)
 int pack_head(sncal_hrnet& net) {
     if (net.dtype != SNCAL_BF16 && !net.x3) return SNCAL_OK;
     const ConvLayer& H0 = net.layers[net.l_head0];
     const ConvLayer& H1 = net.layers[net.l_head1];
     if (!H1.is_set) { set_error("conv %s has no weights", H1.name.c_str()); return SNCAL_ERR_STATE; }
-    const int HP = net.head_hp, NQ = HP / 32, M2 = net.head_m2, Cd = net.head_direct_c, coff = net.head_direct_coff;
-    const int K1 = net.head_k, KS1 = net.head_ks1;      // stage-1 K: the first K1 concat columns (direct + folded branches)
-    if (Cd > 64 || M2 > 4 || K1 > KS1 * 32) return SNCAL_OK;      // fused kernel does not apply; the reference formulation is used
+    // stage-1 K (head_k): the first concat columns (direct + folded branches)
+    const HeadPackShape s{net.head_hp, net.head_m2, net.head_direct_c, net.head_direct_coff, net.head_k, net.head_ks1};
+    if (!head_shape_ok(s)) return SNCAL_OK;      // fused kernel does not apply; the reference formulation is used
+    const Folded W0 = H0.folded(), W1 = H1.folded();
+    DevBuf* P = net.head_packed;
     net.head_ks16 = 0;
-    if (K1 % 16 == 0) {       // A fragments of v_mfma_f32_32x32x16_bf16 -- lane l holds row h32_row_channel(l & 31) of the 32-row
-        const int KS16 = K1 / 16, RB = (M2 * 16 + 31) / 32;                // block, k = 16 ks + 8 (l >> 5) + 0..7
-        std::vector<uint16_t> v0((size_t)NQ * KS16 * 64 * 8, 0), v1((size_t)NQ * RB * 2 * 64 * 8, 0), v0l, v1l;
-        if (net.x3) { v0l.assign(v0.size(), 0); v1l.assign(v1.size(), 0); }
-        auto put = [&](std::vector<uint16_t>& hi, std::vector<uint16_t>& lo, size_t o, float w) {      // bf16: rounded; split engines: hi + lo
-            if (net.x3) x3_split_host(w, &hi[o], &lo[o]); else hi[o] = f2bf(w);
-        };
-        for (int q = 0; q < NQ; ++q)
-            for (int lane = 0; lane < 64; ++lane) {
-                const int row = h32_row_channel(lane & 31), kb = (lane >> 5) * 8;
-                const int ch = q * 32 + row;
-                for (int ks = 0; ks < KS16 && ch < H0.cout; ++ks) {
-                    const size_t o = (((size_t)q * KS16 + ks) * 64 + lane) * 8;
-                    for (int e = 0; e < 8; ++e) put(v0, v0l, o + e, H0.w[(size_t)ch * H0.cin + coff + ks * 16 + kb + e] * H0.scale[ch]);
-                }
-                for (int rb = 0; rb < RB; ++rb)
-                    for (int h = 0; h < 2; ++h) {
-                        const int cls = rb * 32 + row;
-                        if (cls >= H1.cout) continue;
-                        const size_t o = ((((size_t)q * RB + rb) * 2 + h) * 64 + lane) * 8;
-                        for (int e = 0; e < 8; ++e) {
-                            const int k = q * 32 + h * 16 + kb + e;
-                            if (k < H1.cin) put(v1, v1l, o + e, H1.w[(size_t)cls * H1.cin + k] * H1.scale[cls]);
-                        }
-                    }
-            }
-        if (const int rc = upload(net.d_hw0_32, v0)) return rc;
-        if (const int rc = upload(net.d_hw1_32, v1)) return rc;
+    if (s.K1 % 16 == 0) {
+        std::vector<uint16_t> w0, w1, w0_lo, w1_lo;
+        head32_pack_weights(W0, W1, s, net.x3, w0, w1, w0_lo, w1_lo);
+        if (const int rc = upload(P[HPK_W0_32], w0)) return rc;
+        if (const int rc = upload(P[HPK_W1_32], w1)) return rc;
         if (net.x3) {
-            if (const int rc = upload(net.d_hw0_32l, v0l)) return rc;
-            if (const int rc = upload(net.d_hw1_32l, v1l)) return rc;
+            if (const int rc = upload(P[HPK_W0_32_LO], w0_lo)) return rc;
+            if (const int rc = upload(P[HPK_W1_32_LO], w1_lo)) return rc;
         }
-        net.head_ks16 = KS16;
+        net.head_ks16 = s.KS16();
     }
     if (!net.x3) {            // head.hip, bf16 only
-        std::vector<uint16_t> w0((size_t)NQ * 2 * KS1 * 64 * 8, 0), w1((size_t)NQ * M2 * 64 * 8, 0);
-        for (int q = 0; q < NQ; ++q)
-            for (int f = 0; f < 2; ++f)
-                for (int ks = 0; ks < KS1; ++ks)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int m = lane & 15, gk = lane >> 4;
-                        const int ch = q * 32 + (m >> 2) * 8 + f * 4 + (m & 3);      // row permutation, see head.hip
-                        if (ch >= H0.cout) continue;
-                        uint16_t* dst = w0.data() + ((((size_t)(q * 2 + f) * KS1 + ks) * 64) + lane) * 8;
-                        for (int e = 0; e < 8; ++e) {
-                            const int k = ks * 32 + gk * 8 + e;
-                            if (k < K1) dst[e] = f2bf(H0.w[(size_t)ch * H0.cin + coff + k] * H0.scale[ch]);
-                        }
-                    }
-        for (int q = 0; q < NQ; ++q)
-            for (int mi = 0; mi < M2; ++mi)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int cls = mi * 16 + (lane & 15), gk = lane >> 4;
-                    if (cls >= H1.cout) continue;
-                    uint16_t* dst = w1.data() + (((size_t)(q * M2 + mi) * 64) + lane) * 8;
-                    for (int e = 0; e < 8; ++e) {
-                        const int k = q * 32 + gk * 8 + e;
-                        if (k < H1.cin) dst[e] = f2bf(H1.w[(size_t)cls * H1.cin + k] * H1.scale[cls]);
-                    }
-                }
-        if (const int rc = upload(net.d_hw0, w0)) return rc;
-        if (const int rc = upload(net.d_hw1, w1)) return rc;
+        std::vector<uint16_t> w0, w1;
+        head_pack_weights(W0, W1, s, w0, w1);
+        if (const int rc = upload(P[HPK_W0], w0)) return rc;
+        if (const int rc = upload(P[HPK_W1], w1)) return rc;
     }
-    std::vector<float> b0(HP, 0.f), b1((size_t)std::max(M2 * 16, 64), 0.f);      // head32's decode epilogue reads 64 bias slots whatever C
-    for (int co = 0; co < H0.cout; ++co) b0[co] = H0.shift[co];
-    for (int c = 0; c < H1.cout; ++c) b1[c] = H1.shift[c];
+    std::vector<float> b0, b1;
+    head_pack_bias(H0.shift.data(), H0.cout, H1.shift.data(), H1.cout, s, b0, b1);
     if (const int rc = upload(net.d_hb0, b0)) return rc;
     return upload(net.d_hb1, b1);
 }
@@ -459,14 +283,17 @@ int sncal::pack_weights(sncal_hrnet& net) {
         if (!L.is_set) { set_error("conv %s has no weights", L.name.c_str()); return SNCAL_ERR_STATE; }
         choose_packing(net, L);
         if (L.mi == 0) { set_error("no kernel variant for conv %s (k=%d s=%d)", L.name.c_str(), L.k, L.stride); return SNCAL_ERR_STATE; }
-        for (auto pack : {pack_layer, pack_layer_tt, pack_layer_fp8, pack_layer_x3, pack_layer_bbx3, pack_layer_bnp})      // each packs what its kernel serves
-            if (const int rc = pack(net, L)) return rc;
+        if (const int rc = pack_layer(net, L)) return rc;
         std::vector<float>().swap(L.w);
     }
     return SNCAL_OK;
 }
 
 void sncal::release_weights(sncal_hrnet& net) {
-    for (ConvLayer& L : net.layers) release_layer(L);
-    release_head(net);
+    for (ConvLayer& L : net.layers) {
+        for (DevBuf& b : L.packed) release(b);
+        release(L.d_bias); release(L.d_oscale);
+    }
+    for (DevBuf& b : net.head_packed) release(b);
+    release(net.d_hb0); release(net.d_hb1);
 }

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstring>
+#include "pack.hpp"      // f2h, h2f, f2bf
 
 #ifndef SNCAL_X3_F16
 #define SNCAL_X3_F16 1
@@ -163,18 +164,14 @@ __device__ __forceinline__ void x3_split4(const float (&v)[4], float lob, x3u2& 
 inline uint16_t x3_code_host(float v) {
 #if SNCAL_X3_F16
     v = v > 65504.f ? 65504.f : v < -65504.f ? -65504.f : v;
-    const _Float16 h = (_Float16)v;
-    uint16_t c; memcpy(&c, &h, 2); return c;
+    return f2h(v);
 #else
-    uint32_t u; memcpy(&u, &v, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
+    return f2bf(v);
 #endif
 }
 inline float x3_value_host(uint16_t c) {
 #if SNCAL_X3_F16
-    _Float16 h; memcpy(&h, &c, 2); return (float)h;
+    return h2f(c);
 #else
     const uint32_t u = (uint32_t)c << 16; float f; memcpy(&f, &u, 4); return f;
 #endif
