@@ -229,6 +229,11 @@ typedef struct {
     int res_twin;              /* bf16x3: this conv reads its residual from the split twin of tensor `res`, not from its fp32 form */
     int launch;                /* index, in the launch schedule of the layout's own sub-batch size, of the launch that covers this op
                                   (grouped members and the ops of a fused pair share one); -1 = inactive or no schedule yet        */
+    /* What that schedule decided for the op (all 0 when inactive or no schedule yet): */
+    int writes_out;            /* 1 = the launch covering this op writes tensor `out` in its dense form (0 for the first op of a fused
+                                  pair whose output stays in LDS, and for a producer whose dense form nobody reads)                 */
+    int writes_twin;           /* 1 = that launch writes the e4m3 / split twin of `out`                                            */
+    int prep_in;               /* the helper in front of the launch that makes the twin of `in`: 0 none, 1 quantize_fp8, 2 split_f32 */
 } sncal_plan_op;
 typedef struct {
     int C, H, W;               /* NHWC, per frame                                                                              */
@@ -246,7 +251,7 @@ int sncal_hrnet_plan_num_ops(const sncal_hrnet* net);
 int sncal_hrnet_plan_num_tensors(const sncal_hrnet* net);
 /* Valid after sncal_hrnet_workspace / a forward at the shape of interest (the layout decides sizes, twins and head variant);
  * on a finalized network sncal_hrnet_workspace also builds the launch schedule of that sub-batch size (host work only), so that
- * sncal_plan_op.launch is valid without a forward. */
+ * sncal_plan_op.launch, writes_out, writes_twin and prep_in are valid without a forward. */
 int sncal_hrnet_plan_op(const sncal_hrnet* net, int idx, sncal_plan_op* out);
 int sncal_hrnet_plan_tensor(const sncal_hrnet* net, int id, sncal_plan_tensor* out);
 /* Register a tap (op_idx >= 0) or clear all taps (op_idx < 0).  d_dst must hold sncal_plan_tensor.bytes. */

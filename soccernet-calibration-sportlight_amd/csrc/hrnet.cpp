@@ -28,8 +28,8 @@ void conv_params(const sncal_hrnet& net, const Op& op, int sb, char* ws, const M
     memset(&p, 0, sizeof(p));
     p.range = net.d_range;
     p.in = ws + ti.offset;
-    p.out = m.f32 ? ws + to.offset : nullptr;
-    p.out_twin = m.twin ? ws + net.tensors[to.twin].offset : nullptr;
+    p.out = m.out.dense ? ws + to.offset : nullptr;
+    p.out_twin = m.out.twin ? ws + net.tensors[to.twin].offset : nullptr;
     p.res = op.res >= 0 ? ws + net.tensors[op.res].offset : nullptr;
     p.w = L.packed[PK_GENERIC].p; p.w_bytes = (unsigned)L.packed[PK_GENERIC].bytes; p.bias = L.d_bias;
     p.N = sb; p.Hin = ti.H; p.Win = ti.W; p.Cin = ti.C;
@@ -49,15 +49,13 @@ void conv_params(const sncal_hrnet& net, const Op& op, int sb, char* ws, const M
     p.nblk_magic = conv_magic((unsigned)L.nblk); p.tiles_x_magic = conv_magic((unsigned)p.tiles_x); p.tiles_y_magic = conv_magic((unsigned)p.tiles_y);
 }
 
-void tt_member(const sncal_hrnet& net, const Op& op, int sb, char* ws, TTMember& m) {
+void tt_member(const sncal_hrnet& net, const Op& op, const Member& mem, int sb, char* ws, TTMember& m) {
     const ConvLayer& L = net.layers[op.conv];
     const Tensor& ti = net.tensors[op.in];
     const Tensor& to = net.tensors[op.out];
-    bool out = true, twin = false;
-    tt_outputs(net, op, sb, &out, &twin);
     memset(&m, 0, sizeof(m));
-    m.in = ws + ti.offset; m.out = out ? ws + to.offset : nullptr; m.res = op.res >= 0 ? ws + net.tensors[op.res].offset : nullptr;
-    m.out8 = twin ? ws + net.tensors[to.twin].offset : nullptr;
+    m.in = ws + ti.offset; m.out = mem.out.dense ? ws + to.offset : nullptr; m.res = op.res >= 0 ? ws + net.tensors[op.res].offset : nullptr;
+    m.out8 = mem.out.twin ? ws + net.tensors[to.twin].offset : nullptr;
     m.w = L.packed[PK_TT].p; m.w_bytes = (unsigned)L.packed[PK_TT].bytes; m.bias = L.d_bias;
     m.N = sb; m.H = ti.H; m.W = ti.W; m.Cin = L.cin; m.chunks = tt_chunks(L.cin);
     m.cout = L.cout; m.out_cstride = to.C; m.out_coff = op.out_coff; m.relu = op.relu ? 1 : 0;
@@ -77,7 +75,7 @@ void tt_member(const sncal_hrnet& net, const Op& op, int sb, char* ws, TTMember&
         m.chunks = tt8_chunks(L.cin);
         m.w = L.packed[PK_TT_FP8].p; m.w_bytes = (unsigned)L.packed[PK_TT_FP8].bytes;
         m.oscale = L.d_oscale;
-        m.out8_inv_scale = twin && to.scale > 0.f ? 1.0f / to.scale : 1.0f;
+        m.out8_inv_scale = mem.out.twin && to.scale > 0.f ? 1.0f / to.scale : 1.0f;
     }
 }
 
@@ -169,15 +167,14 @@ int run_tt(sncal_hrnet& net, Launch& e, const Call& c) {
             const int rc = launch_absmax_bf16(c.ws + ti.offset, (size_t)sb * ti.H * ti.W * ti.C, net.d_amax + ops[i].in, stream);
             if (rc) return rc;
         }
-        if (x3 && !twin_written_by_producer(net, ops[i].in, sb)) {       // bf16x3: the fp32 input's split twin, unless its producer wrote it
-            const int rc = launch_split_f32(c.ws + ti.offset, c.ws + net.tensors[ti.twin].offset, (size_t)sb * ti.H * ti.W * ti.C, stream, net.d_range);
-            if (rc) return rc;
+        int rc = SNCAL_OK;
+        switch (e.m[i].prep) {       // the input's twin, where no producer wrote it
+            case PREP_NONE: break;
+            case PREP_SPLIT_F32: rc = launch_split_f32(c.ws + ti.offset, c.ws + net.tensors[ti.twin].offset, (size_t)sb * ti.H * ti.W * ti.C, stream, net.d_range); break;
+            case PREP_QUANT_FP8: rc = launch_quantize_fp8(c.ws + ti.offset, c.ws + net.tensors[ti.twin].offset, (size_t)sb * ti.H * ti.W * ti.C, ti.scale, stream); break;
         }
-        if (fp8 && !twin_written_by_producer(net, ops[i].in, sb)) {      // first fp8 conv of a chain: quantise its input here
-            const int rc = launch_quantize_fp8(c.ws + ti.offset, c.ws + net.tensors[ti.twin].offset, (size_t)sb * ti.H * ti.W * ti.C, ti.scale, stream);
-            if (rc) return rc;
-        }
-        tt_member(net, ops[i], sb, c.ws, tp.m[i]);
+        if (rc) return rc;
+        tt_member(net, ops[i], e.m[i], sb, c.ws, tp.m[i]);
     }
     if (!e.plan.n_wgs) {       // static per layout: uploaded by the first launch
         const int rc = tt_build_plan(net, tp.m, n, e.plan, stream);
@@ -283,7 +280,7 @@ int run_bblockx3(const sncal_hrnet& net, const Launch& e, const Call& c) {
     const Op& b = net.ops[e.op + 1];
     const Tensor& ti = net.tensors[a.in];
     const Tensor& to = net.tensors[b.out];
-    if (e.split_in) {         // (a helper in front of the launch: not what the profiling events time)
+    if (e.m[0].prep == PREP_SPLIT_F32) {         // (a helper in front of the launch: not what the profiling events time)
         LaunchEventsHold hold;
         const int rc = launch_split_f32(c.ws + ti.offset, c.ws + net.tensors[ti.twin].offset, (size_t)c.sb * ti.H * ti.W * ti.C, c.stream, net.d_range);
         if (rc) return rc;
@@ -292,8 +289,8 @@ int run_bblockx3(const sncal_hrnet& net, const Launch& e, const Call& c) {
     memset(&bp, 0, sizeof(bp));
     bp.range = net.d_range;
     bp.x = c.ws + net.tensors[ti.twin].offset;
-    bp.out_twin = e.m[1].twin ? c.ws + net.tensors[to.twin].offset : nullptr;
-    bp.out = e.m[1].f32 ? reinterpret_cast<float*>(c.ws + to.offset) : nullptr;
+    bp.out_twin = e.m[1].out.twin ? c.ws + net.tensors[to.twin].offset : nullptr;
+    bp.out = e.m[1].out.dense ? reinterpret_cast<float*>(c.ws + to.offset) : nullptr;
     bp.w1 = net.layers[a.conv].packed[PK_BBX3].p; bp.b1 = net.layers[a.conv].d_bias;
     bp.w2 = net.layers[b.conv].packed[PK_BBX3].p; bp.b2 = net.layers[b.conv].d_bias;
     bp.N = c.sb; bp.H = ti.H; bp.W = ti.W; bp.out_cstride = to.C; bp.out_coff = b.out_coff;
@@ -326,12 +323,12 @@ int run_upadd(const sncal_hrnet& net, const Launch& e, const Call& c) {
     for (int s = 0; s < op.nsrc; ++s) {
         const Tensor& ts = net.tensors[op.srcs[s]];
         p.src[s] = c.ws + ts.offset; p.Hs[s] = ts.H; p.Ws[s] = ts.W;
-        p.sy[s] = to.H > 1 ? (float)(ts.H - 1) / (float)(to.H - 1) : 0.f;
-        p.sx[s] = to.W > 1 ? (float)(ts.W - 1) / (float)(to.W - 1) : 0.f;
+        p.sy[s] = align_corners_ratio(ts.H, to.H);
+        p.sx[s] = align_corners_ratio(ts.W, to.W);
         C0 = ts.C;
     }
-    p.out = e.m[0].f32 ? c.ws + to.offset : nullptr;
-    p.out_twin = e.m[0].twin ? c.ws + net.tensors[to.twin].offset : nullptr;
+    p.out = e.m[0].out.dense ? c.ws + to.offset : nullptr;
+    p.out_twin = e.m[0].out.twin ? c.ws + net.tensors[to.twin].offset : nullptr;
     p.N = c.sb; p.H = to.H; p.W = to.W; p.C = C0;
     p.out_cstride = to.C; p.out_coff = op.out_coff; p.relu = op.relu ? 1 : 0;
     return launch_upsample_add(net.dtype, p, c.stream);
@@ -396,8 +393,7 @@ int run_taps(const sncal_hrnet& net, const Launch& e, const Call& c) {
             const Tensor& tt = net.tensors[tp.tensor];
             if (tt.first < 0) { set_error("sncal_hrnet_plan_tap: tensor %d is not allocated at this layout", tp.tensor); return SNCAL_ERR_STATE; }
             const void* src = tt.external_heat ? (const void*)c.heat : (const void*)(c.ws + tt.offset);
-            const size_t nb = (size_t)c.sb * tt.H * tt.W * tt.C * (tt.f32 ? 4 : tt.fp8 ? 1 : net.esize);
-            SNCAL_CHECK_HIP(hipMemcpyAsync(tp.dst, src, nb, hipMemcpyDeviceToDevice, c.stream));
+            SNCAL_CHECK_HIP(hipMemcpyAsync(tp.dst, src, tensor_bytes(net, tt, c.sb), hipMemcpyDeviceToDevice, c.stream));
         }
     return SNCAL_OK;
 }
@@ -776,8 +772,12 @@ extern "C" int sncal_hrnet_plan_op(const sncal_hrnet* net, int idx, sncal_plan_o
     out->launch = -1;
     for (const Schedule& s : net->schedules) {
         if (s.sb != net->lay_sb) continue;
-        for (size_t k = 0; k < s.launches.size(); ++k)
-            if (idx >= s.launches[k].op && idx < s.launches[k].op + s.launches[k].n) out->launch = (int)k;
+        for (size_t k = 0; k < s.launches.size(); ++k) {
+            const Launch& e = s.launches[k];
+            if (idx < e.op || idx >= e.op + e.n) continue;
+            const Member& m = e.m[idx - e.op];
+            out->launch = (int)k; out->writes_out = m.out.dense ? 1 : 0; out->writes_twin = m.out.twin ? 1 : 0; out->prep_in = (int)m.prep;
+        }
     }
     if (idx < (int)net->op_label.size()) snprintf(out->kernel, sizeof(out->kernel), "%s", net->op_label[idx].c_str());
     return SNCAL_OK;
@@ -793,7 +793,7 @@ extern "C" int sncal_hrnet_plan_tensor(const sncal_hrnet* net, int id, sncal_pla
     if (t.fp8)                      // the calibrated scale is kept on the bf16 tensor the twin belongs to
         for (const Tensor& o : net->tensors) if (o.twin == id) out->scale = o.scale;
     out->sub_batch = net->lay_sb;
-    out->bytes = (size_t)net->lay_sb * t.H * t.W * t.C * (t.f32 ? 4 : t.fp8 ? 1 : net->esize);
+    out->bytes = tensor_bytes(*net, t, net->lay_sb);
     out->offset = t.first >= 0 ? t.offset : 0; out->first = t.first; out->last = t.first >= 0 ? t.last : -1;
     return SNCAL_OK;
 }

@@ -26,8 +26,7 @@ int sncal::layout(sncal_hrnet& net, int sb, int H, int W) {
             // fp16x3: the fused split-arithmetic head (headx3.hip) when its gather boxes fit: branches 2 and 3 against the head's width
             // (the scales head_params will hand headx3_applies, before the tensors have their shapes)
             const int w2 = half(half(bw)), w3 = half(w2);
-            const float sx2 = sw > 1 ? (float)(w2 - 1) / (float)(sw - 1) : 0.f, sx3 = sw > 1 ? (float)(w3 - 1) / (float)(sw - 1) : 0.f;
-            net.use_fused = head_boxes_fit(sx2) && head_boxes_fit(sx3);
+            net.use_fused = head_boxes_fit(align_corners_ratio(w2, sw)) && head_boxes_fit(align_corners_ratio(w3, sw));
         }
         net.use_split = !net.use_fused && net.has_split && net.dtype == SNCAL_F32 && dims_ok;
     }
@@ -172,7 +171,7 @@ int sncal::layout(sncal_hrnet& net, int sb, int H, int W) {
     for (size_t i = 0; i < net.ops.size(); ++i) {
         for (size_t t = 0; t < T.size(); ++t)
             if (T[t].first == (int)i) {
-                T[t].bytes = (size_t)sb * T[t].H * T[t].W * T[t].C * (T[t].f32 ? 4 : T[t].fp8 ? 1 : net.esize);
+                T[t].bytes = tensor_bytes(net, T[t], sb);
                 T[t].offset = alloc(T[t].bytes);
             }
         for (size_t t = 0; t < T.size(); ++t)

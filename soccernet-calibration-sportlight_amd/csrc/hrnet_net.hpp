@@ -118,13 +118,17 @@ enum LaunchKind {
     LK_DECODE,       // keypoint decode (decode.hip)
 };
 enum DecodeAt { DEC_NONE, DEC_HEAD, DEC_TAIL };    // where the keypoint decode runs when a call wants keypoints only
+enum TwinBy : char { TW_NONE, TW_PRODUCER, TW_FRONT };     // who makes a tensor's twin: nobody (not alive), its producer's epilogue, a helper in front of each reader
+enum Prep : char { PREP_NONE, PREP_QUANT_FP8, PREP_SPLIT_F32 };     // the helper (quant.hip) that makes a member's input twin in front of the launch
+struct Forms { bool dense = true, twin = false; };         // what a launch writes of an op's output: the tensor itself, its twin
 
 struct Member {                     // what the schedule resolved for one op a launch covers
     const ConvVariant* v = nullptr; // generic kernel: variant, tile width factor, tiles, dynamic LDS bytes, LDS-transposed epilogue
     int twf = 1, tiles_x = 0, tiles_y = 0;
     size_t lds = 0;
     bool epi_lds = false;
-    bool twin = false, f32 = true;  // the launch writes the output's split twin / the output itself
+    Forms out;                      // the forms of the op's output that the launch writes (neither: it stays in LDS)
+    Prep prep = PREP_NONE;          // LK_TT, LK_BBLOCKX3: the helper in front of the launch for this op's input
 };
 struct TTPlanDev { TTItem* items = nullptr; uint32_t* first = nullptr; int n_wgs = 0; int lazy = 0; int cfg = 0; };
 struct Prof { std::string kernel; double flops = 0, bytes = 0; };
@@ -132,11 +136,15 @@ struct Launch {
     LaunchKind kind = LK_CONV;
     int op = 0, n = 1;              // covers the ops [op, op + n), all active
     Member m[3];
-    bool split_in = false;          // LK_BBLOCKX3: the input's split twin is made in front of the launch
     TTPlanDev plan;                 // LK_TT: work lists (cfg set by the schedule, uploaded by the first launch)
     Prof prof, prof_kp;             // profile row; LK_TAIL: prof_kp when the call wants keypoints only
 };
-struct Schedule { int sb = 0; DecodeAt dec = DEC_NONE; std::vector<Launch> launches; };
+struct Schedule {
+    int sb = 0;
+    DecodeAt dec = DEC_NONE;
+    std::vector<TwinBy> twin_by;    // per tensor: who makes its twin at this layout; every fusion predicate and member reads this
+    std::vector<Launch> launches;
+};
 
 }  // namespace sncal
 
@@ -234,6 +242,14 @@ inline bool op_active(const sncal_hrnet& net, const Op& op) {
     return op.group == GRP_ALL || op.group == head;
 }
 
+// bytes of sb frames of tensor t in its storage type
+inline size_t tensor_bytes(const sncal_hrnet& net, const Tensor& t, int sb) {
+    return (size_t)sb * t.H * t.W * t.C * (t.f32 ? 4 : t.fp8 ? 1 : net.esize);
+}
+
+// source step per destination pixel of an align_corners = True resize
+inline float align_corners_ratio(int src, int dst) { return dst > 1 ? (float)(src - 1) / (float)(dst - 1) : 0.f; }
+
 // ---- the stages: one unit each, what the others call of it, when it runs --------------------------------------------
 // hrnet_graph.cpp: the op graph of a network (sncal_hrnet_create)
 bool build_graph(sncal_hrnet& net);
@@ -246,8 +262,6 @@ int layout(sncal_hrnet& net, int sb, int H, int W);
 void drop_layout(sncal_hrnet& net);
 // hrnet_schedule.cpp: which kernel runs which ops (per layout and sub-batch size), and the predicates layout and launches share
 bool tt_eligible(const sncal_hrnet& net, const Op& op, int sb);
-bool twin_written_by_producer(const sncal_hrnet& net, int t, int sb);
-void tt_outputs(const sncal_hrnet& net, const Op& op, int sb, bool* out, bool* twin);
 void head_params(const sncal_hrnet& net, const Op& op, int sb, HeadParams& hp);
 int schedule_for(sncal_hrnet& net, int sb, Schedule** out);
 

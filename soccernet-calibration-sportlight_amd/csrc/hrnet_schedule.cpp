@@ -26,8 +26,10 @@ bool sncal::tt_eligible(const sncal_hrnet& net, const Op& op, int sb) {
     return in_bytes < (1u << 31) && out_elems < (1ull << 32) && L.packed[PK_TT].bytes < (1u << 31) && L.packed[PK_TT_FP8].bytes < (1u << 31);
 }
 
-// does the active op that produced tensor t write its e4m3 / split twin itself?
-bool sncal::twin_written_by_producer(const sncal_hrnet& net, int t, int sb) {
+namespace {
+
+// does the active op that produced tensor t write its e4m3 / split twin itself?  Asked once per tensor, by twin_table
+bool twin_written_by_producer(const sncal_hrnet& net, int t, int sb) {
     const int pi = t >= 0 && t < (int)net.producer.size() ? net.producer[t] : -1;
     if (pi < 0) return false;
     const Op& po = net.ops[pi];
@@ -42,13 +44,32 @@ bool sncal::twin_written_by_producer(const sncal_hrnet& net, int t, int sb) {
     return po.type == OP_CONV && net.layers[po.conv].fp8_on && tt_eligible(net, po, sb);
 }
 
-namespace {
+// Schedule::twin_by: for every tensor whose twin is alive at this layout, whether its producer's epilogue writes the twin or a helper
+// makes it in front of each launch that reads it
+void twin_table(const sncal_hrnet& net, int sb, std::vector<TwinBy>& by) {
+    by.assign(net.tensors.size(), TW_NONE);
+    for (size_t t = 0; t < net.tensors.size(); ++t) {
+        const int tw = net.tensors[t].twin;
+        if (tw >= 0 && net.tensors[tw].first >= 0) by[t] = twin_written_by_producer(net, (int)t, sb) ? TW_PRODUCER : TW_FRONT;
+    }
+}
 
-// bf16x3: does a generic producer (convolution / fuse sum) write the split twin of tensor t?
-bool writes_twin(const sncal_hrnet& net, int t, int sb) {
-    if (!net.x3 || t < 0) return false;
-    const Tensor& to = net.tensors[t];
-    return to.twin >= 0 && net.tensors[to.twin].first >= 0 && twin_written_by_producer(net, t, sb);
+// The forms of op's output that its launch writes.  Split engine: the twin when the table has the producer write it, the fp32 tensor when
+// there is no such twin or somebody reads the fp32 form.  e4m3 convolution (two-team kernel only): the twin whenever it is alive, the
+// bf16 tensor iff somebody reads it.  Everything else writes the tensor alone.
+Forms out_forms(const sncal_hrnet& net, const Schedule& s, const Op& op, LaunchKind kind) {
+    if (op.out < 0) return Forms{};
+    if (kind == LK_TT && net.layers[op.conv].fp8_on) return Forms{net.need_bf16[op.out] != 0, s.twin_by[op.out] != TW_NONE};
+    if (!net.x3) return Forms{};
+    const bool twin = s.twin_by[op.out] == TW_PRODUCER;
+    return Forms{!twin || net.need_bf16[op.out], twin};
+}
+
+// the helper in front of the launch of a reduced-precision convolution whose input twin no producer wrote
+Prep prep_in(const sncal_hrnet& net, const Schedule& s, const Op& op) {
+    const ConvLayer& L = net.layers[op.conv];
+    if (!(L.fp8_on || L.x3_on) || s.twin_by[op.in] != TW_FRONT) return PREP_NONE;
+    return L.fp8_on ? PREP_QUANT_FP8 : PREP_SPLIT_F32;
 }
 
 bool profile_detail() {          // tuning aid: one profile row per layer shape / two-team launch kind
@@ -109,10 +130,6 @@ int choose_conv(const sncal_hrnet& net, const Op& op, int sb, Member& m) {
         m.epi_lds = shape_ok && fits;
         if (m.epi_lds && need > m.lds) m.lds = need;
     }
-    if (net.x3) {            // bf16x3: the split twin for the two-team convolution that reads this output; fp32 only if somebody reads it
-        m.twin = writes_twin(net, op.out, sb);
-        m.f32 = !m.twin || net.need_bf16[op.out];
-    }
     return SNCAL_OK;
 }
 
@@ -152,7 +169,7 @@ int tt_cfg(const sncal_hrnet& net, const Op* ops, int n, int sb) {
 // ---- the schedule builder: fusion predicates, asked once per (layout, sub-batch size) --------------------------------
 
 // layer1 block 0's tail (bneckx3.hip): op i is the downsample branch, op i + 1 the conv3 that adds it
-bool fuses_bneck_tail(const sncal_hrnet& net, size_t i, int sb) {
+bool fuses_bneck_tail(const sncal_hrnet& net, const Schedule& s, size_t i) {
     const Op& op = net.ops[i];
     if (!(net.fuse_bneck & 2) || !net.x3 || op.relu || op.res >= 0 || op.out_f32 || op.out_coff != 0 || i + 1 >= net.ops.size() ||
         !net.layers[op.conv].packed[PK_BNP].p || net.layers[op.conv].cout != BNP_WIDE || net.layers[op.conv].x3_on || op.launch_group >= 0) return false;
@@ -162,12 +179,12 @@ bool fuses_bneck_tail(const sncal_hrnet& net, size_t i, int sb) {
            net.tensors[op.in].C == BNP_MID && net.tensors[nx.in].C == BNP_MID && net.tensors[nx.out].C == BNP_WIDE &&
            net.tensors[op.in].H == net.tensors[nx.in].H && net.tensors[op.in].W == net.tensors[nx.in].W &&
            net.tensors[op.out].last_read == (int)i + 1 &&      // nobody else reads the downsample branch
-           !writes_twin(net, nx.out, sb);
+           s.twin_by[nx.out] != TW_PRODUCER;                   // nobody is owed a split twin of the block output
 }
 
 // layer1 (bneckx3.hip): conv3 (+ residual, ReLU) of a Bottleneck and conv1 (+ ReLU) of the next one in one pass over the pixels: the
 // 256-channel tensor between them is written once (the next residual) and not read back
-bool fuses_bneck_seam(const sncal_hrnet& net, size_t i, int sb) {
+bool fuses_bneck_seam(const sncal_hrnet& net, const Schedule& s, size_t i) {
     const Op& op = net.ops[i];
     if (!(net.fuse_bneck & 1) || !net.x3 || !op.relu || op.res < 0 || op.out_f32 || op.out_coff != 0 || i + 1 >= net.ops.size() ||
         !net.layers[op.conv].packed[PK_BNP].p || net.layers[op.conv].cout != BNP_WIDE || net.layers[op.conv].x3_on) return false;
@@ -179,19 +196,20 @@ bool fuses_bneck_seam(const sncal_hrnet& net, size_t i, int sb) {
            nx.launch_group < 0 && net.layers[nx.conv].packed[PK_BNP].p && net.layers[nx.conv].cout == BNP_MID && !net.layers[nx.conv].x3_on &&
            t_in.C == BNP_MID && t_res.C == BNP_WIDE && t_y.C == BNP_WIDE && net.tensors[nx.out].C == BNP_MID &&
            t_res.H == t_y.H && t_res.W == t_y.W &&
-           !writes_twin(net, op.out, sb) && !writes_twin(net, nx.out, sb);      // neither output may owe somebody a split twin (they feed generic kernels)
+           s.twin_by[op.out] != TW_PRODUCER && s.twin_by[nx.out] != TW_PRODUCER;      // neither output may owe somebody a split twin (they feed generic kernels)
 }
 
 // bf16x3 engine, 48-channel BasicBlock: conv1 -> mid tile in LDS as hi / lo planes -> conv2 + residual (bblockx3.hip); the mid tensor and
 // its twin are not written at all
-bool fuses_bblockx3(const sncal_hrnet& net, size_t i, int sb) {
+bool fuses_bblockx3(const sncal_hrnet& net, const Schedule& s, size_t i) {
+    const int sb = s.sb;
     const Op& op = net.ops[i];
     if (!net.x3 || !op.relu || op.res >= 0 || op.out_f32 || i + 1 >= net.ops.size() || !net.layers[op.conv].x3_on ||
         !net.layers[op.conv].packed[PK_BBX3].p || !tt_eligible(net, op, sb)) return false;
     const Op& nx = net.ops[i + 1];
     return nx.type == OP_CONV && op_active(net, nx) && nx.in == op.out && nx.res == op.in && nx.relu && !nx.out_f32 && op.out_coff == 0 &&
            net.layers[nx.conv].x3_on && net.layers[nx.conv].packed[PK_BBX3].p && tt_eligible(net, nx, sb) && net.tensors[op.in].C == 48 &&
-           net.tensors[op.in].twin >= 0 && net.tensors[net.tensors[op.in].twin].first >= 0;
+           s.twin_by[op.in] != TW_NONE;
 }
 
 // bf16 engine, 48-channel BasicBlock: conv1 + conv2 (+ residual) fused when the next active op is its second convolution and both layers
@@ -279,9 +297,7 @@ void profile_launch(const sncal_hrnet& net, const Schedule& s, Launch& e) {
                        e.plan.cfg == 2 ? "conv_tt<" SNCAL_X3_NAME ",k3,s1,4x32x96>" : L0.x3_on ? "conv_tt<" SNCAL_X3_NAME ",k3,s1,8x32x96>" :
                        "conv_tt<bf16,k3,s1,8x32x96>";
             if (profile_detail()) {      // one profile row per launch kind
-                bool out = true, twin = false;
-                tt_outputs(net, op, sb, &out, &twin);
-                r.kernel += fmt("@%d members%s%s%s", e.n, op.res >= 0 ? "+res" : "", out ? "+f32" : "", twin ? "+twin" : "");
+                r.kernel += fmt("@%d members%s%s%s", e.n, op.res >= 0 ? "+res" : "", e.m[0].out.dense ? "+f32" : "", e.m[0].out.twin ? "+twin" : "");
             }
             break;
         }
@@ -299,7 +315,7 @@ void profile_launch(const sncal_hrnet& net, const Schedule& s, Launch& e) {
             const Tensor& ti = net.tensors[op.in];
             const double px = (double)sb * ti.H * ti.W;
             r.flops = 2.0 * 2.0 * px * 48 * 48 * 9;
-            if (e.kind == LK_BBLOCKX3) { r.kernel = "bblockx3_fused"; r.bytes = px * 48 * 4 * (1.0 + (e.m[1].twin ? 1.0 : 0.0) + (e.m[1].f32 ? 1.0 : 0.0)) + 2.0 * BBX_W_BYTES; }
+            if (e.kind == LK_BBLOCKX3) { r.kernel = "bblockx3_fused"; r.bytes = px * 48 * 4 * (1.0 + (e.m[1].out.twin ? 1.0 : 0.0) + (e.m[1].out.dense ? 1.0 : 0.0)) + 2.0 * BBX_W_BYTES; }
             else { r.kernel = "bblock48_fused"; r.bytes = 2.0 * px * 48 * 2 + 2.0 * 48 * 48 * 9 * 2; }
             break;
         }
@@ -365,6 +381,7 @@ DecodeAt decode_at(const sncal_hrnet& net, const Schedule& s) {
 // the op alone, on the two-team kernel when it is eligible.
 int build_schedule(const sncal_hrnet& net, int sb, Schedule& s) {
     s.sb = sb;
+    twin_table(net, sb, s.twin_by);
     for (size_t i = 0; i < net.ops.size();) {
         const Op& op = net.ops[i];
         if (!op_active(net, op)) { ++i; continue; }
@@ -380,15 +397,9 @@ int build_schedule(const sncal_hrnet& net, int sb, Schedule& s) {
                 int rc = plan_group(net, i, n, sb, e);
                 if (rc) return rc;
                 if (e.n > 1) break;
-                if (fuses_bneck_tail(net, i, sb)) { e.kind = LK_BNECK_TAIL; e.n = 2; }
-                else if (fuses_bneck_seam(net, i, sb)) { e.kind = LK_BNECK_SEAM; e.n = 2; }
-                else if (fuses_bblockx3(net, i, sb)) {
-                    const int out = net.ops[i + 1].out;
-                    e.kind = LK_BBLOCKX3; e.n = 2;
-                    e.split_in = !twin_written_by_producer(net, op.in, sb);      // the fp32 input's split twin, unless its producer wrote it
-                    e.m[1].twin = writes_twin(net, out, sb);
-                    e.m[1].f32 = !e.m[1].twin || net.need_bf16[out];
-                }
+                if (fuses_bneck_tail(net, s, i)) { e.kind = LK_BNECK_TAIL; e.n = 2; }
+                else if (fuses_bneck_seam(net, s, i)) { e.kind = LK_BNECK_SEAM; e.n = 2; }
+                else if (fuses_bblockx3(net, s, i)) { e.kind = LK_BBLOCKX3; e.n = 2; }
                 else if (fuses_bblock48(net, i)) { e.kind = LK_BBLOCK48; e.n = 2; }
                 else if (tt_eligible(net, op, sb)) { e.kind = LK_TT; e.plan.cfg = tt_cfg(net, &op, 1, sb); }
                 else {
@@ -398,15 +409,16 @@ int build_schedule(const sncal_hrnet& net, int sb, Schedule& s) {
                 }
                 break;
             }
-            case OP_UPADD:
-                e.kind = LK_UPADD;
-                e.m[0].twin = writes_twin(net, op.out, sb);
-                e.m[0].f32 = !e.m[0].twin || net.need_bf16[op.out];
-                break;
+            case OP_UPADD: e.kind = LK_UPADD; break;
             case OP_HEAD: e.kind = LK_HEAD; break;
             case OP_SOFTMAX: e.kind = LK_TAIL; break;
             case OP_DECODE: e.kind = LK_DECODE; break;
         }
+        for (int k = 0; k < e.n; ++k) {      // per covered op: the output forms this launch writes, the helper in front for its input twin
+            e.m[k].out = out_forms(net, s, net.ops[i + k], e.kind);
+            if (e.kind == LK_TT || e.kind == LK_BBLOCKX3) e.m[k].prep = prep_in(net, s, net.ops[i + k]);
+        }
+        if (e.kind == LK_BNECK_TAIL || e.kind == LK_BBLOCKX3 || e.kind == LK_BBLOCK48) e.m[0].out = Forms{false, false};      // stays in LDS
         i += e.n;
         s.launches.push_back(e);
     }
@@ -416,23 +428,6 @@ int build_schedule(const sncal_hrnet& net, int sb, Schedule& s) {
 }
 
 }  // namespace
-
-// which outputs a two-team member writes: the fp32 / bf16 tensor, its twin
-void sncal::tt_outputs(const sncal_hrnet& net, const Op& op, int sb, bool* out, bool* twin) {
-    const ConvLayer& L = net.layers[op.conv];
-    const Tensor& to = net.tensors[op.out];
-    const bool alive = to.twin >= 0 && net.tensors[to.twin].first >= 0;
-    *out = true;
-    *twin = false;
-    if (L.x3_on) {          // the split twin when a bf16x3 convolution reads this tensor next, the fp32 tensor when anybody else does
-        *twin = alive && twin_written_by_producer(net, op.out, sb);
-        *out = !*twin || net.need_bf16[op.out];
-    }
-    if (L.fp8_on) {         // bf16 if anybody reads it, twin if an fp8 conv follows
-        *twin = alive;
-        *out = net.need_bf16[op.out];
-    }
-}
 
 // the fused head's parameters that do not point into the workspace
 void sncal::head_params(const sncal_hrnet& net, const Op& op, int sb, HeadParams& hp) {
@@ -448,15 +443,15 @@ void sncal::head_params(const sncal_hrnet& net, const Op& op, int sb, HeadParams
     for (int s2 = 0; s2 < op.head_nsrc; ++s2) {
         const Tensor& ts = net.tensors[op.head_src[s2]];
         hp.Hs[s2] = ts.H; hp.Ws[s2] = ts.W;
-        hp.sy[s2] = to.H > 1 ? (float)(ts.H - 1) / (float)(to.H - 1) : 0.f;
-        hp.sx[s2] = to.W > 1 ? (float)(ts.W - 1) / (float)(to.W - 1) : 0.f;
+        hp.sy[s2] = align_corners_ratio(ts.H, to.H);
+        hp.sx[s2] = align_corners_ratio(ts.W, to.W);
     }
     hp.nfold = op.head_nfold; hp.ks1 = net.head_ks1;
     for (int s2 = 0; s2 < op.head_nfold; ++s2) {
         const Tensor& tf = net.tensors[op.head_fold[s2]];
         hp.Cf[s2] = tf.C; hp.Hf[s2] = tf.H; hp.Wf[s2] = tf.W;
-        hp.fsy[s2] = to.H > 1 ? (float)(tf.H - 1) / (float)(to.H - 1) : 0.f;
-        hp.fsx[s2] = to.W > 1 ? (float)(tf.W - 1) / (float)(to.W - 1) : 0.f;
+        hp.fsy[s2] = align_corners_ratio(tf.H, to.H);
+        hp.fsx[s2] = align_corners_ratio(tf.W, to.W);
     }
     hp.N = sb; hp.H = to.H; hp.W = to.W; hp.HP = net.head_hp; hp.NQ = net.head_hp / 32; hp.LC = to.C;
 }

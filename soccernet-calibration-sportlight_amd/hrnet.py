@@ -304,7 +304,8 @@ class HRNetHeatmap:
 
     def plan_ops(self):
         """The executor's op list at the current layout (valid after a forward / workspace query): list of dicts.  `launch`: index of the
-        launch that covers the op in the schedule of the layout's own sub-batch size (-1: inactive)."""
+        launch that covers the op in the schedule of the layout's own sub-batch size (-1: inactive); `writes_out` / `writes_twin`: that
+        launch writes the dense form / the twin of `out`; `prep_in`: 0 none, 1 quantize_fp8, 2 split_f32 in front of it for `in`."""
         out = []
         po = _lib.PlanOp()
         for i in range(self._L.sncal_hrnet_plan_num_ops(self._h)):
@@ -315,7 +316,7 @@ class HRNetHeatmap:
                             head_direct=po.head_direct, head_src=list(po.head_src)[:po.head_nsrc],
                             head_fold=list(po.head_fold)[:po.head_nfold], relu=bool(po.relu), out_coff=po.out_coff,
                             out_f32=bool(po.out_f32), fp8=po.fp8 == 1, x3=po.fp8 == 2, x3g=po.fp8 == 3, res_twin=bool(po.res_twin), kernel=po.kernel.decode(),
-                            launch=po.launch))
+                            launch=po.launch, writes_out=bool(po.writes_out), writes_twin=bool(po.writes_twin), prep_in=po.prep_in))
         return out
 
     def plan_tensor(self, tid):

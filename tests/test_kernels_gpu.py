@@ -271,11 +271,11 @@ def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag='', net=Non
                 to = net.plan_tensor(nxt['out'])
                 name = f"{op['name']} + conv2 {to['H']}x{to['W']} 48->48->48"
                 checked = False
-                if to['alive'] and _bf16_written(net, ops, nxt):
+                if to['alive'] and nxt['writes_out']:
                     got = nchw(taps[(nxt['idx'], nxt['out'])])[:, nxt['out_coff']:nxt['out_coff'] + 48]
                     check(name, got, y, rel_out, abs_out + slack, stats, 'bblockx3_fused')
                     checked = True
-                if to['twin'] >= 0 and net.plan_tensor(to['twin'])['alive'] and (nxt['idx'], to['twin']) in taps:
+                if nxt['writes_twin']:
                     check(name + ' [split twin out]', _split_twin_value(taps[(nxt['idx'], to['twin'])]), y, 1e-5 + 2.0 ** -16, abs_out + slack, stats, 'bblockx3_fused split out')
                     checked = True
                 assert checked, name
@@ -335,25 +335,25 @@ def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag='', net=Non
             kern = 'conv_tt<fp8,k3,s1,8x32x96>' if op['fp8'] else ('conv_tt<fp16x3,k3,s1,12x32x64>' if op['cout'] % 96 else 'conv_tt<fp16x3,k3,s1,8x32x96>') if op.get('x3') else label
             name = f"{op['name']} {to['H']}x{to['W']} {op['cin']}->{op['cout']}" + ('+res' if op['res'] >= 0 else '')
             checked = False
-            gen_twin = bool(op.get('x3g')) and _producer_twin(net, op, taps)
+            gen_twin = bool(op.get('x3g')) and op['writes_twin']
             if gen_twin:
                 check(name + ' [split twin out]', _split_twin_value(T(op, to['twin'])), y, 1e-5 + 2.0 ** -16, abs_out + fp8_slack, stats, kern + ' split out')
                 checked = True
-            if to['alive'] and not ((op['fp8'] or op.get('x3') or gen_twin) and not _bf16_written(net, ops, op)):
+            if to['alive'] and op['writes_out']:
                 got = nchw(T(op, op['out']))[:, op['out_coff']:op['out_coff'] + op['cout']]
                 if op['out_f32']:
                     check(name, got, y, 1e-5 if f32_engine else 2.0 ** -9, abs_out, stats, kern)     # fp32 logits of bf16 operands
                 else:
                     check(name, got, y, rel_out, abs_out + fp8_slack, stats, kern)
                 checked = True
-            if op.get('x3') and to['twin'] >= 0 and net.plan_tensor(to['twin'])['alive'] and (op['idx'], to['twin']) in taps:
+            if op.get('x3') and op['writes_twin']:
                 # split twin written by the epilogue: [16 hi | 16 lo] bf16 per 16-channel group; hi + lo reproduces y to 2^-17
                 raw = T(op, to['twin'])                                                  # fp32-typed storage, (N,H,W,C)
                 pr = raw.view(X3_T).reshape(raw.shape[0], raw.shape[1], raw.shape[2], raw.shape[3] // 16, 2, 16).to(torch.float32)
                 got_t = (pr[..., 0, :] + pr[..., 1, :]).reshape(raw.shape).permute(0, 3, 1, 2)
                 check(name + ' [split twin out]', got_t, y, 1e-5 + 2.0 ** -16, abs_out + fp8_slack, stats, kern + ' split out')
                 checked = True
-            if op['fp8'] and to['twin'] >= 0 and net.plan_tensor(to['twin'])['alive']:
+            if op['fp8'] and op['writes_twin']:
                 tw_o = net.plan_tensor(to['twin'])
                 got8 = e4m3_decode(T(op, to['twin'])).permute(0, 3, 1, 2) * tw_o['scale']
                 ref8 = e4m3_round(bf16r(y) / tw_o['scale']) * tw_o['scale']
@@ -375,10 +375,10 @@ def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag='', net=Non
             if op['relu']:
                 acc = torch.relu(acc)
             nm = f"fuse sum -> {to['H']}x{to['W']}x{C0} ({len(op['src'])} sources)"
-            tw = dtype == 'fp16x3' and _producer_twin(net, op, taps)
+            tw = op['writes_twin']
             if tw:          # fp16x3: the sum's split twin for the two-team convolution that reads it; the fp32 form only if somebody reads that
                 check(nm + ' [split twin out]', _split_twin_value(T(op, to['twin'])).permute(0, 2, 3, 1), acc, 1e-5 + 2.0 ** -16, abs_out, stats, 'upsample_add split out')
-            if not tw or _bf16_written(net, ops, op):
+            if op['writes_out']:
                 got = T(op, op['out']).to(torch.float32)[..., op['out_coff']:op['out_coff'] + C0]
                 check(nm, got, acc, rel_out, abs_out, stats, 'upsample_add')
         elif op['type'] == 'head':
@@ -391,7 +391,7 @@ def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag='', net=Non
             lg = logits[..., :C].permute(0, 3, 1, 2)
             ref = torch.softmax(lg, dim=1) if net.cfg.get('head') == 'softmax' else torch.log_softmax(lg, dim=1)
             check('softmax head', got, ref, 1e-5, 1e-5, stats, 'softmax_nchw')
-    pairs, skipped = producer_reader_identity(net, ops, taps, dtype)
+    pairs, skipped = producer_reader_identity(net, ops, taps)
     twins = twin_value_identity(net, ops, taps, dtype, stats, skipped)
     stats['_case'] = dict(tag=tag, dtype=dtype, fp8_layers=fp8_layers, frames=int(B), input=list(x.shape[2:]),
                           reader_pairs=pairs, lds_intermediates=len(skipped), **twins)
@@ -403,29 +403,15 @@ FUSED_PAIR_KERNELS = ('bblock48_fused', 'bblockx3_fused', 'bneck_tail_ds_x3')   
 X3_ENGINES = ('fp16x3', 'bf16x3', 'x3')
 
 
-def _twin_by_producer(net, po, dtype):
-    """Does op `po` write the e4m3 / split twin of its output itself?  (hrnet_schedule.cpp twin_written_by_producer; otherwise a
-    quantise / split helper makes the twin in front of every launch that reads it.)"""
-    to = net.plan_tensor(po['out'])
-    if po['type'] == 'conv' and po['fp8']:
-        return True
-    if po['type'] == 'conv' and po.get('x3'):
-        return po['out_coff'] == 0 and to['C'] == po['cout']
-    if dtype in X3_ENGINES and po['type'] == 'conv' and po.get('x3g'):
-        return po['out_coff'] == 0 and not po['out_f32'] and to['C'] == po['cout'] and po['cout'] % 16 == 0
-    if dtype in X3_ENGINES and po['type'] == 'upsample_add':
-        return po['out_coff'] == 0 and to['C'] % 16 == 0
-    return False
-
-
-def _real_reads(net, o, producers, dtype):
+def _real_reads(net, o):
     """Tensor ids the launch of op `o` really reads for it: the twin in place of `in` for the e4m3 / split two-team convolutions (and
-    `in` itself beside it when the helper in front of the launch has to make the twin), the twin in place of `res` for res_twin."""
+    `in` itself beside it when the schedule puts a helper in front of the launch to make the twin: prep_in), the twin in place of `res`
+    for res_twin."""
     r = []
     if o['in'] >= 0:
         if o['type'] == 'conv' and (o['fp8'] or o.get('x3')):
             r.append(net.plan_tensor(o['in'])['twin'])
-            if not _twin_by_producer(net, producers[o['in']][0], dtype):
+            if o['prep_in']:
                 r.append(o['in'])
         else:
             r.append(o['in'])
@@ -439,7 +425,7 @@ def _bits(t):
     return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()])
 
 
-def producer_reader_identity(net, ops, taps, dtype):
+def producer_reader_identity(net, ops, taps):
     """The per-launch checks above recompute a launch from the operands it READ; a launch in between that clobbered a live tensor would
     hand the reader clobbered operands and pass.  So: for every allocated tensor and twin, the tap taken at its producing op equals, byte
     for byte, the tap taken at every later op that really reads it (last reader included); concat tensors per producer slice, from that
@@ -457,7 +443,7 @@ def producer_reader_identity(net, ops, taps, dtype):
             twin_of[tw] = t
     readers = {}
     for o in act:
-        for t in _real_reads(net, o, producers, dtype):
+        for t in _real_reads(net, o):
             assert net.plan_tensor(t)['alive'], (o['idx'], t)
             readers.setdefault(t, []).append(o)
     for t in readers:
@@ -474,15 +460,16 @@ def producer_reader_identity(net, ops, taps, dtype):
         if o['kernel'] in FUSED_PAIR_KERNELS:
             nxt = by_idx[o['idx'] + 1]
             assert nxt['launch'] == o['launch'], (o['idx'], o['kernel'])
-            expected |= {t for t in _real_reads(net, nxt, producers, dtype) if twin_of.get(t, t) == o['out']}
+            expected |= {t for t in _real_reads(net, nxt) if twin_of.get(t, t) == o['out']}
     assert skipped == expected, f'tensors without a writer {sorted(skipped)} != intermediates of the fused pairs {sorted(expected)}'
     pairs = 0
     for t, rs in readers.items():
         if t in skipped:
             continue
         base = twin_of.get(t, t)
-        in_front = t in twin_of and not _twin_by_producer(net, producers[base][0], dtype)
+        in_front = t in twin_of and not any(p['writes_twin'] for p in producers[base])
         # (a twin its producer does not write is made in front of each reading launch, from the tensor -- itself compared as `base`)
+        assert not in_front or rs[0]['prep_in'], f"twin {t} of tensor {base}: no producer writes it and op {rs[0]['idx']} reads it with no helper in front"
         writers = [rs[0]] if in_front else producers[base]
         for p in writers:
             lo, hi = 0, taps[(p['idx'], t)].shape[-1]
@@ -511,12 +498,12 @@ QUANTIZE_GRID_ELEMENTS = 2048 * 256 * 8          # quant.hip: elements one trip 
                                                  # takes the grid-stride loop round a second time (split_f32_kernel: 4096 * 256 * 8)
 
 
-def twin_plan(net, ops, dtype, skipped):
+def twin_plan(net, ops, skipped):
     """From the plan alone (no taps): [(kind 'fp8' | 'x3', where 'front' | 'both', op, tensor id, twin id)].
     'front': the launch of `op` reads a twin its producer did not write, so quantize_fp8_kernel / split_f32_kernel makes it from the
-    dense tensor in front of that launch (hrnet.cpp run_tt / run_bblockx3).  'both': `op` writes its output AND the output's twin
-    (hrnet_schedule.cpp tt_outputs, writes_twin: the twin when a reduced-precision convolution reads it, the dense form when anybody else
-    does).  The intermediates of the fused pairs (`skipped`) live in LDS and have neither form."""
+    dense tensor in front of that launch (the op's prep_in).  'both': `op` writes its output AND the output's twin (its writes_out and
+    writes_twin: the twin when a reduced-precision convolution reads it, the dense form when anybody else does).  The intermediates of
+    the fused pairs (`skipped`) live in LDS and have neither form."""
     act = [o for o in ops if o['active'] and o['type'] != 'decode']
     producers = {}
     for o in act:
@@ -529,7 +516,8 @@ def twin_plan(net, ops, dtype, skipped):
             if tw in skipped or o['in'] in skipped:
                 continue
             assert tw >= 0 and net.plan_tensor(tw)['alive'], (o['idx'], o['in'], tw)
-            if not _twin_by_producer(net, producers[o['in']][0], dtype):
+            if o['prep_in']:
+                assert o['prep_in'] == (1 if o['fp8'] else 2), (o['idx'], o['prep_in'])
                 plan.append(('fp8' if o['fp8'] else 'x3', 'front', o, o['in'], tw))
     for t, ps in producers.items():
         to = net.plan_tensor(t)
@@ -537,7 +525,7 @@ def twin_plan(net, ops, dtype, skipped):
         if tw < 0 or not net.plan_tensor(tw)['alive'] or t in skipped or tw in skipped or len(ps) != 1:
             continue
         p = ps[0]
-        if _twin_by_producer(net, p, dtype) and to['alive'] and _bf16_written(net, ops, p):
+        if p['writes_twin'] and to['alive'] and p['writes_out']:
             plan.append(('fp8' if p['type'] == 'conv' and p['fp8'] else 'x3', 'both', p, t, tw))
     return plan
 
@@ -559,7 +547,7 @@ def twin_value_identity(net, ops, taps, dtype, stats, skipped=()):
     that has twins: the four of TWIN_ROWS (ops = pairs, sites = pairs per kernel label).  Returns the counts for stats['_case'], with the
     largest tensor a helper converted in front of a launch (its capped grid-stride loop, QUANTIZE_GRID_ELEMENTS)."""
     import handoff_ref as hr
-    plan = twin_plan(net, ops, dtype, skipped)
+    plan = twin_plan(net, ops, skipped)
     largest = {'fp8': 0, 'x3': 0}
     rows = {}
     labels = {o['launch']: o['kernel'] for o in ops if o['active'] and o['kernel']}      # (grouped / fused members carry no label of their own)
@@ -609,28 +597,6 @@ def _split_twin_value(raw):
     """(N,H,W,C) fp32-typed storage of a split twin -> (N,C,H,W) fp32: hi + lo."""
     pr = raw.view(X3_T).reshape(raw.shape[0], raw.shape[1], raw.shape[2], raw.shape[3] // 16, 2, 16).to(torch.float32)
     return (pr[..., 0, :] + pr[..., 1, :]).reshape(raw.shape).permute(0, 3, 1, 2)
-
-
-def _producer_twin(net, op, taps):
-    """fp16x3: does this generic convolution / fuse sum write the split twin of its (dense) output?  (hrnet_schedule.cpp writes_twin)"""
-    to = net.plan_tensor(op['out'])
-    if to['twin'] < 0 or not net.plan_tensor(to['twin'])['alive'] or (op['idx'], to['twin']) not in taps:
-        return False
-    return op['out_coff'] == 0 and to['C'] % 16 == 0 and (op['type'] == 'upsample_add' or (op.get('x3g') and to['C'] == op['cout'] and not op['out_f32']))
-
-
-def _bf16_written(net, ops, op):
-    """An fp8 convolution writes its bf16 output only when somebody reads it (residuals, fuse layers, bf16 convolutions)."""
-    t = op['out']
-    for o in ops:
-        if not o['active'] or o['idx'] <= op['idx']:
-            continue
-        readers = [-1 if o.get('res_twin') else o['res'], o['base'], o['head_direct']] + o['src'] + o['head_src'] + o['head_fold']
-        if t in readers:
-            return True
-        if o['in'] == t and not (o['type'] == 'conv' and (o['fp8'] or o.get('x3'))):
-            return True
-    return False
 
 
 def head_reference(net, op, T, W, by_idx, stats, dev, exact=False):
@@ -699,9 +665,9 @@ def _twin_rows(stats, *rows):
 
 FP8_TWIN_ROWS = ('quantize_fp8 in front', 'e4m3 twin = q(dense)')
 # The split engine's producers -- the two-team and generic convolutions, bblockx3, the fuse sums -- write every twin a stock network
-# (W18 / W32 / W48, line network; 140p .. 1080p) reads, so NO launch of such a plan has split_f32_kernel in front (twin_plan finds none,
-# and producer_reader_identity would fail on a twin the plan held for producer-written that a helper made later): the row is reported,
-# with compared == expected == 0, and nothing is asserted about a path the engine does not take.
+# (W18 / W32 / W48, line network; 140p .. 1080p) reads, so NO launch of such a plan has split_f32_kernel in front (no op reports prep_in == 2:
+# tests/test_workspace_gpu.py _audit_forms asserts it over every audited layout): the row is reported, with compared == expected == 0, and
+# nothing is asserted about a path the engine does not take.
 X3_TWIN_ROWS = ('split twin = split(dense)',)
 
 

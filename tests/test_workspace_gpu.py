@@ -8,7 +8,8 @@ this file checks what no single launch shows.  Every assertion is bit-exact equa
   2a  the bytes the workspace held before a forward do not show in its results (nobody reads memory nobody wrote);
   2b  a ragged last sub-batch -- another schedule over the layout of the full sub-batch -- equals the same frames alone;
   2c  one handle driven through different shapes, outputs, input types, fp8 selections, taps and profiling modes equals fresh handles;
-  3   a static audit of the planner over many shapes: two tensors that share bytes are never live in the same launch.
+  3   a static audit of the planner over many shapes: two tensors that share bytes are never live in the same launch, and the forms the
+      schedule reports per op (dense output, twin, helper in front) supply every reader of the op graph exactly once.
 """
 import ctypes
 import functools
@@ -296,7 +297,7 @@ class _Plan:
         for i in range(self.n_ops):
             assert L.sncal_hrnet_plan_op(h, i, rpo) == 0
             if po.active:
-                dyn.append((i, po.launch, po.fp8, po.res_twin))
+                dyn.append((i, po.launch, po.fp8, po.res_twin, po.writes_out, po.writes_twin, po.prep_in))
         tens = np.zeros((self.n_t, 6), dtype=np.int64)           # alive, offset, bytes, twin, first, last
         for t in range(self.n_t):
             assert L.sncal_hrnet_plan_tensor(h, t, rpt) == 0
@@ -317,7 +318,7 @@ def _audit_layout(plan, ws_bytes, what, tamper=None):
     lo = np.full(n_t, -1, dtype=np.int64)
     hi = np.full(n_t, -1, dtype=np.int64)
     by_launch = {}
-    for i, launch, fp8, res_twin in dyn:
+    for i, launch, fp8, res_twin, *_ in dyn:
         assert launch >= 0, f'{what}: active op {i} is covered by no launch'
         by_launch.setdefault(launch, []).append((i, fp8, res_twin))
     for launch in sorted(by_launch):
@@ -357,6 +358,66 @@ def _audit_layout(plan, ws_bytes, what, tamper=None):
         raise AssertionError(f'{what}: {len(clash)} pairs of tensors share bytes while both live; first: tensor {a} [{off[a]}, {off[a] + nbytes[a]}) '
                              f'launches {lo[a]}..{hi[a]} (allocator ops {tens[a, 4]}..{tens[a, 5]}) and tensor {b} [{off[b]}, {off[b] + nbytes[b]}) '
                              f'launches {lo[b]}..{hi[b]} (allocator ops {tens[b, 4]}..{tens[b, 5]})')
+    _audit_forms(plan, dyn, alive, twin, what)
+
+
+def _audit_forms(plan, dyn, alive, twin, what):
+    """The forms the schedule reports per op -- writes_out, writes_twin, prep_in (include/sncal.h) -- against the op graph alone.  A reduced-
+    precision convolution (fp8 field 1 / 2) reads the twin of `in`, a res_twin convolution the twin of `res`, everybody else the dense
+    tensors.  A read inside the launch that produces the tensor (a fused pair's intermediate) needs no form at all.
+      1  a twin that is read was written by an earlier launch, or made by a helper in front of that launch or an earlier one (a dense
+         tensor that is read has an earlier writer: _audit_layout; that the writer wrote the dense form: 4);
+      2  for every twin read by another launch, exactly one of: a producer of the tensor reports writes_twin, EVERY launch reading it as
+         `in` reports prep_in -- never both;
+      3  an op that writes neither form is the first op of a two-op launch whose second op reads its output;
+      4  every producer of a tensor reports writes_out when a later launch reads the dense form;
+      5  no launch of a stock network has split_f32 in front (prep_in == 2): the split engine's producers write every twin."""
+    producers, in_readers, members = {}, {}, {}
+    for d in dyn:
+        i, launch, fp8 = d[:3]
+        typ, t_in, _, t_out, _ = plan.static[i]
+        members.setdefault(launch, []).append(i)
+        if t_out >= 0:
+            producers.setdefault(t_out, []).append(d)
+        if typ == 1 and fp8 in (1, 2) and t_in >= 0 and twin[t_in] >= 0:
+            in_readers.setdefault(t_in, []).append(d)
+
+    def local(t, launch):
+        return any(p[1] == launch for p in producers.get(t, ()))
+
+    for t, rs in in_readers.items():                                                                  # 2
+        rs = [r for r in rs if not local(t, r[1])]
+        by_producer = any(p[5] for p in producers.get(t, ()))
+        front = [r[0] for r in rs if r[6]]
+        assert not (by_producer and front), f'{what}: twin of tensor {t}: both written by its producer and made in front of op(s) {front}'
+        assert by_producer or len(front) == len(rs), \
+            f'{what}: twin of tensor {t}: its producer does not write it and no helper makes it in front of op(s) {[r[0] for r in rs if not r[6]]}'
+    for i, launch, fp8, res_twin, w_out, w_twin, prep in dyn:
+        typ, t_in, t_res, t_out, reads = plan.static[i]
+        dense, twins = list(reads), []
+        if typ == 1 and fp8 in (1, 2) and t_in >= 0 and twin[t_in] >= 0 and not prep:      # (with a helper in front: `in` itself, dense)
+            dense.remove(t_in)
+            twins.append(t_in)
+        if res_twin:
+            dense.remove(t_res)
+            twins.append(t_res)
+        for t in twins:                                                                               # 1
+            assert local(t, launch) or any(p[5] and p[1] < launch for p in producers.get(t, ())) or \
+                any(r[6] and r[1] <= launch for r in in_readers.get(t, ())), \
+                f'{what}: op {i} (launch {launch}) reads the twin of tensor {t}, which no earlier launch wrote and no helper made'
+        for t in dense:                                                                               # 4
+            for p in producers.get(t, ()):
+                assert p[1] >= launch or p[4], f'{what}: op {p[0]} does not write tensor {t} in dense form, which op {i} (launch {launch}) reads'
+        if w_twin:
+            assert t_out >= 0 and twin[t_out] >= 0 and alive[twin[t_out]], f'{what}: op {i} writes the twin of tensor {t_out}, which is not allocated'
+    for i, launch, _, _, w_out, w_twin, _ in dyn:                                                     # 3
+        t_out = plan.static[i][3]
+        if t_out >= 0 and not w_out and not w_twin:
+            pair = members[launch]
+            assert len(pair) == 2 and pair[0] == i and t_out in plan.static[pair[1]][4], \
+                f'{what}: op {i} writes neither form of tensor {t_out} and is not the first op of a fused pair that reads it'
+    split_front = [d[0] for d in dyn if d[6] == 2]                                                    # 5
+    assert not split_front, f'{what}: split_f32 in front of op(s) {split_front}: a stock network has none'
 
 
 def _audit(net, what):
@@ -386,7 +447,7 @@ def test_the_audit_reports_what_a_wrong_planner_would_do(sncal, cuda, cfg_name, 
     _audit_layout(plan, ws_bytes, 'untouched')
     dyn, _ = plan.read()
     by_launch = {}
-    for i, launch, _, _ in dyn:
+    for i, launch, *_ in dyn:
         by_launch.setdefault(launch, []).append(i)
     fused = [ops for ops in by_launch.values() if len(ops) == 2 and plan.static[ops[0]][3] in plan.static[ops[1]][4]]
     grouped = [ops for ops in by_launch.values() if len(ops) >= 2 and plan.static[ops[0]][3] not in plan.static[ops[1]][4]]
@@ -407,6 +468,31 @@ def test_the_audit_reports_what_a_wrong_planner_would_do(sncal, cuda, cfg_name, 
 
     with pytest.raises(AssertionError, match='end beyond'):
         _audit_layout(plan, ws_bytes, 'tampered', beyond)
+
+    def setting(k, field, value):                       # row k of the plan's per-op report with one field edited
+        def tamper(dyn, tens):
+            row = list(dyn[k])
+            row[field] = value
+            dyn[k] = tuple(row)
+        return tamper
+
+    W_OUT, W_TWIN, PREP = 4, 5, 6
+    row_of_out = {plan.static[d[0]][3]: k for k, d in enumerate(dyn)}
+    dense_read = [row_of_out[t] for d in dyn for t in plan.static[d[0]][4]
+                  if not (d[2] in (1, 2) and t == plan.static[d[0]][1]) and not (d[3] and t == plan.static[d[0]][2])
+                  and t in row_of_out and dyn[row_of_out[t]][1] < d[1]]
+    assert dense_read and dyn[dense_read[0]][W_OUT]
+    with pytest.raises(AssertionError, match='does not write tensor .* in dense form'):
+        _audit_layout(plan, ws_bytes, 'tampered', setting(dense_read[0], W_OUT, 0))
+    if dtype == 'fp16x3':                               # (the bf16 engine has no twins)
+        handed = [(row_of_out[plan.static[d[0]][1]], k) for k, d in enumerate(dyn)
+                  if d[2] == 2 and dyn[row_of_out[plan.static[d[0]][1]]][W_TWIN] and dyn[row_of_out[plan.static[d[0]][1]]][1] < d[1]]
+        assert handed
+        producer, reader = handed[0]
+        with pytest.raises(AssertionError, match='its producer does not write it'):
+            _audit_layout(plan, ws_bytes, 'tampered', setting(producer, W_TWIN, 0))
+        with pytest.raises(AssertionError, match='both written by its producer'):
+            _audit_layout(plan, ws_bytes, 'tampered', setting(reader, PREP, 2))
 
 
 _AUDIT_CASES = [(c, d, e) for c, d in ENGINES for e in AUDIT_ENV]
