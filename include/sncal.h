@@ -386,6 +386,12 @@ int sncal_evaluate_cameras_detail(const sncal_camera* d_cams, int B, const doubl
  * restart intervals.  Progressive / arithmetic / CMYK / 4:4:0 / multi-scan -> SNCAL_ERR_UNSUPPORTED; damaged
  * streams -> SNCAL_ERR_ARG; the message names the frame.  A file whose EXIF orientation tag asks for a rotation / flip (cv2.imread applies it)
  * -> SNCAL_ERR_UNSUPPORTED as well: the decoder never returns pixels cv2.imread would not.
+ * Scaled decode (sncal_jpeg_create_scaled, scale_denom d = 2, 4, 8): libjpeg's own scale_num / scale_denom = 1 / d with every
+ * other default kept, i.e. the array cv2.imread(path, cv2.IMREAD_REDUCED_COLOR_2 / _4 / _8) returns, ceil(H / d) x ceil(W / d).
+ * The frame is shrunk in the DCT domain (jidctred.c: 4x4, 2x2, 1x1 inverse transforms of the same coefficients; jdmaster.c
+ * transforms the chroma of a subsampled frame one size larger instead of upsampling it; jdsample.c upsamples what is left, with
+ * the triangle filter at 1/2 and 1/4 and by replication at 1/8) and is bit-exact as well.  It is NOT cv2.resize of the full
+ * decode.  The host stage is the same at every scale (libjpeg entropy-decodes everything too); the device stage shrinks.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct sncal_jpeg sncal_jpeg;
 typedef struct {
@@ -407,9 +413,21 @@ int sncal_jpeg_entropy_decode(const unsigned char* data, size_t len, int16_t* co
  * into one tensor, make_submit.py:63).  n_threads host workers for the entropy decode (0 = hardware concurrency,
  * capped at 32).  Owns pinned staging (double-buffered) and the device coefficient / sample-plane buffers. */
 int sncal_jpeg_create(int max_batch, int height, int width, int n_threads, sncal_jpeg** out);
+/* The same for frames of height x width SOURCE pixels decoded at 1 / scale_denom (1, 2, 4 or 8; anything else is
+ * SNCAL_ERR_ARG).  sncal_jpeg_create is exactly scale_denom = 1. */
+int sncal_jpeg_create_scaled(int max_batch, int height, int width, int scale_denom, int n_threads, sncal_jpeg** out);
 void sncal_jpeg_destroy(sncal_jpeg* dec);
-/* data[b], len[b]: host pointers to B encoded frames.  d_bgr: (B,height,width,3) uint8 on the device.  The host
- * part runs inside the call; the copy and the two kernels are enqueued on `stream`. */
+/* Size of the frames the decoder writes: ceil(height / scale_denom) x ceil(width / scale_denom). */
+int sncal_jpeg_output_size(const sncal_jpeg* dec, int* out_h, int* out_w);
+/* Host only: the plan of a scaled decode for one header (the one the decoder itself follows).  out_hw = {height, width} of
+ * the decoded frame; per component c < info->components: comp_block[c] the side of its inverse transform (8, 4, 2, 1),
+ * comp_hw[c] = {height, width} of its sample plane, comp_up[c] = {vertical, horizontal} upsampling left to do (1 or 2).
+ * Entries of absent components are 0. */
+int sncal_jpeg_scaled_layout(const sncal_jpeg_info* info, int scale_denom, int32_t out_hw[2], int32_t comp_block[3],
+                             int32_t comp_hw[3][2], int32_t comp_up[3][2]);
+/* data[b], len[b]: host pointers to B encoded frames.  d_bgr: (B,out_h,out_w,3) uint8 on the device (the source size at
+ * scale 1).  A frame whose SOURCE size is not the decoder's is refused.  The host part runs inside the call; the copy and
+ * the two kernels are enqueued on `stream`. */
 int sncal_jpeg_decode(sncal_jpeg* dec, const unsigned char* const* data, const size_t* len, int B,
                       unsigned char* d_bgr, void* stream);
 

@@ -132,6 +132,12 @@ SIGNATURES = {
     'sncal_jpeg_probe': (ctypes.c_int, [vp, ctypes.c_size_t, ctypes.POINTER(JpegInfo)]),
     'sncal_jpeg_entropy_decode': (ctypes.c_int, [vp, ctypes.c_size_t, vp, ctypes.c_size_t, ctypes.POINTER(JpegInfo)]),
     'sncal_jpeg_create': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]),
+    'sncal_jpeg_create_scaled': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.POINTER(vp)]),
+    'sncal_jpeg_output_size': (ctypes.c_int, [vp, c_int_p, c_int_p]),
+    'sncal_jpeg_scaled_layout': (ctypes.c_int, [ctypes.POINTER(JpegInfo), ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
+                                                ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                                ctypes.POINTER(ctypes.c_int32)]),
     'sncal_jpeg_destroy': (None, [vp]),
     'sncal_jpeg_decode': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_size_t),
                                          ctypes.c_int, vp, vp]),

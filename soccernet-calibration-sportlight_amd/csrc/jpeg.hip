@@ -10,6 +10,10 @@
 //          jpeg_colour_kernel  jdsample.c h2v2 / h2v1 fancy upsampling (triangle filter with libjpeg's alternating
 //                              rounding bias, edge replication) fused with jdcolor.c ycc_rgb_convert, 4 pixels a lane
 // Integer arithmetic end to end: the result is bit-identical to libjpeg-turbo's (tests/test_jpeg_gpu.py).
+// Scaled decode (scale 1/2, 1/4, 1/8 = cv2.imread's IMREAD_REDUCED_COLOR_2 / _4 / _8): the same host stage and coefficient upload,
+//          jpeg_idct_scaled_kernel  jidctred.c's 4x4 / 2x2 / 1x1 transforms, the block size per component and frame as jdmaster.c
+//                              chooses it (scaled_layout), two 4x4 / four 2x2 / eight 1x1 blocks per eight lanes
+//          jpeg_colour_kernel  over the reduced frame, upsampling what the plan leaves (tests/test_jpeg_reduced_gpu.py)
 // Both kernels are HBM-trivial (~6 bytes moved per pixel); the stage exists to take the IDCT / upsampling / colour
 // work -- more than half of a CPU decode -- and the float conversion off the host.
 #include "common.hpp"
@@ -294,7 +298,35 @@ struct FrameDesc {
     int32_t bw[3], bh[3];
     uint32_t coef_off;              // first block of this frame in the batch coefficient buffer
     uint16_t q[3][64];
+    // the scaled-decode plan of this frame (scaled_layout below; at scale 1: 8, the component's size, the sampling factors)
+    int32_t bs[3];                  // side of the inverse transform's output block: 8, 4, 2 or 1
+    int32_t ph[3], pw[3];           // size of the component's sample plane
+    int32_t uv[3], uh[3];           // upsampling factors to the output, each 1 or 2
+    int32_t fancy;                  // chroma is upsampled with the triangle filter (else replicated)
 };
+
+inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// jdmaster.c jpeg_core_output_dimensions + use_merged/upsampling bookkeeping for scale 8/d: output size, per component the IDCT
+// block size (the chroma of a subsampled frame is transformed one size larger instead of being upsampled, while that divides
+// evenly), the component's plane size and the upsampling that is left.  comp_hw is {height, width}, comp_up {vertical, horizontal}.
+void scaled_layout(const sncal_jpeg_info& in, int d, int32_t out_hw[2], int32_t comp_block[3], int32_t comp_hw[3][2], int32_t comp_up[3][2]) {
+    const int m = 8 / d, maxh = in.h_samp, maxv = in.v_samp;
+    out_hw[0] = ceil_div((long long)in.height * m, 8);
+    out_hw[1] = ceil_div((long long)in.width * m, 8);
+    for (int c = 0; c < 3; ++c) {
+        comp_block[c] = comp_hw[c][0] = comp_hw[c][1] = comp_up[c][0] = comp_up[c][1] = 0;
+        if (c >= in.components) continue;
+        const int hc = c == 0 ? maxh : 1, vc = c == 0 ? maxv : 1;
+        int s = m;
+        while (s < 8 && (maxh * m) % (hc * s * 2) == 0 && (maxv * m) % (vc * s * 2) == 0) s *= 2;
+        comp_block[c] = s;
+        comp_hw[c][0] = ceil_div((long long)in.height * vc * s, (long long)maxv * 8);
+        comp_hw[c][1] = ceil_div((long long)in.width * hc * s, (long long)maxh * 8);
+        comp_up[c][0] = (maxv * m) / (vc * s);
+        comp_up[c][1] = (maxh * m) / (hc * s);
+    }
+}
 
 constexpr int F0_298 = 2446, F0_390 = 3196, F0_541 = 4433, F0_765 = 6270, F0_899 = 7373, F1_175 = 9633, F1_501 = 12299,
               F1_847 = 15137, F1_961 = 16069, F2_053 = 16819, F2_562 = 20995, F3_072 = 25172;
@@ -366,13 +398,124 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const int16_t* __restric
     *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
 }
 
+// ---- scaled decode (jidctred.c): the 4x4, 2x2 and 1x1 inverse transforms libjpeg runs for scale 1/2, 1/4, 1/8
+constexpr int R0_211 = 1730, R0_509 = 4176, R0_601 = 4926, R0_720 = 5906, R0_850 = 6967, R1_061 = 8697, R1_272 = 10426,
+              R1_451 = 11893, R2_172 = 17799, R3_624 = 29692;
+
+// which of the eight rows (pass 1) / columns (both passes) of a coefficient block an S-point reduced transform reads
+__device__ __forceinline__ constexpr bool red_reads(int S, int k) { return S == 8 || (S == 4 ? k != 4 : (k == 0 || (k & 1))); }
+
+// one S-point pass; P1 selects the descale of the column pass (CONST_BITS - PASS1_BITS [+1, +2]) or of the row pass
+template <int S, bool P1>
+__device__ __forceinline__ void idct_red(const int (&x)[8], int (&o)[S]) {
+    if constexpr (S == 8) {
+        idct8<P1 ? 11 : 18>(x, o);
+    } else if constexpr (S == 4) {
+        constexpr int SHIFT = P1 ? 12 : 19, H = 1 << (SHIFT - 1);
+        const int t0 = x[0] * 16384;
+        const int t2 = x[2] * F1_847 - x[6] * F0_765;
+        const int t10 = t0 + t2, t12 = t0 - t2;
+        const int oa = -x[7] * R0_211 + x[5] * R1_451 - x[3] * R2_172 + x[1] * R1_061;
+        const int ob = -x[7] * R0_509 - x[5] * R0_601 + x[3] * F0_899 + x[1] * F2_562;
+        o[0] = (t10 + ob + H) >> SHIFT; o[3] = (t10 - ob + H) >> SHIFT;
+        o[1] = (t12 + oa + H) >> SHIFT; o[2] = (t12 - oa + H) >> SHIFT;
+    } else {
+        static_assert(S == 2, "block size");
+        constexpr int SHIFT = P1 ? 13 : 20, H = 1 << (SHIFT - 1);
+        const int t10 = x[0] * 32768;
+        const int t0 = -x[7] * R0_720 + x[5] * R0_850 - x[3] * R1_272 + x[1] * R3_624;
+        o[0] = (t10 + t0 + H) >> SHIFT; o[1] = (t10 - t0 + H) >> SHIFT;
+    }
+}
+
+// An eight-lane group takes a SLOT of 8 / S consecutive blocks of one component, so that the row pass keeps all eight lanes busy
+// whatever the block size: one 8x8 block, two 4x4, four 2x2 (or eight 1x1, which have no passes).  Column pass: lane i transforms
+// column i of each block of the slot (the columns the row pass never reads are skipped) into rows [b * S, b * S + S) of the slot's
+// workspace.
+template <int S>
+__device__ __forceinline__ void red_columns(const int16_t* __restrict__ src, const uint16_t* q, int cnt, int (&ws)[8][9], int i) {
+    if (!red_reads(S, i)) return;
+#pragma unroll
+    for (int b = 0; b < 8 / S; ++b) {
+        if (b >= cnt) break;
+        int x[8], o[S];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) x[r] = red_reads(S, r) ? (int)src[b * 64 + r * 8 + i] * (int)q[r * 8 + i] : 0;
+        idct_red<S, true>(x, o);
+#pragma unroll
+        for (int r = 0; r < S; ++r) ws[b * S + r][i] = o[r];
+    }
+}
+
+// Row pass: lane i owns row i % S of block i / S of the slot and stores its S samples with one aligned store (planes are
+// allocated with a width that is a multiple of every block size in use).
+template <int S>
+__device__ __forceinline__ void red_rows(const int (&ws)[8][9], int i, int first, int cnt, int bw, unsigned char* __restrict__ plane, int Wp) {
+    const int b = i / S, r = i % S;
+    if (b >= cnt) return;
+    int x[8], o[S];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = red_reads(S, j) ? ws[i][j] : 0;
+    idct_red<S, false>(x, o);
+    const int k = first + b, by = k / bw, bx = k - by * bw;
+    unsigned char* dst = plane + (size_t)(by * S + r) * Wp + bx * S;
+    if constexpr (S == 8) {
+        const unsigned lo = range_limit(o[0]) | (range_limit(o[1]) << 8) | (range_limit(o[2]) << 16) | (range_limit(o[3]) << 24);
+        const unsigned hi = range_limit(o[4]) | (range_limit(o[5]) << 8) | (range_limit(o[6]) << 16) | (range_limit(o[7]) << 24);
+        *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
+    } else if constexpr (S == 4) {
+        *reinterpret_cast<unsigned*>(dst) = range_limit(o[0]) | (range_limit(o[1]) << 8) | (range_limit(o[2]) << 16) | (range_limit(o[3]) << 24);
+    } else {
+        *reinterpret_cast<unsigned short*>(dst) = (unsigned short)(range_limit(o[0]) | (range_limit(o[1]) << 8));
+    }
+}
+
+// slots a component of n blocks of size S occupies
+__host__ __device__ __forceinline__ int red_slots(int n, int S) { const int per = 8 / S; return (n + per - 1) / per; }
+
+// planes: (B, 3, Hp, Wp) uint8, Hp/Wp = the source size rounded up to 16, times scale.  One launch per batch; the block size is
+// the component's of the frame (FrameDesc::bs), so a batch may mix sampling layouts.
+__global__ __launch_bounds__(256) void jpeg_idct_scaled_kernel(const int16_t* __restrict__ coef, const FrameDesc* __restrict__ desc,
+                                                               unsigned char* __restrict__ planes, int Hp, int Wp) {
+    __shared__ int ws[32][8][9];
+    const FrameDesc& fd = desc[blockIdx.y];
+    const int t = threadIdx.x, ls = t >> 3, i = t & 7;
+    int slot = blockIdx.x * 32 + ls;                    // slot index within the frame, then within its component
+    int c = 0, base = 0;                                // component; its first block within the frame
+    bool live = false;
+    for (int cc = 0; cc < fd.ncomp && !live; ++cc) {
+        const int n = fd.bw[cc] * fd.bh[cc], slots = red_slots(n, fd.bs[cc]);
+        if (slot < slots) { live = true; c = cc; }
+        else { slot -= slots; base += n; }
+    }
+    const int S = live ? fd.bs[c] : 0;
+    const int first = live ? slot * (8 / S) : 0;        // first block of the slot within the component
+    const int cnt = live ? min(8 / S, fd.bw[c] * fd.bh[c] - first) : 0;
+    const int16_t* src = coef + ((size_t)fd.coef_off + base + first) * 64;
+    const uint16_t* q = fd.q[c];
+    if (S == 8) red_columns<8>(src, q, cnt, ws[ls], i);
+    else if (S == 4) red_columns<4>(src, q, cnt, ws[ls], i);
+    else if (S == 2) red_columns<2>(src, q, cnt, ws[ls], i);
+    __syncthreads();
+    if (!live) return;
+    unsigned char* plane = planes + ((size_t)blockIdx.y * 3 + c) * Hp * Wp;
+    if (S == 8) red_rows<8>(ws[ls], i, first, cnt, fd.bw[c], plane, Wp);
+    else if (S == 4) red_rows<4>(ws[ls], i, first, cnt, fd.bw[c], plane, Wp);
+    else if (S == 2) red_rows<2>(ws[ls], i, first, cnt, fd.bw[c], plane, Wp);
+    else if (i < cnt) {                                 // jpeg_idct_1x1: the DC term alone
+        const int k = first + i, by = k / fd.bw[c], bx = k - by * fd.bw[c];
+        plane[(size_t)by * Wp + bx] = (unsigned char)range_limit(((int)src[i * 64] * (int)q[0] + 4) >> 3);
+    }
+}
+
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// one chroma sample at full resolution: jdsample.c h2v2_fancy_upsample / h2v1_fancy_upsample / replication
-__device__ __forceinline__ int chroma_at(const unsigned char* __restrict__ p, int Wp, int x, int y, int hs, int vs, int cw, int ch) {
+// one chroma sample at output resolution: jdsample.c h2v2_fancy_upsample / h2v1_fancy_upsample / replication.  hs, vs: the
+// upsampling factors that are left after the inverse transform; cw, ch: the size of the component's plane
+__device__ __forceinline__ int chroma_at(const unsigned char* __restrict__ p, int Wp, int x, int y, int hs, int vs, int cw, int ch, bool fancy) {
     if (hs == 1) return p[(size_t)y * Wp + x];
     const int c = x >> 1;
-    if (cw <= 2) return p[(size_t)(vs == 2 ? y >> 1 : y) * Wp + c];       // jinit_upsampler: fancy only when downsampled_width > 2
+    if (!fancy) return p[(size_t)(vs == 2 ? y >> 1 : y) * Wp + c];        // jinit_upsampler: fancy only when downsampled_width > 2 (and not at scale 1/8)
     const int cn = (x & 1) ? min(c + 1, cw - 1) : max(c - 1, 0);
     if (vs == 1) {
         const unsigned char* row = p + (size_t)y * Wp;
@@ -396,7 +539,8 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const unsigned char* _
     const unsigned char* py = planes + (size_t)blockIdx.y * 3 * Hp * Wp;
     const unsigned char* pcb = py + (size_t)Hp * Wp;
     const unsigned char* pcr = pcb + (size_t)Hp * Wp;
-    const int hs = fd.hs, vs = fd.vs, cw = (W + hs - 1) / hs, ch = (H + vs - 1) / vs;
+    const int hs = fd.uh[1], vs = fd.uv[1], cw = fd.pw[1], ch = fd.ph[1];
+    const bool fancy = fd.fancy != 0;
     unsigned char px[12];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -404,8 +548,8 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const unsigned char* _
         const int yy = py[(size_t)y * Wp + x];
         int b = yy, g = yy, r = yy;
         if (fd.ncomp == 3) {
-            const int xb = chroma_at(pcb, Wp, x, y, hs, vs, cw, ch) - 128;
-            const int xr = chroma_at(pcr, Wp, x, y, hs, vs, cw, ch) - 128;
+            const int xb = chroma_at(pcb, Wp, x, y, hs, vs, cw, ch, fancy) - 128;
+            const int xr = chroma_at(pcr, Wp, x, y, hs, vs, cw, ch, fancy) - 128;
             r = clampi(yy + ((91881 * xr + 32768) >> 16), 0, 255);                     // jdcolor.c build_ycc_rgb_table
             b = clampi(yy + ((116130 * xb + 32768) >> 16), 0, 255);
             g = clampi(yy + ((-22554 * xb + 32768 - 46802 * xr) >> 16), 0, 255);
@@ -431,7 +575,8 @@ size_t max_blocks(int H, int W) {                       // 4:4:4 rounded to 16-p
 }  // namespace
 
 struct sncal_jpeg {
-    int max_batch = 0, H = 0, W = 0, Hp = 0, Wp = 0, threads = 1;
+    int max_batch = 0, H = 0, W = 0, Hp = 0, Wp = 0, threads = 1;     // H, W: the source size; Hp, Wp: the sample planes'
+    int scale = 1, OH = 0, OW = 0;                                     // scale denominator and the size of the decoded frame
     size_t frame_blocks = 0;
     int16_t* h_coef[2] = {nullptr, nullptr};
     FrameDesc* h_desc[2] = {nullptr, nullptr};
@@ -479,15 +624,42 @@ extern "C" void sncal_jpeg_destroy(sncal_jpeg* d) {
     delete d;
 }
 
+extern "C" int sncal_jpeg_scaled_layout(const sncal_jpeg_info* info, int scale_denom, int32_t out_hw[2], int32_t comp_block[3],
+                                        int32_t comp_hw[3][2], int32_t comp_up[3][2]) {
+    SNCAL_CHECK_ARG(info && out_hw && comp_block && comp_hw && comp_up, "sncal_jpeg_scaled_layout: null argument");
+    SNCAL_CHECK_ARG(scale_denom == 1 || scale_denom == 2 || scale_denom == 4 || scale_denom == 8,
+                    "sncal_jpeg_scaled_layout: scale_denom %d (1, 2, 4 or 8)", scale_denom);
+    SNCAL_CHECK_ARG(info->width > 0 && info->height > 0 && (info->components == 1 || info->components == 3) &&
+                    (info->h_samp == 1 || info->h_samp == 2) && (info->v_samp == 1 || info->v_samp == 2) && info->v_samp <= info->h_samp,
+                    "sncal_jpeg_scaled_layout: not the header of a supported frame (%dx%d, %d components, luma sampling %dx%d)",
+                    info->width, info->height, info->components, info->h_samp, info->v_samp);
+    scaled_layout(*info, scale_denom, out_hw, comp_block, comp_hw, comp_up);
+    return SNCAL_OK;
+}
+
+extern "C" int sncal_jpeg_output_size(const sncal_jpeg* d, int* out_h, int* out_w) {
+    SNCAL_CHECK_ARG(d && out_h && out_w, "sncal_jpeg_output_size: null argument");
+    *out_h = d->OH; *out_w = d->OW;
+    return SNCAL_OK;
+}
+
 extern "C" int sncal_jpeg_create(int max_batch, int height, int width, int n_threads, sncal_jpeg** out) {
+    return sncal_jpeg_create_scaled(max_batch, height, width, 1, n_threads, out);
+}
+
+extern "C" int sncal_jpeg_create_scaled(int max_batch, int height, int width, int scale_denom, int n_threads, sncal_jpeg** out) {
     SNCAL_CHECK_ARG(out, "sncal_jpeg_create: null output");
     *out = nullptr;
     SNCAL_CHECK_ARG(max_batch > 0 && max_batch <= 4096, "sncal_jpeg_create: max_batch %d", max_batch);
     SNCAL_CHECK_ARG(height > 0 && width > 0 && height <= 16384 && width <= 16384, "sncal_jpeg_create: frame size %dx%d", width, height);
+    SNCAL_CHECK_ARG(scale_denom == 1 || scale_denom == 2 || scale_denom == 4 || scale_denom == 8,
+                    "sncal_jpeg_create_scaled: scale_denom %d (1, 2, 4 or 8)", scale_denom);
     SNCAL_CHECK_ARG(n_threads >= 0, "sncal_jpeg_create: n_threads %d", n_threads);
     sncal_jpeg* d = new sncal_jpeg();
-    d->max_batch = max_batch; d->H = height; d->W = width;
-    d->Hp = (height + 15) / 16 * 16; d->Wp = (width + 15) / 16 * 16;
+    d->max_batch = max_batch; d->H = height; d->W = width; d->scale = scale_denom;
+    d->OH = ceil_div(height, scale_denom); d->OW = ceil_div(width, scale_denom);
+    // every component's plane is whole blocks of at most the luma MCU's extent: the source rounded up to 16, scaled
+    d->Hp = (height + 15) / 16 * 16 / scale_denom; d->Wp = (width + 15) / 16 * 16 / scale_denom;
     if (n_threads == 0) n_threads = (int)std::thread::hardware_concurrency();
     d->threads = n_threads < 1 ? 1 : (n_threads > 32 ? 32 : n_threads);
     d->frame_blocks = max_blocks(height, width);
@@ -523,7 +695,7 @@ extern "C" int sncal_jpeg_decode(sncal_jpeg* d, const unsigned char* const* data
     FrameDesc* h_desc = d->h_desc[slot];
     // pass 1 (serial, microseconds): headers -> block counts -> packed offsets
     std::vector<Header> hdr(B);
-    size_t blocks = 0, max_frame = 0;
+    size_t blocks = 0, max_frame = 0, max_slots = 0;
     for (int b = 0; b < B; ++b) {
         const Fail f = parse_header(data[b], len[b], hdr[b]);
         if (f.code != SNCAL_OK) { sncal::set_error("sncal_jpeg_decode: frame %d: %s", b, f.msg.c_str()); return f.code; }
@@ -534,14 +706,22 @@ extern "C" int sncal_jpeg_decode(sncal_jpeg* d, const unsigned char* const* data
         memset(&fd, 0, sizeof(fd));
         fd.ncomp = h.ncomp; fd.hs = h.comp[0].h; fd.vs = h.comp[0].v;
         fd.coef_off = (uint32_t)blocks;
-        size_t nb = 0;
+        sncal_jpeg_info info;
+        fill_info(h, &info);
+        int32_t out_hw[2], comp_hw[3][2], comp_up[3][2];
+        scaled_layout(info, d->scale, out_hw, fd.bs, comp_hw, comp_up);
+        size_t nb = 0, ns = 0;
         for (int c = 0; c < h.ncomp; ++c) {
             fd.bw[c] = h.bw[c]; fd.bh[c] = h.bh[c];
+            fd.ph[c] = comp_hw[c][0]; fd.pw[c] = comp_hw[c][1]; fd.uv[c] = comp_up[c][0]; fd.uh[c] = comp_up[c][1];
             memcpy(fd.q[c], h.qt[h.comp[c].tq], sizeof(fd.q[c]));
             nb += (size_t)h.bw[c] * h.bh[c];
+            ns += (size_t)red_slots(h.bw[c] * h.bh[c], fd.bs[c]);
         }
+        fd.fancy = h.ncomp == 3 && d->scale < 8 && fd.pw[1] > 2;
         blocks += nb;
         max_frame = nb > max_frame ? nb : max_frame;
+        max_slots = ns > max_slots ? ns : max_slots;
     }
     // pass 2: Huffman decode, one frame per worker at a time
     std::atomic<int> next{0}, bad{-1};
@@ -571,10 +751,13 @@ extern "C" int sncal_jpeg_decode(sncal_jpeg* d, const unsigned char* const* data
     SNCAL_CHECK_HIP(hipMemcpyAsync(d->d_coef, h_coef, blocks * 64 * sizeof(int16_t), hipMemcpyHostToDevice, st));
     SNCAL_CHECK_HIP(hipMemcpyAsync(d->d_desc, h_desc, (size_t)B * sizeof(FrameDesc), hipMemcpyHostToDevice, st));
     SNCAL_CHECK_HIP(hipEventRecord(d->copied[slot], st));
-    jpeg_idct_kernel<<<dim3((unsigned)((max_frame + 31) / 32), B), 256, 0, st>>>(d->d_coef, d->d_desc, d->d_planes, d->Hp, d->Wp);
+    if (d->scale == 1)
+        jpeg_idct_kernel<<<dim3((unsigned)((max_frame + 31) / 32), B), 256, 0, st>>>(d->d_coef, d->d_desc, d->d_planes, d->Hp, d->Wp);
+    else
+        jpeg_idct_scaled_kernel<<<dim3((unsigned)((max_slots + 31) / 32), B), 256, 0, st>>>(d->d_coef, d->d_desc, d->d_planes, d->Hp, d->Wp);
     SNCAL_CHECK_LAUNCH();
-    const int quads = (d->W + 3) / 4;
-    jpeg_colour_kernel<<<dim3((unsigned)(((size_t)quads * d->H + 255) / 256), B), 256, 0, st>>>(d->d_planes, d->d_desc, d_bgr, d->H, d->W, d->Hp, d->Wp);
+    const int quads = (d->OW + 3) / 4;
+    jpeg_colour_kernel<<<dim3((unsigned)(((size_t)quads * d->OH + 255) / 256), B), 256, 0, st>>>(d->d_planes, d->d_desc, d_bgr, d->OH, d->OW, d->Hp, d->Wp);
     SNCAL_CHECK_LAUNCH();
     return SNCAL_OK;
 }

@@ -7,7 +7,10 @@
     16-process pool, CameraCreator per row :65-69          one batched solve on a side stream (overlaps the next batch)
     json.dump(cam.to_json_parameters())   :36-37          interop.save_cameras, written while the next batch runs
 
-    python -m sncal_amd.submit --img-dir DIR --model model.pth --save-dir OUT [--lines-file lines.pkl]
+    python -m sncal_amd.submit --img-dir DIR --model model.pth --save-dir OUT [--lines-file lines.pkl] [--reduce 2]
+
+--reduce 2 / 4 / 8 (make_submit(..., reduce=)) is the loop whose imread carries cv2.IMREAD_REDUCED_COLOR_2 / _4 / _8: libjpeg's
+scaled decode, so that 1920x1080 footage reaches a network trained at 960x540 at the size it was trained for.
 """
 import argparse
 import warnings
@@ -20,7 +23,7 @@ import torch  # noqa: E402
 
 from . import _lib
 from .interop import save_cameras
-from .jpeg import JpegDecoder, probe
+from .jpeg import JpegDecoder, check_reduce, probe
 from .metamodel import load_model
 from .pipeline import CalibrationPipeline
 from .pitch import PITCH_POINTS
@@ -54,18 +57,26 @@ def run_frame_size(img_dir: str, img_names: List[str], sample: int = 32):
 
 
 def make_submit(img_dir: str, model, calibrator: CameraCreator, save_dir: str, batch_size: int = 64,
-                decoder_threads: int = 0, img_names: Optional[List[str]] = None, max_skip_fraction: float = 0.5) -> dict:
+                decoder_threads: int = 0, img_names: Optional[List[str]] = None, max_skip_fraction: float = 0.5, reduce: int = 1) -> dict:
     """The directory loop on a non-blocking stream of its own (JPEG decode, network, result copies), never on the legacy null
-    stream: the condition for the pipeline's CU-masked solve streams (pipeline.py).  See _make_submit for the loop itself."""
+    stream: the condition for the pipeline's CU-masked solve streams (pipeline.py).  See _make_submit for the loop itself.
+
+    reduce=2 / 4 / 8: the frames are decoded at that fraction of their size (libjpeg's scaled decode, what the reference's loop
+    computes when its imread carries cv2.IMREAD_REDUCED_COLOR_2 / _4 / _8 -- not cv2.resize).  The run's size vote and the
+    per-file size check stay on the SOURCE size; the network, the pipeline and the calibrator see the reduced frames, and the
+    cameras written are in the pixels of the DECODED frame, exactly as in that reference loop.  A caller who wants them in
+    source pixels rescales them with Camera.scale_resolution."""
+    check_reduce(reduce)                                                            # refuses a bad denominator before anything runs
     own = torch.cuda.Stream(device=model.nn_module.device)
     with torch.cuda.stream(own):
-        res = _make_submit(img_dir, model, calibrator, save_dir, batch_size, decoder_threads, img_names, max_skip_fraction)
+        res = _make_submit(img_dir, model, calibrator, save_dir, batch_size, decoder_threads, img_names, max_skip_fraction, reduce)
     own.synchronize()
     return res
 
 
 def _make_submit(img_dir: str, model, calibrator: CameraCreator, save_dir: str, batch_size: int = 64,
-                 decoder_threads: int = 0, img_names: Optional[List[str]] = None, max_skip_fraction: float = 0.5) -> dict:
+                 decoder_threads: int = 0, img_names: Optional[List[str]] = None, max_skip_fraction: float = 0.5,
+                 reduce: int = 1) -> dict:
     """Returns {'frames', 'written', 'completeness', 'skipped'} (make_submit.py:72 prints the completeness).  Files the device
     decoder cannot take are skipped with a warning; when more than `max_skip_fraction` of the run was skipped the function
     raises instead of returning a near-empty result that looks like a bad model."""
@@ -79,8 +90,8 @@ def _make_submit(img_dir: str, model, calibrator: CameraCreator, save_dir: str, 
     net = model.nn_module
     pt = model.prediction_transform
     pipe = CalibrationPipeline(net, calibrator, decode_size=(pt.H, pt.W))
-    dec = JpegDecoder(H, W, max_batch=batch_size, threads=decoder_threads, device=net.device)
-    frames = [torch.empty((batch_size, H, W, 3), dtype=torch.uint8, device=net.device) for _ in range(2)]
+    dec = JpegDecoder(H, W, max_batch=batch_size, threads=decoder_threads, device=net.device, reduce=reduce)     # H, W: the source size
+    frames = [torch.empty((batch_size, dec.out_height, dec.out_width, 3), dtype=torch.uint8, device=net.device) for _ in range(2)]
     pending = []                                                                    # (names, records, event)
     written = 0
     skipped = []                                                                    # frames the device decoder cannot take
@@ -148,6 +159,9 @@ def main(argv=None):
     ap.add_argument('--save-dir', required=True)
     ap.add_argument('--lines-file', default=None, help='lines pickle of export_line_result.py (optional)')
     ap.add_argument('--batch-size', type=int, default=64)
+    ap.add_argument('--reduce', type=int, default=1, choices=[1, 2, 4, 8],
+                    help="decode the frames at 1/N of their size (libjpeg's scaled decode = cv2.IMREAD_REDUCED_COLOR_N): 2 takes "
+                         '1920x1080 footage into a 960x540 network; the cameras are in the pixels of the decoded frame')
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--dtype', default=None, choices=['fp16x3', 'bf16x3', 'fp32', 'bf16', 'fp8'],
                     help='default: the fp32-class engine of the build (fp16x3: split-fp16 products, fp32 accumulation -- the exact engine\'s '
@@ -157,7 +171,7 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise _lib.SncalError('no GPU visible: this package has no CPU path')
     model = load_model(a.model, loss=None, optimizer=None, device=a.device, dtype=a.dtype)
-    res = make_submit(a.img_dir, model, default_calibrator(a.lines_file), a.save_dir, batch_size=a.batch_size)
+    res = make_submit(a.img_dir, model, default_calibrator(a.lines_file), a.save_dir, batch_size=a.batch_size, reduce=a.reduce)
     print(f"Completeness: {res['completeness']:.2f}")
     return res
 

@@ -8,14 +8,17 @@ every stage on the GPU path.
     EvalAImetric: 16-process pool per frame    metrics.py:97-229  metrics.EvalAImetric: batched solve + batched evaluation
     Loss metric (argus)                                           mean of the step losses weighted by step size (see validate())
 
-    python -m sncal_amd.validate --data DIR --model model.pth [--lines-file lines.pkl] [--batch-size 16]
+    python -m sncal_amd.validate --data DIR --model model.pth [--lines-file lines.pkl] [--batch-size 16] [--reduce 2]
 
 The line model (line/train_config.yaml: val_loss and the monitored val_acc) is scored by validate_line():
     EHMDataset listing, sort_anno, extreme points  line/dataset.py:54-92   list_line_split, annotations.line_keypoints
     model.val_step: forward, EHMLoss, decode       line/metamodel.py:51-71 EHMMetaModel.val_step: one forward, fused loss, target rebuilt
     AccMetric                                      line/metrics.py:20-137  metrics.AccMetric: counts on the device
 
-    python -m sncal_amd.validate --line --data DIR --model line.pth [--batch-size 8]
+    python -m sncal_amd.validate --line --data DIR --model line.pth [--batch-size 8] [--reduce 2]
+
+--reduce 2 / 4 / 8 decodes the split's frames at that fraction (libjpeg's scaled decode = cv2.imread's IMREAD_REDUCED_COLOR flags, not
+cv2.resize): a 1920x1080 split scored by a 960x540 checkpoint.
 """
 import argparse
 import json
@@ -29,7 +32,7 @@ import torch
 from . import _lib
 from .annotations import get_extreme_points, get_intersections, keypoint_labels_device, line_keypoints, sort_anno
 from .evaluate import scale_points
-from .jpeg import JpegDecoder, probe
+from .jpeg import JpegDecoder, check_reduce, probe, reduced_size
 from .lines import LINE_CLS
 from .metrics import AccMetric, EvalAImetric, L2metric
 from .prediction import CameraCreator
@@ -79,11 +82,14 @@ def list_split(folder: str):
 
 
 def decoded_batches(folder: str, names: Sequence[str], batch_size: int, device, decoder_threads: int, skipped: List[str],
-                    frame_size=None) -> Iterator[tuple]:
+                    frame_size=None, reduce: int = 1) -> Iterator[tuple]:
     """(indices into `names`, (n,H,W,3) uint8 BGR frames on the device) per batch of the JPEG files `names` of `folder`.  A file
     the decoder cannot take, or whose size is not the run's (frame_size (H, W), or the first frame's when None), is left out of
-    its batch and named in `skipped`; a batch left empty is not yielded."""
+    its batch and named in `skipped`; a batch left empty is not yielded.
+    reduce=2 / 4 / 8: the files are decoded at that fraction (JpegDecoder(reduce=): libjpeg's scaled decode, cv2.imread's
+    IMREAD_REDUCED_COLOR flags).  frame_size stays the size of the frames YIELDED: a file is taken when its reduced size equals it."""
     dec, size = None, frame_size
+    check_reduce(reduce)
 
     def skip(name, why):
         warnings.warn(f'{name}: skipped ({why})')
@@ -97,12 +103,16 @@ def decoded_batches(folder: str, names: Sequence[str], batch_size: int, device, 
                     with open(os.path.join(folder, names[j]), 'rb') as f:
                         blob = f.read()
                     fi = probe(blob)
+                    got = reduced_size(fi['height'], fi['width'], reduce)
                     if size is None:
-                        size = (fi['height'], fi['width'])
-                    if (fi['height'], fi['width']) != tuple(size):
-                        raise _lib.SncalError(f"{fi['width']}x{fi['height']} where the run's frames are {size[1]}x{size[0]}")
-                    if dec is None:
-                        dec = JpegDecoder(size[0], size[1], max_batch=batch_size, threads=decoder_threads, device=device)
+                        size = got
+                    if got != tuple(size):
+                        raise _lib.SncalError(f"{fi['width']}x{fi['height']}" + (f' (1/{reduce}: {got[1]}x{got[0]})' if reduce != 1 else '') +
+                                              f" where the run's frames are {size[1]}x{size[0]}")
+                    if dec is not None and (fi['height'], fi['width']) != (dec.height, dec.width):      # sizes that round up to the same frame
+                        raise _lib.SncalError(f"{fi['width']}x{fi['height']} where the run's source frames are {dec.width}x{dec.height}")
+                    if dec is None:         # the decoder is built for the SOURCE size of the first frame taken
+                        dec = JpegDecoder(fi['height'], fi['width'], max_batch=batch_size, threads=decoder_threads, device=device, reduce=reduce)
                 except (_lib.SncalError, OSError) as e:
                     skip(names[j], e)
                     continue
@@ -142,8 +152,9 @@ def _label_mode(labels: str, transform):
 
 
 def folder_batches(folder: str, batch_size: int, device, num_keypoints: int, margin: float, img_size, decoder_threads: int,
-                   skipped: List[str], transform=None, labels: str = 'host') -> Iterator[dict]:
-    """The batch dicts of a split folder, frames decoded on the device as uint8 BGR.  A file the decoder cannot take is left out
+                   skipped: List[str], transform=None, labels: str = 'host', reduce: int = 1) -> Iterator[dict]:
+    """The batch dicts of a split folder, frames decoded on the device as uint8 BGR (at 1 / reduce: see decoded_batches; the labels
+    are normalised coordinates and do not change).  A file the decoder cannot take is left out
     of its batch and named in `skipped`.  transform: None, or the label transform of the reference's validation loader
     (augment.test_transform(): FixLRAmbiguous), applied to each annotation before scale_points and annot_to_keypoints as
     HRNetDataset.__getitem__ does (dataset.py:60-64).  labels: see labelled_batch."""
@@ -151,7 +162,7 @@ def folder_batches(folder: str, batch_size: int, device, num_keypoints: int, mar
     transform, fix_lr = _label_mode(labels, transform)
     if transform is not None:
         annots = [transform.labels(a) for a in annots]
-    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped)
+    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped, reduce=reduce)
     try:
         for keep, image in frames:
             yield labelled_batch(image, [annots[j] for j in keep], [names[j] for j in keep], num_keypoints, margin, img_size,
@@ -191,7 +202,7 @@ def labelled_batch(image, annots: Sequence[dict], names: Sequence[str], num_keyp
 
 def train_batches(folder: str, batch_size: int, transform, shuffle: bool = True, seed=None, device='cuda:0', num_keypoints: int = 57,
                   margin: float = 0.0, img_size=(960, 540), decoder_threads: int = 0, skipped: List[str] = None,
-                  labels: str = 'host') -> Iterator[dict]:
+                  labels: str = 'host', reduce: int = 1) -> Iterator[dict]:
     """One epoch of the reference's TRAINING batches (train.py:31-33: HRNetDataset with train_transform under a shuffling loader)
     of a split folder: {'image', 'keypoints', 'mask', 'raw_annot', 'img_name'}.  Frames are decoded and augmented on the device
     (augment.train_transform: 'image' is fp32 (B,3,H,W) with ToTensor in the list, uint8 (B,H,W,3) without); the labels come from
@@ -199,12 +210,13 @@ def train_batches(folder: str, batch_size: int, transform, shuffle: bool = True,
     the transform's draws from random / numpy.random are those of a run without shuffling.  A file the decoder cannot take is
     left out of its batch and named in `skipped` (when a list is given); the last batch may be short, as the reference's is.
     labels: see labelled_batch; with 'device' the transform's FixLRAmbiguous is carried out by the label kernel (it draws nothing,
-    so the other transforms' draws are those of labels='host')."""
+    so the other transforms' draws are those of labels='host').  reduce: the frames are decoded at 1 / reduce (decoded_batches)
+    before the transform sees them."""
     names, annots = list_split(folder)
     order = np.random.RandomState(seed).permutation(len(names)) if shuffle else np.arange(len(names))
     names, annots = [names[j] for j in order], [annots[j] for j in order]
     transform, fix_lr = _label_mode(labels, transform)
-    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped if skipped is not None else [])
+    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped if skipped is not None else [], reduce=reduce)
     try:
         for keep, image in frames:
             out = transform({'image': image, 'annot': [annots[j] for j in keep]})
@@ -235,11 +247,14 @@ def list_line_split(folder: str, input_size=(960, 540)):
 
 
 def line_folder_batches(folder: str, batch_size: int, device, num_keypoint_pairs: int, input_size, decoder_threads: int,
-                        skipped: List[str]) -> Iterator[dict]:
+                        skipped: List[str], reduce: int = 1) -> Iterator[dict]:
     """The line model's batch dicts {'image', 'keypoints', 'line_para', 'img_name'} of a split folder (no 'keypoint_maps': the
-    loss rebuilds them).  Frames must be input_size (W, H): the reference's cv2.resize is not built, another size is skipped."""
+    loss rebuilds them).  A frame is taken when its size at 1 / reduce is input_size (W, H): a 1920x1080 split goes into the
+    960x540 network with reduce=2.  That is libjpeg's scaled decode (cv2.imread's IMREAD_REDUCED_COLOR_2), NOT the cv2.resize of
+    line/dataset.py:73, which is not built -- a declared deviation; a frame of any other size is skipped."""
     names, labels = list_line_split(folder, input_size)
-    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped, frame_size=(input_size[1], input_size[0]))
+    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped, frame_size=(input_size[1], input_size[0]),
+                             reduce=reduce)
     try:
         for keep, image in frames:
             pairs = [line_keypoints(labels[j], num_keypoint_pairs) for j in keep]
@@ -253,7 +268,7 @@ def line_folder_batches(folder: str, batch_size: int, device, num_keypoint_pairs
 
 def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreator, Sequence[CameraCreator]], batch_size: int = 16,
              loss=None, decoder_threads: int = 0, conf_threshold: float = 0.5, pckhs_thres: Sequence[float] = (2.0, 5.0, 10.0, 50.0),
-             threshold: int = 5, img_size=(960, 540), transform=None, labels: str = 'host'):
+             threshold: int = 5, img_size=(960, 540), transform=None, labels: str = 'host', reduce: int = 1):
     """-> {'val_loss', 'val_l2', 'val_precision', 'val_recall', 'val_pcks-2.0', ..., 'val_l2_reprojection', 'val_completeness',
     'val_eval_precision', 'val_eval_recall', 'val_eval_accuracy', 'val_evalai'} as floats (a ValidationResult).
 
@@ -269,6 +284,9 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
             keypoints the reference takes them against
     labels  folder form only.  'host': annotations.get_intersections per frame; 'device': one launch of the label kernel per batch,
             the transform's FixLRAmbiguous included
+    reduce  folder form only.  2 / 4 / 8: the frames are decoded at that fraction of their size (libjpeg's scaled decode, what
+            cv2.imread returns with IMREAD_REDUCED_COLOR_2 / _4 / _8; not cv2.resize), so that a 1920x1080 split is scored by a
+            network trained at 960x540.  img_size stays the size the metrics work in; the labels are normalised and do not change
 
     val_loss is the mean of the step losses weighted by step size.  This is the one definition here NOT taken from the reference:
     it is computed by pytorch-argus' Loss metric there, whose source is not part of the reference tree.
@@ -278,6 +296,8 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
         raise _lib.SncalError('transform applies to the folder form: batches handed in carry their labels already')
     if labels != 'host' and not isinstance(data, (str, os.PathLike)):
         raise _lib.SncalError('labels applies to the folder form: batches handed in carry their labels already')
+    if reduce != 1 and not isinstance(data, (str, os.PathLike)):
+        raise _lib.SncalError('reduce applies to the folder form: batches handed in carry their frames already')
     cams = list(camera) if isinstance(camera, (list, tuple)) else [camera]
     own_loss = model.loss
     if loss is not None:
@@ -291,7 +311,7 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
         skipped: List[str] = []
         if isinstance(data, (str, os.PathLike)):
             batches = folder_batches(os.fspath(data), batch_size, model.device, nk, float(loss_fn.sigma), img_size, decoder_threads, skipped,
-                                     transform=transform, labels=labels)
+                                     transform=transform, labels=labels, reduce=reduce)
         loss_sum = torch.zeros((), dtype=torch.float64, device=model.device)
         frames = 0
         for batch in (batches if batches is not None else data):
@@ -323,18 +343,23 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
 
 
 def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, loss=None, conf_threshold: float = 0.2,
-                  decoder_threads: int = 0, input_size=(960, 540)):
+                  decoder_threads: int = 0, input_size=(960, 540), reduce: int = 1):
     """Score a line-model checkpoint (EHMMetaModel) -> {'val_loss', 'val_acc'} as floats (a ValidationResult): the two numbers
     line/train_config.yaml logs and monitors.
 
-    data    a SoccerNet split folder of input_size frames (NNNNN.jpg + NNNNN.json; frames whose annotation the reference's
-            sort_anno rejects are dropped, as its dataset drops them), or any iterable of the batch dicts the reference's loader
+    data    a SoccerNet split folder (NNNNN.jpg + NNNNN.json; frames whose annotation the reference's sort_anno rejects are
+            dropped, as its dataset drops them) whose frames are input_size once decoded at 1 / reduce, or any iterable of the batch dicts the reference's loader
             yields ({'image', 'keypoints', 'line_para', ['keypoint_maps']}; batch_size then is whatever the iterable delivers)
     loss    an EHMLoss; default: the model's own (params['loss'] of the checkpoint)
+    reduce  folder form only.  A 1920x1080 split is taken with reduce=2: libjpeg's scaled decode (cv2.imread with
+            IMREAD_REDUCED_COLOR_2), which is NOT the cv2.resize of line/dataset.py:73 -- a declared deviation.
+            The labels are normalised coordinates and do not change; a frame whose reduced size is not input_size is skipped
 
     val_loss is the mean of the step losses weighted by step size, as in validate(); val_acc is AccMetric's value (the plain mean
     of the per-batch a@20 * 1.15, so it depends on batch_size, as in the reference).  A frame the decoder refuses (folder form) is
     left out and named in .skipped.  The host waits for the GPU once, at the end."""
+    if reduce != 1 and not isinstance(data, (str, os.PathLike)):
+        raise _lib.SncalError('reduce applies to the folder form: batches handed in carry their frames already')
     own_loss = model.loss
     if loss is not None:
         model.loss = loss                      # for this call only: restored below
@@ -344,7 +369,8 @@ def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, 
         acc = AccMetric(num_keypoints=len(LINE_CLS), conf_threshold=conf_threshold)
         skipped: List[str] = []
         if isinstance(data, (str, os.PathLike)):
-            batches = line_folder_batches(os.fspath(data), batch_size, model.device, acc.num_keypoints, input_size, decoder_threads, skipped)
+            batches = line_folder_batches(os.fspath(data), batch_size, model.device, acc.num_keypoints, input_size, decoder_threads, skipped,
+                                          reduce=reduce)
         loss_sum = torch.zeros((), dtype=torch.float64, device=model.device)
         frames = 0
         for batch in (batches if batches is not None else data):
@@ -377,6 +403,8 @@ def main(argv=None):
     ap.add_argument('--model', required=True, help='argus checkpoint of the keypoint model (model_name/params/nn_state_dict)')
     ap.add_argument('--lines-file', default=None, help='lines pickle of export_line_result.py (optional)')
     ap.add_argument('--batch-size', type=int, default=None, help='default 16, with --line 8')
+    ap.add_argument('--reduce', type=int, default=1, choices=[1, 2, 4, 8],
+                    help="decode the frames at 1/N of their size (libjpeg's scaled decode = cv2.IMREAD_REDUCED_COLOR_N)")
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--dtype', default=None, choices=['fp16x3', 'bf16x3', 'fp32', 'bf16', 'fp8'])
     a = ap.parse_args(argv)
@@ -384,9 +412,9 @@ def main(argv=None):
         raise _lib.SncalError('no GPU visible: this package has no CPU path')
     model = load_model(a.model, device=a.device, dtype=a.dtype)
     if a.line:
-        res = validate_line(model, a.data, batch_size=a.batch_size or 8)
+        res = validate_line(model, a.data, batch_size=a.batch_size or 8, reduce=a.reduce)
     else:
-        res = validate(model, a.data, default_calibrator(a.lines_file), batch_size=a.batch_size or 16)
+        res = validate(model, a.data, default_calibrator(a.lines_file), batch_size=a.batch_size or 16, reduce=a.reduce)
     for k, v in res.items():
         print(f'{k}: {v:.6f}')
     if res.skipped:
