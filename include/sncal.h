@@ -58,6 +58,9 @@ const char* sncal_x3_name(void);
  *   x = first column holding the channel maximum of exp(logp), y = first row holding it (the two
  *   come from separate reductions, exactly like the reference), conf = that maximum,
  *   x_px = x*img_w/w, y_px = y*img_h/h.   exp is float32(exp(float64(.))) -- see oracle/decode.py.
+ *   Size limit: h <= 8192, w <= 2048 and (h + 5*w + 4) * 4 <= 65536 bytes -- one workgroup keeps a plane's row and
+ *   column maxima in 64 KiB of LDS (6140 x 2048 and 8192 x 1637 are the largest at either end); anything larger is
+ *   SNCAL_ERR_ARG, and the message names the shape and the bound.
  * ---------------------------------------------------------------------------------------------- */
 int sncal_heatmap_decode(const float* d_logp, int B, int C, int h, int w, int img_h, int img_w,
                          float* d_out, void* stream);

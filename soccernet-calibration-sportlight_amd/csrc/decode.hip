@@ -295,6 +295,20 @@ __global__ __launch_bounds__(256) void line_decode_kernel(const float* __restric
 
 namespace sncal {
 
+// Dynamic LDS one workgroup may ask for without opting in to more: none of the decode kernels sets the attribute, so a shape
+// whose per-plane vectors need more than this is refused in the argument checks, never sent to a launch that cannot be configured.
+constexpr size_t DECODE_LDS_MAX = 65536;
+
+// kp_finish_kernel holds the h row maxima, the w column maxima and 4 scratch words of one plane in LDS
+static int kp_finish_lds(const char* who, int h, int w, size_t* lds) {
+    *lds = ((size_t)h + (size_t)w + 4) * sizeof(float);
+    if (h <= 0 || w <= 0 || *lds > DECODE_LDS_MAX) {
+        set_error("%s: heatmap %dx%d needs (h + w + 4) * 4 = %zu bytes of LDS, the limit is %zu", who, h, w, *lds, DECODE_LDS_MAX);
+        return SNCAL_ERR_ARG;
+    }
+    return SNCAL_OK;
+}
+
 size_t logsoftmax_decode_scratch(int B, int C, int h, int w) {
     const int nstrips = (h + RC_ROWS - 1) / RC_ROWS;
     return ((size_t)B * (C - 1) * h + (size_t)B * nstrips * (C - 1) * w) * sizeof(float);
@@ -304,12 +318,14 @@ int launch_logsoftmax_decode(const float* logits, int cstride, int C, int B, int
                              float* kpts, hipStream_t s) {
     if (C > 64 || C < 2 || cstride % 4 != 0) { set_error("fused log-softmax decode supports 2..64 classes"); return SNCAL_ERR_ARG; }
     if (w > 8192 || h > 8192) { set_error("fused log-softmax decode: heatmap %dx%d too large", h, w); return SNCAL_ERR_ARG; }
+    size_t lds;
+    if (int rc = kp_finish_lds("fused log-softmax decode", h, w, &lds)) return rc;
     const int nstrips = (h + RC_ROWS - 1) / RC_ROWS;
     float* rowmax = scratch;
     float* colpart = scratch + (size_t)B * (C - 1) * h;
     SNCAL_LAUNCH_FIRST(logsoftmax_rowcol_kernel, dim3(nstrips, B), dim3(256), 0, s, logits, cstride, C, h, w, rowmax, colpart, nstrips);
     SNCAL_CHECK_LAUNCH();
-    SNCAL_LAUNCH_LAST(kp_finish_kernel, dim3(B * (C - 1)), dim3(256), (size_t)(h + w + 4) * sizeof(float), s, rowmax, 1, colpart, nstrips,
+    SNCAL_LAUNCH_LAST(kp_finish_kernel, dim3(B * (C - 1)), dim3(256), lds, s, rowmax, 1, colpart, nstrips,
                        C - 1, h, w, img_h, img_w, kpts);
     SNCAL_CHECK_LAUNCH();
     return SNCAL_OK;
@@ -319,7 +335,9 @@ int launch_logsoftmax_decode(const float* logits, int cstride, int C, int B, int
 // partials per row [B][C-1][h][row_parts], column maxima in `col_parts` strips [B][col_parts][C-1][w]
 int launch_kp_finish(const float* rowpart, int row_parts, const float* colpart, int col_parts, int C, int B, int h, int w, int img_h, int img_w,
                      float* kpts, hipStream_t s) {
-    SNCAL_LAUNCH(kp_finish_kernel, dim3(B * (C - 1)), dim3(256), (size_t)(h + w + 4) * sizeof(float), s, rowpart, row_parts, colpart, col_parts,
+    size_t lds;
+    if (int rc = kp_finish_lds("keypoint decode of the head's maxima", h, w, &lds)) return rc;
+    SNCAL_LAUNCH(kp_finish_kernel, dim3(B * (C - 1)), dim3(256), lds, s, rowpart, row_parts, colpart, col_parts,
                  C - 1, h, w, img_h, img_w, kpts);
     SNCAL_CHECK_LAUNCH();
     return SNCAL_OK;
@@ -331,9 +349,12 @@ extern "C" int sncal_heatmap_decode(const float* d_logp, int B, int C, int h, in
                                     float* d_out, void* stream) {
     SNCAL_CHECK_ARG(B >= 0 && C >= 2 && h > 0 && w > 0, "sncal_heatmap_decode: bad shape B=%d C=%d h=%d w=%d", B, C, h, w);
     SNCAL_CHECK_ARG(w <= 2048 && h <= 8192, "sncal_heatmap_decode: heatmap %dx%d exceeds 8192x2048", h, w);
+    // kp_decode_kernel's LDS: h row maxima, 4 waves x w column maxima, w merged column maxima, 4 scratch words
+    const size_t lds = ((size_t)h + 5 * (size_t)w + 4) * sizeof(float);
+    SNCAL_CHECK_ARG(lds <= sncal::DECODE_LDS_MAX, "sncal_heatmap_decode: heatmap %dx%d needs (h + 5*w + 4) * 4 = %zu bytes of LDS, the limit is %zu",
+                    h, w, lds, sncal::DECODE_LDS_MAX);
     if (B == 0) return SNCAL_OK;
     SNCAL_CHECK_ARG(d_logp && d_out, "sncal_heatmap_decode: null pointer");
-    const size_t lds = (size_t)(h + 5 * w + 4) * sizeof(float);
     const bool vec4 = (w % 4 == 0) && ((reinterpret_cast<uintptr_t>(d_logp) & 15) == 0);
     const int nvec = vec4 ? w / 4 : w;
     const int nq = (nvec + 63) / 64;
