@@ -270,7 +270,9 @@ typedef struct {              /* one solved camera; mirrors baseline/camera.py:7
     double cx, cy;            /* calibration[0,2], [1,2] used by solve_pnp/refine (Q3)             */
     double rmse;              /* Camera.projection_rmse of the selected camera (mean L2, px)       */
     int32_t status;           /* 0 = no camera (reference returns None), >0 = which branch produced it */
-    int32_t n_points;         /* matched points used                                               */
+    int32_t n_points;         /* size of the matched-point set `rmse` is the mean over: the selection plus the admitted line
+                                 points (status 1, 2, 5, 7; opencv_calibration: its ground points), that set cut to keep_points
+                                 (3) / to the ground plane (6), the H-consistent ground points plus the top gates (4); 0 with status 0 */
 } sncal_camera;
 
 enum {                        /* sncal_camera.status                                               */

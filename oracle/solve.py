@@ -747,6 +747,7 @@ class Cam:
         self.principal_point = (w / 2, h / 2)
         self.rmse = None
         self.tag = ''
+        self.ids = None              # the point ids `rmse` is the mean over (sncal_camera.n_points = len(ids))
 
     @property
     def K4(self):
@@ -827,11 +828,13 @@ def camera_from_homography(ids, uv, img_wh=(960, 540)):
         cam.xfocal_length = cam.yfocal_length = 1.0
         cam.solve_pnp(ids, uv)
         cam.refine_camera(ids, uv)
+        cam.ids = list(ids)
         return cam, cam.projection_rmse(ids, uv)
     cam.xfocal_length, cam.yfocal_length = fx, fy
     cam.calibration = np.array([[fx, 0, img_wh[0] / 2], [0, fy, img_wh[1] / 2], [0, 0, 1.0]])
     cam.solve_pnp(ids, uv)
     cam.refine_camera(ids, uv)
+    cam.ids = list(ids)
     return cam, cam.projection_rmse(ids, uv)
 
 
@@ -852,6 +855,7 @@ def camera_all_points(ids, uv, img_wh=(960, 540)):
         # whatever refine_camera does to it, so it is not refined (under f ~ 0.04 px the reference's 20000-iteration LM runs to the end)
         if len(ids) > 6 and 10 <= cam.calibration[0, 0] <= 20000:
             cam.refine_camera(ids, uv)
+        cam.ids = list(ids)
         return cam, cam.projection_rmse(ids, uv)
     except Exception:
         return None
@@ -881,10 +885,15 @@ class CameraCreatorOracle:
             return None
 
     def _select(self, pred, reliable_rule):
-        n_det = int(np.count_nonzero(pred[:, 2] > self.conf_thresh))
+        # The reference runs on numpy 1.24 (its requirements.txt), whose value-based casting compares a float32 SCALAR with a python
+        # float in double (prediction.py:181, 265, 348: float32(0.2) > 0.2 holds) but a float32 ARRAY with a python float in float32
+        # (:178, 345: n_det_points does not count a confidence of exactly float32(0.2)).  Written out, so that the numpy that runs
+        # this file does not decide.
+        thr = float(self.conf_thresh)
+        n_det = int(np.count_nonzero(pred[:, 2].astype(np.float32) > np.float32(thr)))
         ids, uv = [], []
         for i in range(pred.shape[0]):
-            if pred[i, 2] > self.conf_thresh and (not reliable_rule or n_det < self.reliable_thresh or i in KEEP_POINTS):
+            if float(pred[i, 2]) > thr and (not reliable_rule or n_det < self.reliable_thresh or i in KEEP_POINTS):
                 ids.append(i)
                 uv.append((float(pred[i, 0]), float(pred[i, 1])))
         return ids, uv
@@ -934,6 +943,7 @@ class CameraCreatorOracle:
             cam.tag = 'original_hom'
         if cam is not None:
             cam.rmse = cam.projection_rmse(ids, uv)
+            cam.ids = list(ids)
         return cam
 
     def voter(self, pred, name):
@@ -957,6 +967,7 @@ class CameraCreatorOracle:
             if c is not None and good_cam(c[0]):
                 cams.append((c[0], c[1], tag))
         cam = None
+        candidates = [(tag, r, tag == 'camera_rel' and r < self.max_rmse_rel) for _, r, tag in cams]
         if cams:
             best = max(cams, key=lambda x: (x[2] == 'camera_rel' and x[1] < self.max_rmse_rel, 1 / x[1]))
             if best[1] < self.max_rmse:
@@ -965,6 +976,8 @@ class CameraCreatorOracle:
         if cam is None and hom is not None and hom[1] < self.max_rmse:
             cam = hom[0]
             cam.tag, cam.rmse = 'voter_hom', hom[1]
+        if cam is not None:
+            cam.candidates = candidates          # (tag, rmse, good) of the list the selection chose from
         return cam
 
     def _accurate(self, ids, uv, thr):
@@ -985,7 +998,7 @@ class CameraCreatorOracle:
 
     def opencv_calibration(self, pred, name):
         """prediction.py:138-170: ground-plane points only, single view, pose straight from calibrateCamera."""
-        ids = [i for i in range(pred.shape[0]) if i not in TOP_GATES and pred[i, 2] > self.conf_thresh]
+        ids = [i for i in range(pred.shape[0]) if i not in TOP_GATES and float(pred[i, 2]) > float(self.conf_thresh)]      # :145, a scalar
         if len(ids) <= 5:
             return None
         uv32 = pred[ids, :2].astype(np.float64)
@@ -995,6 +1008,7 @@ class CameraCreatorOracle:
         cam = _cam_from_calibration(res, self.img_size)
         cam.tag = 'opencv_calibration'
         cam.rmse = cam.projection_rmse(ids, uv32)
+        cam.ids = list(ids)
         return cam
 
     def opencv_calibration_multiplane(self, pred, name):
@@ -1019,4 +1033,5 @@ class CameraCreatorOracle:
             cam.refine_camera(ids, uv)
         cam.tag = 'multiplane'
         cam.rmse = cam.projection_rmse(ids, uv)
+        cam.ids = list(ids)
         return cam

@@ -66,7 +66,7 @@ __device__ __forceinline__ void store_camera(sncal_camera* out, int st, const Ca
         for (int i = 0; i < 3; ++i) o.position[i] = cam.pos[i];
         for (int i = 0; i < 9; ++i) o.rotation[i] = cam.R[i];
         o.fx = cam.fx; o.fy = cam.fy; o.cx = cam.cx; o.cy = cam.cy; o.rmse = cam.rmse;
-        o.status = cam.tag;
+        o.status = cam.tag; o.n_points = cam.n_points;
     }
     *out = o;
 }

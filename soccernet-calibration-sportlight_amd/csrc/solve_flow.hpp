@@ -21,6 +21,7 @@ struct Cam {
     double ppx, ppy;            // principal_point used by project_point / JSON
     double rmse;
     int tag;
+    int n_points;               // size of the point set rmse is the mean over (sncal_camera.n_points); set wherever rmse is
 };
 
 __device__ __forceinline__ void cam_set_pose(Cam& c, const double* R, const double* t) {   // position = -R^T t
@@ -142,7 +143,7 @@ __device__ int camera_from_homography(u64 mask, const Pts& p, int img_w, int img
 #ifdef SNCAL_SOLVE_TIMING
     if ((threadIdx.x & 63) == 0) printf("  hom wave %d: solve_pnp %llu clk refine %llu clk fx %g\n", (int)(threadIdx.x >> 6), th1 - th0, __builtin_amdgcn_s_memtime() - th1, c.fx);
 #endif
-    c.rmse = cam_rmse(c, mask, p);
+    c.rmse = cam_rmse(c, mask, p); c.n_points = popc64(mask);
     return ST_OK;
 }
 
@@ -173,7 +174,7 @@ __device__ int camera_all_points(u64 mask, const Pts& p, int img_w, int img_h, C
     // one wavefront for a camera nobody uses, which is what the 200-iteration cap of rounds 1-3 was for)
     if (popc64(mask) > 6 && c.fx >= 10 && c.fx <= 20000) cam_refine(c, mask, p);
     CAP_LAP("refine %llu clk");
-    c.rmse = cam_rmse(c, mask, p);
+    c.rmse = cam_rmse(c, mask, p); c.n_points = popc64(mask);
     return ST_OK;
 }
 
@@ -215,8 +216,12 @@ __device__ u64 select_points(const float conf, double thr, bool reliable_rule, i
     const int lane = threadIdx.x & 63;
     const bool det = lane < NPTS && (double)conf > thr;
     const u64 dm = __ballot(det);
-    if (!reliable_rule || popc64(dm) < reliable_thresh) return dm;
-    return dm & KEEP_MASK;
+    if (!reliable_rule) return dm;
+    // n_det_points (prediction.py:178, 345) compares the float32 COLUMN with the python float: under the reference's numpy (1.24) that is a
+    // float32 comparison, unlike the per-point test above (a float32 scalar: double) -- a confidence of exactly float32(0.2) is a point
+    // but does not count here
+    const int n_det = popc64(__ballot(lane < NPTS && conf > (float)thr));
+    return n_det < reliable_thresh ? dm : dm & KEEP_MASK;
 }
 
 // prediction.py:339-437, in the three pieces calibrate_kernel runs on two wavefronts (the homography camera and the calibrated camera are
@@ -248,7 +253,7 @@ __device__ int ov_combine(u64 mask, const Pts& p, int hs, const Cam& hom, int cs
     if (cs == ST_OK) out = cal;
     else if (hs == ST_OK && hom.rmse < 26) { out = hom; out.tag = SNCAL_CAM_ORIGINAL_HOM; }
     else return ST_NONE;
-    out.rmse = cam_rmse(out, mask, p);
+    out.rmse = cam_rmse(out, mask, p); out.n_points = popc64(mask);
     return ST_OK;
 }
 
@@ -333,7 +338,7 @@ __device__ int opencv_calibration(const float* kp, const sncal_voter_cfg& cfg, c
     if (!calibrate_planes(p.sched, &v, 1, p.X32, p.u32, p.v32, cfg.img_w, cfg.img_h, f, R0, t0)) return ST_RAISE;
     cam_from_calibration(out, f, R0, t0, cfg.img_w, cfg.img_h);
     out.tag = SNCAL_CAM_ORIGINAL;
-    out.rmse = cam_rmse(out, mask, p);
+    out.rmse = cam_rmse(out, mask, p); out.n_points = popc64(mask);
     return ST_OK;
 }
 
@@ -350,7 +355,7 @@ __device__ int opencv_calibration_multiplane(const float* kp, const float* line_
     cam_from_calibration(out, f, R0, t0, cfg.img_w, cfg.img_h);
     if (popc64(mask) > cfg.min_points_for_refinement) cam_refine(out, mask, p);
     out.tag = SNCAL_CAM_ORIGINAL;
-    out.rmse = cam_rmse(out, mask, p);
+    out.rmse = cam_rmse(out, mask, p); out.n_points = popc64(mask);
     return ST_OK;
 }
 

@@ -54,6 +54,7 @@ def camera_from_record(rec, img_size=IMG_SIZE) -> Optional[Camera]:
     cam.principal_point = (img_size[0] / 2.0, img_size[1] / 2.0)
     cam.rmse = float(rec.rmse)
     cam.source = STATUS_NAMES.get(rec.status, str(rec.status))
+    cam.n_points = int(rec.n_points)          # size of the matched-point set rmse is the mean over (sncal_camera.n_points)
     return cam
 
 
