@@ -262,6 +262,7 @@ int sncal_hrnet_plan_tap(sncal_hrnet* net, int op_idx, int tensor_id, void* d_ds
 
 /* ------------------------------------------------------------------------------------------------
  * S0-S11  camera solve (batched, one wavefront per frame)
+ *         sncal_calibrate / _ws: one configuration; sncal_calibrate_sweep: the same solve, every (max_rmse, max_rmse_rel) of a grid
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {              /* one solved camera; mirrors baseline/camera.py:79-90 attributes     */
     double position[3];
@@ -352,10 +353,34 @@ int sncal_calibrate_ws(const float* d_kpts, const float* d_line_pts, int B, cons
 /* Free what the library holds outside its handles (the scratch blocks of sncal_calibrate above); synchronises those streams. */
 int sncal_shutdown(void);
 
+/* One solve, a whole grid of (max_rmse, max_rmse_rel) -- the two parameters optimize_valid.yaml tunes.  They are read by the voter's final
+ * choice alone (prediction.py:293-329): no camera that is solved depends on them.  A frame therefore has at most S = 1 + 5 T distinct
+ * cameras, T = n_conf_threshs (iterative_voter) or 1 (voter, its threshold is cfg->conf_thresh), and every grid point is a choice among them.
+ *   algorithm     0 (iterative_voter) or 2 (voter).  1, 3 and 4 never read the two parameters: SNCAL_ERR_ARG, the message says so.
+ *                 cfg->max_rmse and cfg->max_rmse_rel are ignored.
+ *   d_grid        (n_grid,2) fp64 rows [max_rmse, max_rmse_rel], 1 <= n_grid <= 4096; NaN and infinities compare as they do in the solve
+ *   d_outcomes    (B,S) sncal_camera.  Slot 0: the camera of the first (original_voter) pass -- status 0 when the frame went on to the
+ *                 voter, always for algorithm 2.  Slot 1 + 5 t + k: camera k of threshold t in the order rel, acc, all, ground, hom, written
+ *                 as sncal_calibrate writes it when the selection takes it (status 3, 4, 5, 6, 7; its own rmse and n_points).  A slot no grid
+ *                 point can take is the all-zero record: a solve that failed, a camera good_camera refuses, and every slot of a threshold
+ *                 whose voter raises or that lies behind such a threshold.
+ *   d_choice      (n_grid,B) int32: the slot grid point g takes for frame b, -1 = no camera (the all-zero record).
+ * For every g and b, d_outcomes[b][d_choice[g][b]] equals byte for byte what sncal_calibrate_ws writes for frame b when cfg carries grid
+ * point g (tests/test_sweep_gpu.py).  The cameras come from the kernels of sncal_calibrate's default path, unchanged; the remarks there on
+ * RANSAC sampling and on parity with OpenCV apply as they stand.
+ * Caller-owned workspace of sncal_calibrate_sweep_workspace bytes, 16-byte aligned (SNCAL_ERR_WORKSPACE when short); nothing is launched
+ * after an argument error; B == 0 returns SNCAL_OK without touching a pointer.  Asynchronous on `stream`.
+ * NOT swept: conf_thresh(s), min_points*, reliable_thresh and min_focal_length decide which points a solve sees -- they change the solves. */
+int sncal_calibrate_sweep_workspace(int B, const sncal_voter_cfg* cfg, int n_grid, size_t* bytes);
+int sncal_calibrate_sweep(const float* d_kpts, const float* d_line_pts, int B, const sncal_voter_cfg* cfg,
+                          const double* d_grid, int n_grid, sncal_camera* d_outcomes, int32_t* d_choice,
+                          void* d_ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * H2 / N2  batched camera evaluation (accuracy@t of the SoccerNet calibration benchmark)
  * replaces get_polylines / distance_to_polyline / evaluate_camera_prediction and the mirrored-label accuracy choice
  *          baseline/evaluate_camera.py:14-229, 293-320 (the inner loop of src/models/hrnet/metrics.py:97-229)
+ *          (sncal_evaluate_outcomes / sncal_sweep_fold below: the same evaluation for the outcome sets of sncal_calibrate_sweep)
  *   d_cams (B) solved cameras (status 0 = missed frame); d_field (n_pts,3) fp64 sampled pitch model in class order,
  *   d_class_start (n_cls+1) int32, d_mirror (n_cls) int32 = index of the left/right-symmetric class
  *   (SoccerPitch.symetric_classes); d_gt (B,n_cls,max_gt,2) fp64 annotated points in pixels with counts
@@ -378,6 +403,18 @@ int sncal_evaluate_cameras_detail(const sncal_camera* d_cams, int B, const doubl
                                   const int* d_mirror, int n_cls, const double* d_gt, const int* d_gt_cnt,
                                   const int* d_gt_extra, int max_gt, double threshold, int img_w, int img_h,
                                   float* d_out, double* d_err, int* d_class_conf, void* stream);
+/* The evaluation of sncal_calibrate_sweep's outcome sets: d_outcomes (B,S) candidate cameras, each evaluated against ITS FRAME's
+ * annotations (the tables are those of sncal_evaluate_cameras, ONE set per frame, not per slot).  d_contrib (B,S,8) fp64 = what
+ * EvalAImetric accumulates for one frame (metrics.py:185-207) should that camera be the frame's: [missed, accuracy of the kept pass,
+ * evaluated, tp, tp + fp, tp + fn, sum of the point distances over the classes both predicted and annotated -- class by class, point by
+ * point --, number of those points]; a slot with status 0 gives [1,0,0,0,0,0,0,0].  The per-point detail never leaves the workgroup. */
+int sncal_evaluate_outcomes(const sncal_camera* d_outcomes, int B, int S, const double* d_field, const int* d_class_start,
+                            const int* d_mirror, int n_cls, const double* d_gt, const int* d_gt_cnt,
+                            const int* d_gt_extra, int max_gt, double threshold, int img_w, int img_h,
+                            double* d_contrib, void* stream);
+/* d_acc (n_grid,8) fp64: acc[g] = sum over b of d_contrib[b][d_choice[g][b]] ([1,0,0,0,0,0,0,0] for -1), summed in frame order without
+ * atomics: the same bits every run. */
+int sncal_sweep_fold(const double* d_contrib, const int32_t* d_choice, int B, int S, int n_grid, double* d_acc, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * N3  input stage: JPEG bytes -> BGR uint8 frames on the device

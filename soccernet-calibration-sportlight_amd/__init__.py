@@ -15,8 +15,8 @@ from .evaluate import CameraEvaluator  # noqa: F401
 from .jpeg import JpegDecoder  # noqa: F401
 from .pipeline import CalibrationPipeline  # noqa: F401
 from .loss import HRNetLoss, EHMLoss  # noqa: F401
-from .metrics import L2metric, EvalAImetric, AccMetric  # noqa: F401
+from .metrics import L2metric, EvalAImetric, EvalAISweep, AccMetric  # noqa: F401
 
 __all__ = ['HRNetPredictionTransform', 'EHMPredictionTransform', 'HRNetHeatmap', 'load_config',
            'HRNetMetaModel', 'EHMMetaModel', 'load_model', 'Camera', 'CameraCreator', 'PITCH_POINTS',
-           'INTERSECTON_TO_PITCH_POINTS', 'HRNetLoss', 'EHMLoss', 'L2metric', 'EvalAImetric', 'AccMetric']
+           'INTERSECTON_TO_PITCH_POINTS', 'HRNetLoss', 'EHMLoss', 'L2metric', 'EvalAImetric', 'EvalAISweep', 'AccMetric']

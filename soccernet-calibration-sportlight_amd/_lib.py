@@ -166,6 +166,11 @@ SIGNATURES = {
     'sncal_calibrate': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.POINTER(VoterCfg), vp, vp]),
     'sncal_calibrate_workspace': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(VoterCfg), ctypes.POINTER(ctypes.c_size_t)]),
     'sncal_calibrate_ws': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.POINTER(VoterCfg), vp, vp, ctypes.c_size_t, vp]),
+    'sncal_calibrate_sweep_workspace': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(VoterCfg), ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    'sncal_calibrate_sweep': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.POINTER(VoterCfg), vp, ctypes.c_int, vp, vp, vp, ctypes.c_size_t, vp]),
+    'sncal_evaluate_outcomes': (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int, vp, vp, vp, ctypes.c_int,
+                                               ctypes.c_double, ctypes.c_int, ctypes.c_int, vp, vp]),
+    'sncal_sweep_fold': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]),
     'sncal_shutdown': (ctypes.c_int, []),
     'sncal_stream_create_cu_mask': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(vp)]),
     'sncal_stream_destroy': (ctypes.c_int, [vp]),

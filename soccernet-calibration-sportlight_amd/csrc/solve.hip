@@ -163,6 +163,94 @@ __global__ __launch_bounds__(64) void voter_select_kernel(int B, sncal_voter_cfg
     store_camera(out + frame, st, cam);
 }
 
+// ---- sncal_calibrate_sweep: one solve, every (max_rmse, max_rmse_rel) ------------------------------------------------------------------
+// The two parameters are read by voter_select alone: what the first pass and voter_task_kernel compute does not depend on them.  A frame
+// therefore has at most S = 1 + 5 T distinct cameras (the first pass's, and five per threshold), and a grid point is a choice among
+// them.  sweep_outcomes_kernel writes them as the records store_camera would write had the selection taken them, plus the few numbers the
+// selection reads (SweepCand); sweep_select_kernel is voter_select_kernel's walk over the thresholds per (grid point, frame).
+struct SweepCand { double rmse[5]; unsigned ok; int raises; };      // rel, acc, all, ground, hom of one (frame, threshold): voter_pick's inputs
+
+// the voter of this threshold raises whatever the two parameters are: voter_select's two ST_RAISE exits
+__device__ __forceinline__ bool voter_raises(const VoterShared& sh) {
+    if (sh.hs == ST_RAISE) return true;
+    for (int i = 0; i < 4; ++i)
+        if (sh.st[i] == ST_OK && good_camera(sh.cands[i]) && sh.cands[i].rmse == 0.0) return true;
+    return false;
+}
+
+// voter (algorithm 2) has no first pass: every frame goes to the task stage
+__global__ __launch_bounds__(64) void sweep_mark_pending_kernel(int B, sncal_camera* __restrict__ first) {
+    const int frame = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (frame >= B) return;
+    Cam none;
+    none.tag = SNCAL_CAM_NONE;
+    store_camera(first + frame, ST_NONE, none);
+    first[frame].status = STATUS_PENDING;
+}
+
+// One thread per (frame, 0 = first pass | 1 + t = threshold t).  A slot no grid point can take is the all-zero record: a solve that failed,
+// a camera good_camera refuses, every slot of a threshold that raises or lies behind one that does, and the voter slots of a frame the
+// first pass settled (their VoterShared was never written).
+__global__ __launch_bounds__(64) void sweep_outcomes_kernel(int B, int T, const sncal_camera* __restrict__ first, const VoterShared* __restrict__ slots,
+                                                            sncal_camera* __restrict__ outcomes, SweepCand* __restrict__ cands) {
+    const int i = (int)(blockIdx.x * 64 + threadIdx.x), frame = i / (T + 1), j = i % (T + 1);
+    if (frame >= B) return;
+    const size_t S = 1 + 5 * (size_t)T;
+    const bool pending = first[frame].status == STATUS_PENDING;
+    Cam none;
+    none.tag = SNCAL_CAM_NONE;
+    if (j == 0) {
+        if (pending) store_camera(outcomes + frame * S, ST_NONE, none);
+        else outcomes[frame * S] = first[frame];
+        return;
+    }
+    const int t = j - 1;
+    sncal_camera* const o = outcomes + frame * S + 1 + 5 * t;
+    SweepCand sc;
+    for (int k = 0; k < 5; ++k) sc.rmse[k] = 0.0;
+    sc.ok = 0; sc.raises = 0;
+    bool open = pending;                                   // some grid point may reach this threshold
+    for (int q = 0; q < t && open; ++q) open = !voter_raises(slots[(size_t)frame * T + q]);
+    if (open && voter_raises(slots[(size_t)frame * T + t])) { sc.raises = 1; open = false; }
+    const int tags[4] = {SNCAL_CAM_VOTER_REL, SNCAL_CAM_VOTER_ACC, SNCAL_CAM_VOTER_ALL, SNCAL_CAM_VOTER_GROUND};
+    for (int k = 0; k < 5; ++k) {
+        bool ok = false;
+        if (open) {
+            const VoterShared& sh = slots[(size_t)frame * T + t];
+            ok = k < 4 ? (sh.st[k] == ST_OK && good_camera(sh.cands[k])) : sh.hs == ST_OK;
+            if (ok) {
+                Cam c = k < 4 ? sh.cands[k] : sh.hom;
+                c.tag = k < 4 ? tags[k] : SNCAL_CAM_VOTER_HOM;
+                store_camera(o + k, ST_OK, c);
+                sc.rmse[k] = c.rmse; sc.ok |= 1u << k;
+            }
+        }
+        if (!ok) store_camera(o + k, ST_NONE, none);
+    }
+    cands[(size_t)frame * T + t] = sc;
+}
+
+// One thread per (grid point, frame), frame fastest: a wavefront's 64 choices are 256 contiguous bytes of d_choice (n_grid, B).
+__global__ __launch_bounds__(256) void sweep_select_kernel(int B, int T, int n_grid, const double* __restrict__ grid, const sncal_camera* __restrict__ first,
+                                                           const SweepCand* __restrict__ cands, int32_t* __restrict__ choice) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)n_grid * B) return;
+    const int g = (int)(i / B), frame = (int)(i % B);
+    const double max_rmse = grid[2 * g], max_rmse_rel = grid[2 * g + 1];
+    const int fs = first[frame].status;
+    int pick = fs > 0 ? 0 : -1;
+    if (fs == STATUS_PENDING) {
+        for (int t = 0; t < T; ++t) {                      // prediction.py:250-256: the first threshold with a camera, or an exception, ends the walk
+            const SweepCand sc = cands[(size_t)frame * T + t];
+            const int r = voter_pick(max_rmse, max_rmse_rel, sc.raises != 0, sc.ok, sc.rmse);
+            if (r == PICK_NONE) continue;
+            if (r >= 0) pick = 1 + 5 * t + r;
+            break;
+        }
+    }
+    choice[i] = pick;
+}
+
 // iterative_voter / original_voter (algorithms 0, 1): TWO wavefronts per frame, two frames per workgroup -- wave 2 i the homography
 // camera, wave 2 i + 1 the calibrated camera of frame i (ov_hom / ov_cal above), the even wave combines them in the reference's order
 // and, for iterative_voter, marks a frame without a camera pending for the voter stage.  The other algorithms: one wavefront per frame,
@@ -522,7 +610,85 @@ extern "C" int sncal_calibrate_ws(const float* d_kpts, const float* d_line_pts, 
     return calibrate_impl(d_kpts, d_line_pts, B, cfg, d_out, d_ws, ws_bytes, false, stream);
 }
 
-static int env_schedule() {       // SNCAL_SOLVE_SCHEDULE=converged: the two single-camera entries on the run-to-convergence minimisers
+// ---- sncal_calibrate_sweep --------------------------------------------------------------------------------------------------------------
+// workspace: [FirstPass x B][VoterShared x B x T][sncal_camera x B: the first pass's result][SweepCand x B x T], each part on 256 bytes
+namespace {
+constexpr int SWEEP_MAX_GRID = 4096;
+struct SweepLayout { int T; size_t slots, first, cands, bytes; };
+size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+SweepLayout sweep_layout(int B, const sncal_voter_cfg* cfg) {
+    SweepLayout l;
+    l.T = cfg->algorithm == 2 ? 1 : cfg->n_conf_threshs;
+    l.slots = calibrate_fp_bytes(B);
+    l.first = l.slots + up256((size_t)B * std::max(l.T, 1) * sizeof(VoterShared));
+    l.cands = l.first + up256((size_t)B * sizeof(sncal_camera));
+    l.bytes = std::max(l.cands + up256((size_t)B * std::max(l.T, 1) * sizeof(SweepCand)), (size_t)256);
+    return l;
+}
+int sweep_check(const char* fn, int B, const sncal_voter_cfg* cfg, int n_grid) {
+    SNCAL_CHECK_ARG(B >= 0 && cfg, "%s: bad arguments", fn);
+    SNCAL_CHECK_ARG(cfg->algorithm >= 0 && cfg->algorithm <= 4, "%s: algorithm %d", fn, cfg->algorithm);
+    SNCAL_CHECK_ARG(cfg->algorithm == 0 || cfg->algorithm == 2,
+                    "%s: algorithm %d never reads max_rmse / max_rmse_rel, there is nothing to sweep (iterative_voter = 0 and voter = 2 do)", fn, cfg->algorithm);
+    SNCAL_CHECK_ARG(cfg->n_conf_threshs >= 0 && cfg->n_conf_threshs <= SNCAL_MAX_CONF_THRESHS, "%s: n_conf_threshs", fn);
+    SNCAL_CHECK_ARG(n_grid >= 1 && n_grid <= SWEEP_MAX_GRID, "%s: n_grid %d outside 1..%d", fn, n_grid, SWEEP_MAX_GRID);
+    return SNCAL_OK;
+}
+}  // namespace
+
+extern "C" int sncal_calibrate_sweep_workspace(int B, const sncal_voter_cfg* cfg, int n_grid, size_t* bytes) {
+    const int rc = sweep_check("sncal_calibrate_sweep_workspace", B, cfg, n_grid);
+    if (rc) return rc;
+    SNCAL_CHECK_ARG(bytes, "sncal_calibrate_sweep_workspace: bad arguments");
+    *bytes = sweep_layout(B, cfg).bytes;
+    return SNCAL_OK;
+}
+
+extern "C" int sncal_calibrate_sweep(const float* d_kpts, const float* d_line_pts, int B, const sncal_voter_cfg* cfg, const double* d_grid, int n_grid,
+                                     sncal_camera* d_outcomes, int32_t* d_choice, void* d_ws, size_t ws_bytes, void* stream) {
+    const int rca = sweep_check("sncal_calibrate_sweep", B, cfg, n_grid);
+    if (rca) return rca;
+    if (B == 0) return SNCAL_OK;
+    SNCAL_CHECK_ARG(d_kpts && d_grid && d_outcomes && d_choice, "sncal_calibrate_sweep: null pointer");
+    SNCAL_CHECK_ARG(cfg->img_w > 1 && cfg->img_h > 1, "sncal_calibrate_sweep: image size");
+    SNCAL_CHECK_ARG(d_ws && (reinterpret_cast<uintptr_t>(d_ws) & 15) == 0, "sncal_calibrate_sweep: workspace pointer (16-byte aligned device memory)");
+    const SweepLayout lay = sweep_layout(B, cfg);
+    if (ws_bytes < lay.bytes) { sncal::set_error("sncal_calibrate_sweep: workspace of %zu bytes, %zu needed (sncal_calibrate_sweep_workspace)", ws_bytes, lay.bytes); return SNCAL_ERR_WORKSPACE; }
+    const int rc = ensure_pitch_uploaded();
+    if (rc) return rc;
+    hipStream_t st = sncal::as_stream(stream);
+    char* const ws = reinterpret_cast<char*>(d_ws);
+    FirstPass* const fp = reinterpret_cast<FirstPass*>(ws);
+    VoterShared* const slots = reinterpret_cast<VoterShared*>(ws + lay.slots);
+    sncal_camera* const first = reinterpret_cast<sncal_camera*>(ws + lay.first);
+    SweepCand* const cands = reinterpret_cast<SweepCand*>(ws + lay.cands);
+    const int T = lay.T;
+    sncal_voter_cfg c = *cfg;                    // what the solve kernels see: the thresholds as the task stage indexes them
+    if (cfg->algorithm == 2) {
+        c.n_conf_threshs = 1; c.conf_threshs[0] = cfg->conf_thresh;
+        hipLaunchKernelGGL(sweep_mark_pending_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, B, first);
+        SNCAL_CHECK_LAUNCH();
+    } else {                                     // the stages of sncal_calibrate's default path, unchanged
+        hipLaunchKernelGGL(first_pass_task_kernel, dim3((unsigned)(2 * B)), dim3(64), 0, st, d_kpts, d_line_pts, B, c, fp);
+        SNCAL_CHECK_LAUNCH();
+        hipLaunchKernelGGL(first_pass_combine_kernel, dim3((unsigned)B), dim3(64), 0, st, d_kpts, d_line_pts, B, c, (const FirstPass*)fp, first, T > 0 ? 1 : 0);
+        SNCAL_CHECK_LAUNCH();
+    }
+    if (T > 0) {
+        hipLaunchKernelGGL(voter_task_kernel, dim3((unsigned)(B * T * VT_TASKS)), dim3(64), 0, st, d_kpts, d_line_pts, B, c, (const sncal_camera*)first, slots);
+        SNCAL_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(sweep_outcomes_kernel, dim3((unsigned)((B * (T + 1) + 63) / 64)), dim3(64), 0, st, B, T, (const sncal_camera*)first,
+                       (const VoterShared*)slots, d_outcomes, cands);
+    SNCAL_CHECK_LAUNCH();
+    const size_t n = (size_t)n_grid * B;
+    hipLaunchKernelGGL(sweep_select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, B, T, n_grid, d_grid, (const sncal_camera*)first,
+                       (const SweepCand*)cands, d_choice);
+    SNCAL_CHECK_LAUNCH();
+    return SNCAL_OK;
+}
+
+static int env_schedule() {      // SNCAL_SOLVE_SCHEDULE=converged: the two single-camera entries on the run-to-convergence minimisers
     static const int v = (getenv("SNCAL_SOLVE_SCHEDULE") && std::string(getenv("SNCAL_SOLVE_SCHEDULE")) == "converged") ? SCHED_CONVERGED : SCHED_OPENCV;
     return v;
 }

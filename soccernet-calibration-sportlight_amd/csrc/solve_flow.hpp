@@ -277,6 +277,28 @@ __device__ int voter_select(const sncal_voter_cfg& cfg, int hs, const Cam& hom, 
     return ST_NONE;
 }
 
+// voter_select's choice as an INDEX, on the numbers it reads alone (sncal_calibrate_sweep: one solve, many (max_rmse, max_rmse_rel)):
+// 0..3 = cands[i] (rel, acc, all, ground), 4 = the homography camera, -1 = no camera, -2 = the voter raises.  ok bit i: cands[i] was
+// solved and is a good_camera; bit 4: the homography camera was solved.  Same comparisons in the same order as voter_select above;
+// tests/test_sweep_gpu.py holds the two together byte for byte.
+enum { PICK_HOM = 4, PICK_NONE = -1, PICK_RAISE = -2 };
+__device__ __forceinline__ int voter_pick(double max_rmse, double max_rmse_rel, bool hom_raises, unsigned ok, const double (&rmse)[5]) {
+    if (hom_raises) return PICK_RAISE;
+    int best = -1;
+    bool best_flag = false;
+    double best_inv = 0;
+    for (int i = 0; i < 4; ++i) {
+        if (!((ok >> i) & 1)) continue;
+        if (rmse[i] == 0.0) return PICK_RAISE;
+        const bool flag = i == 0 && rmse[i] < max_rmse_rel;
+        const double inv = 1.0 / rmse[i];
+        if (best < 0 || (flag && !best_flag) || (flag == best_flag && inv > best_inv)) { best = i; best_flag = flag; best_inv = inv; }
+    }
+    if (best >= 0 && rmse[best] < max_rmse) return best;
+    if (((ok >> PICK_HOM) & 1) && rmse[PICK_HOM] < max_rmse) return PICK_HOM;
+    return PICK_NONE;
+}
+
 // (noinline: calibrate_kernel calls it in one place, and inlined there its five cameras share the register allocation of the kernel's other
 // algorithms -- the kernel's own spills went from 117 to 1778 VGPRs.  As a function it compiles to what it was with two call sites.)
 __device__ __attribute__((noinline)) int voter(const float* kp, const float* line_pts, const sncal_voter_cfg& cfg, double thr, Pts p, Cam& out) {

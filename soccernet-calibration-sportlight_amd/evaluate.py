@@ -177,6 +177,41 @@ class CameraEvaluator:
                 _lib.current_stream_ptr()), 'sncal_evaluate_cameras_detail')
         return (out, err, cls) if detail else out
 
+    def evaluate_outcomes(self, outcomes, annotations: Sequence[Dict[str, list]]):
+        """outcomes (B,S,sizeof(sncal_camera)) uint8 from CameraCreator.sweep_device -> contrib (B,S,8) fp64 on the device: what
+        EvalAImetric accumulates for frame b should slot s be its camera (sncal_evaluate_outcomes).  The annotations are packed and
+        uploaded once per frame, not per slot."""
+        import torch
+        _lib.require_device(outcomes, torch.uint8, 'outcomes')
+        if outcomes.dim() != 3 or outcomes.shape[0] != len(annotations) or outcomes.shape[2] != ctypes.sizeof(_lib.Camera):
+            raise _lib.SncalError('outcomes must be (B, S, sizeof(sncal_camera)) with one annotation dict per frame')
+        B, S = outcomes.shape[0], outcomes.shape[1]
+        contrib = torch.empty((B, S, 8), dtype=torch.float64, device=self.device)
+        if B == 0:
+            return contrib
+        gt, cnt, extra, max_gt = self.pack(annotations)
+        d_gt, d_cnt, d_extra = (torch.from_numpy(a).to(self.device) for a in (gt, cnt, extra))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().sncal_evaluate_outcomes(
+                outcomes.data_ptr(), B, S, self._field.data_ptr(), self._start.data_ptr(), self._mirror.data_ptr(), len(CLASSES),
+                d_gt.data_ptr(), d_cnt.data_ptr(), d_extra.data_ptr(), max_gt, self.threshold, self.width, self.height,
+                contrib.data_ptr(), _lib.current_stream_ptr()), 'sncal_evaluate_outcomes')
+        return contrib
+
+    def sweep_fold(self, contrib, choice):
+        """contrib (B,S,8) fp64, choice (n_grid,B) int32 -> (n_grid,8) fp64: per grid point the sum over the frames of the
+        contribution of the camera it takes (sncal_sweep_fold: frame order, the same bits every run)."""
+        import torch
+        _lib.require_device(contrib, torch.float64, 'contrib')
+        _lib.require_device(choice, torch.int32, 'choice')
+        if contrib.dim() != 3 or contrib.shape[2] != 8 or choice.dim() != 2 or choice.shape[1] != contrib.shape[0]:
+            raise _lib.SncalError('contrib must be (B,S,8) and choice (n_grid,B)')
+        acc = torch.empty((choice.shape[0], 8), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().sncal_sweep_fold(contrib.data_ptr(), choice.data_ptr(), contrib.shape[0], contrib.shape[1],
+                                                   choice.shape[0], acc.data_ptr(), _lib.current_stream_ptr()), 'sncal_sweep_fold')
+        return acc
+
     @staticmethod
     def frame_detail(out, err, cls, annotations, b: int, which: int = 0):
         """The `per_class_confusion` / `dict_errors` dictionaries evaluate_camera_prediction (evaluate_camera.py:172-226)

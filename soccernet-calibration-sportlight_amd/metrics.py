@@ -157,20 +157,98 @@ class EvalAImetric:
         return (self.total_frames - missed) / self.total_frames if self.total_frames > 0 else 0.0
 
     def epoch_complete(self, state):
+        _evalai_epoch(state, self.name, self._read(), self._skipped, self.total_frames)
+
+
+def _evalai_epoch(state, name, a, skipped, total_frames):
+    """metrics.py:209-229 on one accumulator row [missed, accuracy, n_accuracy, tp, n_precision, n_recall, l2_proj_sum, n_l2_proj]."""
+    missed = float(a[0]) + skipped
+    completeness = (total_frames - missed) / total_frames if total_frames > 0 else 0.0
+    accuracy = a[1] / a[2] if a[2] > 0 else 0.0
+    precision = a[3] / a[4] if a[4] > 0 else 0.0
+    recall = a[3] / a[5] if a[5] > 0 else 0.0
+    l2_reproj = a[6] / a[7] if a[7] > 0 else float('inf')
+    p = _prefix(state)
+    state.metrics[f'{p}l2_reprojection'] = float(l2_reproj)
+    state.metrics[f'{p}completeness'] = float(completeness)
+    state.metrics[f'{p}eval_precision'] = float(precision)
+    state.metrics[f'{p}eval_recall'] = float(recall)
+    state.metrics[f'{p}eval_accuracy'] = float(accuracy)
+    state.metrics[f'{p}{name}'] = float(completeness * accuracy)
+
+
+class EvalAISweep:
+    """EvalAImetric for every (max_rmse, max_rmse_rel) of a grid at once (the search space of optimize_valid.yaml), from ONE solve and
+    ONE evaluation per distinct camera: the two parameters only choose among the at most 1 + 5 T cameras a frame's solve produces
+    (CameraCreator.sweep_device), and what a frame adds to the accumulators depends on its camera alone.  Per batch: the solve, the
+    evaluation of every outcome slot (CameraEvaluator.evaluate_outcomes), and a gather-sum per grid point (sweep_fold).
+
+    pred2cam: a CameraCreator with algorithm 'iterative_voter' or 'voter' (its own max_rmse / max_rmse_rel are not read); the grid
+    is the cartesian product of the two lists, max_rmse outermost: .grid (n_grid,2), .params(g).  Same keys, same add_missed /
+    total_frames handling as EvalAImetric, once per grid point g."""
+    name = 'evalai'
+    better = 'max'
+
+    def __init__(self, pred2cam, max_rmse: Sequence[float], max_rmse_rel: Sequence[float], threshold: int = 5,
+                 img_size: Tuple[int, int] = (960, 540)):
+        from .prediction import sweep_grid
+        self.pred2cam = pred2cam
+        pred2cam.sweep_slots()                   # refuses the algorithms that have nothing to sweep
+        self._values = (list(max_rmse), list(max_rmse_rel))
+        self.grid = sweep_grid(*self._values)
+        self.threshold = threshold
+        self.img_size = tuple(int(v) for v in img_size)
+        self._evaluator = None
+        self.reset()
+
+    def __len__(self):
+        return len(self.grid)
+
+    def params(self, g: int) -> dict:
+        return {'max_rmse': float(self.grid[g, 0]), 'max_rmse_rel': float(self.grid[g, 1])}
+
+    def reset(self):
+        self.total_frames = 0
+        self._skipped = 0
+        self._acc = None             # fp64 (n_grid, 8) on the device: EvalAImetric's accumulator, one row per grid point
+
+    def add_missed(self, n: int):
+        self.total_frames += int(n)
+        self._skipped += int(n)
+
+    evaluator = EvalAImetric.evaluator
+
+    def update(self, step_output: dict):
+        preds = step_output['prediction']
+        d_lp = None
+        lp = self.pred2cam.line_points_array(step_output.get('img_name'))
+        if lp is not None:
+            d_lp = torch.from_numpy(lp).to(preds.device)
+        outcomes, choice = self.pred2cam.sweep_device(preds.contiguous().float(), d_lp, *self._values)
+        self.update_outcomes(outcomes, choice, step_output['raw_annots'])
+
+    def update_outcomes(self, outcomes: torch.Tensor, choice: torch.Tensor, raw_annots: List[dict]):
+        B = outcomes.shape[0]
+        self.total_frames += B
+        if B == 0:
+            return
+        ev = self.evaluator(outcomes.device)
+        a = ev.sweep_fold(ev.evaluate_outcomes(outcomes, raw_annots), choice)
+        self._acc = a if self._acc is None else self._acc + a
+
+    def _read(self):
+        if self._acc is None:
+            return np.zeros((len(self.grid), 8))
+        return self._acc.cpu().numpy()
+
+    def compute(self) -> List[float]:
+        """EvalAImetric.compute (completeness) per grid point."""
         a = self._read()
-        missed = float(a[0]) + self._skipped
-        completeness = (self.total_frames - missed) / self.total_frames if self.total_frames > 0 else 0.0
-        accuracy = a[1] / a[2] if a[2] > 0 else 0.0
-        precision = a[3] / a[4] if a[4] > 0 else 0.0
-        recall = a[3] / a[5] if a[5] > 0 else 0.0
-        l2_reproj = a[6] / a[7] if a[7] > 0 else float('inf')
-        p = _prefix(state)
-        state.metrics[f'{p}l2_reprojection'] = float(l2_reproj)
-        state.metrics[f'{p}completeness'] = float(completeness)
-        state.metrics[f'{p}eval_precision'] = float(precision)
-        state.metrics[f'{p}eval_recall'] = float(recall)
-        state.metrics[f'{p}eval_accuracy'] = float(accuracy)
-        state.metrics[f'{p}{self.name}'] = float(completeness * accuracy)
+        return [(self.total_frames - (float(a[g, 0]) + self._skipped)) / self.total_frames if self.total_frames > 0 else 0.0
+                for g in range(len(self.grid))]
+
+    def epoch_complete(self, state, g: int):
+        _evalai_epoch(state, self.name, self._read()[g], self._skipped, self.total_frames)
 
 
 ACC_TS = (5.0, 10.0, 20.0)          # metrics.py:117-118

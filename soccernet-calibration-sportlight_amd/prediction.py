@@ -58,6 +58,31 @@ def camera_from_record(rec, img_size=IMG_SIZE) -> Optional[Camera]:
     return cam
 
 
+SWEEP_MAX_GRID = 4096          # sncal_calibrate_sweep's bound on n_grid
+
+
+def sweep_grid(max_rmse, max_rmse_rel) -> np.ndarray:
+    """(n_grid,2) float64 rows [max_rmse, max_rmse_rel]: the cartesian product of the two value lists, max_rmse outermost."""
+    a = np.asarray(list(max_rmse), dtype=np.float64).reshape(-1)
+    r = np.asarray(list(max_rmse_rel), dtype=np.float64).reshape(-1)
+    if not (1 <= len(a) * len(r) <= SWEEP_MAX_GRID):
+        raise _lib.SncalError(f'a sweep holds 1..{SWEEP_MAX_GRID} grid points, not {len(a)} x {len(r)}')
+    return np.ascontiguousarray(np.stack([np.repeat(a, len(r)), np.tile(r, len(a))], axis=1))
+
+
+def parse_range(text: str):
+    """'start:stop:step' -> the values of Hydra's range(start, stop, step): stop excluded; ints stay ints.  'start:stop' steps by 1."""
+    parts = text.split(':')
+    if len(parts) not in (2, 3) or not all(p.strip() for p in parts):
+        raise ValueError(f'{text!r}: start:stop[:step]')
+    nums = [float(p) if any(c in p for c in '.eEn') else int(p) for p in parts]
+    start, stop, step = nums[0], nums[1], nums[2] if len(nums) == 3 else 1
+    if step == 0 or not all(np.isfinite(v) for v in (start, stop, step)):
+        raise ValueError(f'{text!r}: the step is zero or a bound is not finite')
+    n = max(0, int(np.ceil((stop - start) / step)))
+    return [start + i * step for i in range(n)]
+
+
 class CameraCreator:
     def __init__(self, pitch: Dict[str, np.ndarray] = None, img_size: Tuple[int, int] = (960, 540),
                  conf_thresh: float = 0.2, algorithm: str = 'opencv_calibration', lines_file=None, **kwargs):
@@ -157,6 +182,42 @@ class CameraCreator:
                                                      _lib.current_stream_ptr()),
                        'sncal_calibrate_ws')
         return out
+
+    def sweep_slots(self) -> int:
+        """S of sweep_device: the first pass's camera and five per voter threshold."""
+        if self.algorithm_name not in ('iterative_voter', 'voter'):
+            raise _lib.SncalError(f'{self.algorithm_name} never reads max_rmse / max_rmse_rel: there is nothing to sweep '
+                                  "(algorithm 'iterative_voter' or 'voter')")
+        return 1 + 5 * (len(self.conf_threshs) if self.algorithm_name == 'iterative_voter' else 1)
+
+    def sweep_device(self, d_kpts, d_line_pts, max_rmse, max_rmse_rel):
+        """ONE batched solve for every (max_rmse, max_rmse_rel) of the cartesian product, max_rmse outermost (sweep_grid): the two
+        parameters only choose among the cameras a solve produces (sncal_calibrate_sweep).  -> (outcomes (B,S,sizeof(sncal_camera))
+        uint8, choice (n_grid,B) int32), both on the device: outcomes[b, choice[g, b]] is the record solve_device returns for frame b
+        with grid point g's values (choice -1: no camera, the all-zero record).  This creator's own max_rmse / max_rmse_rel are not
+        read.  Asynchronous on the current stream."""
+        import torch
+        _lib.require_device(d_kpts, torch.float32, 'kpts')
+        B = d_kpts.shape[0]
+        if tuple(d_kpts.shape[1:]) != (57, 3):
+            raise _lib.SncalError('kpts must be (B,57,3)')
+        if d_line_pts is not None:
+            _lib.require_device(d_line_pts, torch.float32, 'line_pts')
+        S = self.sweep_slots()
+        grid = sweep_grid(max_rmse, max_rmse_rel)
+        cfg = self._cfg()
+        n = ctypes.c_size_t()
+        _lib.check(_lib.lib().sncal_calibrate_sweep_workspace(B, ctypes.byref(cfg), len(grid), ctypes.byref(n)), 'sncal_calibrate_sweep_workspace')
+        with torch.cuda.device(d_kpts.device):
+            d_grid = torch.from_numpy(grid).to(d_kpts.device)
+            outcomes = torch.empty((B, S, ctypes.sizeof(_lib.Camera)), dtype=torch.uint8, device=d_kpts.device)
+            choice = torch.empty((len(grid), B), dtype=torch.int32, device=d_kpts.device)
+            ws = torch.empty(n.value, dtype=torch.uint8, device=d_kpts.device)
+            _lib.check(_lib.lib().sncal_calibrate_sweep(d_kpts.data_ptr(), d_line_pts.data_ptr() if d_line_pts is not None else None,
+                                                        B, ctypes.byref(cfg), d_grid.data_ptr(), len(grid), outcomes.data_ptr(),
+                                                        choice.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
+                       'sncal_calibrate_sweep')
+        return outcomes, choice
 
     @staticmethod
     def records(out_tensor):

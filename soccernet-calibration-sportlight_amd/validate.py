@@ -34,8 +34,8 @@ from .annotations import get_extreme_points, get_intersections, keypoint_labels_
 from .evaluate import scale_points
 from .jpeg import JpegDecoder, check_reduce, probe, reduced_size
 from .lines import LINE_CLS
-from .metrics import AccMetric, EvalAImetric, L2metric
-from .prediction import CameraCreator
+from .metrics import AccMetric, EvalAImetric, EvalAISweep, L2metric
+from .prediction import CameraCreator, parse_range
 
 
 class _State:
@@ -48,6 +48,12 @@ class ValidationResult(dict):
     """The metrics dict; .frames = frames seen, .skipped = names of the frames that could not be decoded (counted as missed)."""
     frames = 0
     skipped: List[str] = []
+    params: Dict[str, float] = {}           # validate(sweep=): the grid point this result belongs to
+
+
+class SweepResults(list):
+    """validate(sweep=)'s ValidationResults in grid order (max_rmse outermost); .best = index of the first maximum of val_evalai."""
+    best = 0
 
 
 def annot_to_keypoints(annot: dict, num_keypoints: int = 57, margin: float = 0.0):
@@ -268,7 +274,7 @@ def line_folder_batches(folder: str, batch_size: int, device, num_keypoint_pairs
 
 def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreator, Sequence[CameraCreator]], batch_size: int = 16,
              loss=None, decoder_threads: int = 0, conf_threshold: float = 0.5, pckhs_thres: Sequence[float] = (2.0, 5.0, 10.0, 50.0),
-             threshold: int = 5, img_size=(960, 540), transform=None, labels: str = 'host', reduce: int = 1):
+             threshold: int = 5, img_size=(960, 540), transform=None, labels: str = 'host', reduce: int = 1, sweep: Dict[str, Sequence[float]] = None):
     """-> {'val_loss', 'val_l2', 'val_precision', 'val_recall', 'val_pcks-2.0', ..., 'val_l2_reprojection', 'val_completeness',
     'val_eval_precision', 'val_eval_recall', 'val_eval_accuracy', 'val_evalai'} as floats (a ValidationResult).
 
@@ -287,6 +293,12 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
     reduce  folder form only.  2 / 4 / 8: the frames are decoded at that fraction of their size (libjpeg's scaled decode, what
             cv2.imread returns with IMREAD_REDUCED_COLOR_2 / _4 / _8; not cv2.resize), so that a 1920x1080 split is scored by a
             network trained at 960x540.  img_size stays the size the metrics work in; the labels are normalised and do not change
+    sweep   {'max_rmse': [...], 'max_rmse_rel': [...]}: the search space of optimize_valid.yaml in ONE pass.  camera then is one
+            CameraCreator ('iterative_voter' or 'voter'; its own max_rmse / max_rmse_rel are not read): every batch is solved once
+            and each distinct camera evaluated once (metrics.EvalAISweep), and a SweepResults comes back: one ValidationResult per
+            point of the cartesian product, max_rmse outermost, each with .params, equal key by key to validate(..., [one
+            calibrator per grid point]); .best is the first maximum of val_evalai.  val_loss and the keypoint metrics are computed
+            once.  conf_thresh(s), min_points* and reliable_thresh change the solves themselves: they stay the caller's loop
 
     val_loss is the mean of the step losses weighted by step size.  This is the one definition here NOT taken from the reference:
     it is computed by pytorch-argus' Loss metric there, whose source is not part of the reference tree.
@@ -298,6 +310,11 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
         raise _lib.SncalError('labels applies to the folder form: batches handed in carry their labels already')
     if reduce != 1 and not isinstance(data, (str, os.PathLike)):
         raise _lib.SncalError('reduce applies to the folder form: batches handed in carry their frames already')
+    if sweep is not None:
+        if isinstance(camera, (list, tuple)):
+            raise _lib.SncalError('sweep takes ONE CameraCreator: the grid replaces the list of calibrators')
+        if set(sweep) != {'max_rmse', 'max_rmse_rel'}:
+            raise _lib.SncalError(f"sweep={{'max_rmse': [...], 'max_rmse_rel': [...]}}, not keys {sorted(sweep)}")
     cams = list(camera) if isinstance(camera, (list, tuple)) else [camera]
     own_loss = model.loss
     if loss is not None:
@@ -307,7 +324,10 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
         loss_fn = model._loss()
         nk = loss_fn.num_keypoints
         l2 = L2metric(num_keypoints=nk, conf_threshold=conf_threshold, pckhs_thres=pckhs_thres)
-        evals = [EvalAImetric(c, threshold=threshold, img_size=img_size) for c in cams]
+        if sweep is not None:
+            evals = [EvalAISweep(camera, sweep['max_rmse'], sweep['max_rmse_rel'], threshold=threshold, img_size=img_size)]
+        else:
+            evals = [EvalAImetric(c, threshold=threshold, img_size=img_size) for c in cams]
         skipped: List[str] = []
         if isinstance(data, (str, os.PathLike)):
             batches = folder_batches(os.fspath(data), batch_size, model.device, nk, float(loss_fn.sigma), img_size, decoder_threads, skipped,
@@ -329,16 +349,26 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
         if loss is not None:
             model.loss = own_loss
     val_loss = float(loss_sum.item()) / frames if frames else float('nan')
-    results = []
+    results = SweepResults() if sweep is not None else []
     for ev in evals:
         ev.add_missed(len(skipped))
-        state = _State('val')
-        state.metrics['val_loss'] = val_loss
-        l2.epoch_complete(state)
-        ev.epoch_complete(state)
-        res = ValidationResult({k: float(v) for k, v in state.metrics.items()})
-        res.frames, res.skipped = ev.total_frames, list(skipped)          # the camera metric's own count: scored + skipped
-        results.append(res)
+        for g in (range(len(ev)) if sweep is not None else [None]):
+            state = _State('val')
+            state.metrics['val_loss'] = val_loss
+            l2.epoch_complete(state)
+            if g is None:
+                ev.epoch_complete(state)
+            else:
+                ev.epoch_complete(state, g)
+            res = ValidationResult({k: float(v) for k, v in state.metrics.items()})
+            res.frames, res.skipped = ev.total_frames, list(skipped)          # the camera metric's own count: scored + skipped
+            if g is not None:
+                res.params = ev.params(g)
+            results.append(res)
+    if sweep is not None:
+        scores = [r['val_evalai'] for r in results]
+        results.best = scores.index(max(scores))
+        return results
     return results if isinstance(camera, (list, tuple)) else results[0]
 
 
@@ -405,16 +435,34 @@ def main(argv=None):
     ap.add_argument('--batch-size', type=int, default=None, help='default 16, with --line 8')
     ap.add_argument('--reduce', type=int, default=1, choices=[1, 2, 4, 8],
                     help="decode the frames at 1/N of their size (libjpeg's scaled decode = cv2.IMREAD_REDUCED_COLOR_N)")
+    ap.add_argument('--sweep-max-rmse', default=None, metavar='START:STOP:STEP',
+                    help="sweep camera.max_rmse over Hydra's range(start, stop, step), stop excluded (optimize_valid.yaml: 10:70:4); one solve per batch")
+    ap.add_argument('--sweep-max-rmse-rel', default=None, metavar='START:STOP:STEP', help='the same for camera.max_rmse_rel (optimize_valid.yaml: 4:16:2)')
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--dtype', default=None, choices=['fp16x3', 'bf16x3', 'fp32', 'bf16', 'fp8'])
     a = ap.parse_args(argv)
+    sweep = None
+    if a.sweep_max_rmse is not None or a.sweep_max_rmse_rel is not None:
+        if a.line:
+            ap.error('--sweep-max-rmse / --sweep-max-rmse-rel are the keypoint model\'s: the line model has no calibrator')
+        cal = default_calibrator(None)             # an axis that is not swept keeps the calibrator's value
+        sweep = {'max_rmse': parse_range(a.sweep_max_rmse) if a.sweep_max_rmse is not None else [cal.max_rmse],
+                 'max_rmse_rel': parse_range(a.sweep_max_rmse_rel) if a.sweep_max_rmse_rel is not None else [cal.max_rmse_rel]}
     if not torch.cuda.is_available():
         raise _lib.SncalError('no GPU visible: this package has no CPU path')
     model = load_model(a.model, device=a.device, dtype=a.dtype)
     if a.line:
         res = validate_line(model, a.data, batch_size=a.batch_size or 8, reduce=a.reduce)
     else:
-        res = validate(model, a.data, default_calibrator(a.lines_file), batch_size=a.batch_size or 16, reduce=a.reduce)
+        res = validate(model, a.data, default_calibrator(a.lines_file), batch_size=a.batch_size or 16, reduce=a.reduce, sweep=sweep)
+    if sweep is not None:
+        print(f"{'max_rmse':>10} {'max_rmse_rel':>12} {'completeness':>12} {'accuracy':>10} {'evalai':>10}")
+        for r in res:
+            print(f"{r.params['max_rmse']:>10g} {r.params['max_rmse_rel']:>12g} {r['val_completeness']:>12.6f} {r['val_eval_accuracy']:>10.6f} "
+                  f"{r['val_evalai']:>10.6f}")
+        best = res[res.best]
+        print(f"best: max_rmse={best.params['max_rmse']:g} max_rmse_rel={best.params['max_rmse_rel']:g} val_evalai={best['val_evalai']:.6f}")
+        res = best
     for k, v in res.items():
         print(f'{k}: {v:.6f}')
     if res.skipped:
