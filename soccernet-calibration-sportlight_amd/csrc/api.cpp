@@ -2,7 +2,9 @@
 #include "common.hpp"
 #include "persist.hpp"
 #include "x3.hpp"
+#include <cassert>
 #include <cstring>
+#include <mutex>
 #include <vector>
 
 namespace sncal {
@@ -14,6 +16,26 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 LaunchEvents& launch_events() { static thread_local LaunchEvents e; return e; }
+
+// ---- env.hpp: the table's rows and the accessors
+enum { FLAG, INT, STR };
+enum { PROCESS, NET, PLAN, LAUNCH };
+static const struct { const char* name; int kind; long long dflt; bool process; } g_env[ENV_COUNT] = {      // (the description: for the reader)
+#define SNCAL_ENV_ROW(id, name, kind, dflt, life, what) {name, kind, (long long)(dflt), life == PROCESS},
+    SNCAL_ENV_TABLE(SNCAL_ENV_ROW)
+#undef SNCAL_ENV_ROW
+};
+// the variable's value, null when unset; a PROCESS row's is a copy taken at the first call for that row.  kind: the calling accessor's
+static const char* env_value(EnvId id, int kind) {
+    static struct { std::once_flag once; const char* v; } kept[ENV_COUNT];
+    assert(g_env[id].kind == kind);
+    if (!g_env[id].process) return getenv(g_env[id].name);
+    std::call_once(kept[id].once, [id] { const char* v = getenv(g_env[id].name); kept[id].v = v ? strdup(v) : nullptr; });
+    return kept[id].v;
+}
+bool env_flag(EnvId id) { const char* v = env_value(id, FLAG); return v ? strcmp(v, "0") != 0 : g_env[id].dflt != 0; }
+long long env_int(EnvId id) { const char* v = env_value(id, INT); return v ? atoll(v) : g_env[id].dflt; }
+const char* env_str(EnvId id) { return env_value(id, STR); }
 
 // ---- host half of persist.hpp
 bool opt_in_lds_kernel(const void* kernel, int bytes) {

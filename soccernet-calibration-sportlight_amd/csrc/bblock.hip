@@ -306,12 +306,10 @@ int launch_bblock48(const BBlockParams& p0, int n_cus, hipStream_t s) {
     BBlockParams p = p0;
     p.tiles_x = (p.W + BB_TW - 1) / BB_TW;
     p.tiles_y = (p.H + BB_TH - 1) / BB_TH;
-    static const int dbg = env_int("SNCAL_BB_DBG", 0);
-    p.dbg = dbg;
+    p.dbg = env_int(ENV_BB_DBG);
     if (!opt_in_lds<&bblock48_kernel>(160 * 1024)) return SNCAL_ERR_HIP;
     const int n_wgs = persistent_grid(n_cus);
-    static const char* trace_file = getenv("SNCAL_BB_TRACE");
-    TraceScope trace(trace_file, (size_t)n_wgs * BB_NW * 8, s);
+    TraceScope trace(env_str(ENV_BB_TRACE), (size_t)n_wgs * BB_NW * 8, s);
     p.trace = trace.words;
     if (!p.ticket) { set_error("launch_bblock48: no ticket words"); return SNCAL_ERR_ARG; }
     SNCAL_LAUNCH(bblock48_kernel, dim3((unsigned)n_wgs), dim3(64 * BB_NW), (size_t)BB_LDS + 16, s, p);

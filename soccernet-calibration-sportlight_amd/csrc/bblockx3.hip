@@ -473,8 +473,7 @@ int launch_bblockx3(const BBlockX3Params& p0, int n_cus, hipStream_t s) {
     BBlockX3Params p = p0;
     // one launch addresses its tensors with 32-bit buffer offsets: more frames than fit go in several launches
     const size_t img = (size_t)p.H * p.W * (size_t)(p.out && p.out_cstride * 4 > 192 ? p.out_cstride * 4 : 192);
-    const char* lim_env = getenv("SNCAL_BBX_MAX_BYTES");             // (test hook: a small limit sends a small batch down the several-launches path)
-    const size_t lim = lim_env ? (size_t)atoll(lim_env) : (size_t)0xf0000000u;
+    const size_t lim = (size_t)env_int(ENV_BBX_MAX_BYTES);           // (test hook: a small limit sends a small batch down the several-launches path)
     const size_t n_max = img ? lim / img : 0;
     if (n_max == 0 || (size_t)(p.H + 1) * (p.H + 1) * (n_max < (size_t)p.N ? n_max : (size_t)p.N) >= ((size_t)1 << 32)) {
         set_error("launch_bblockx3: image too large for 32-bit offsets");
@@ -495,14 +494,13 @@ int launch_bblockx3(const BBlockX3Params& p0, int n_cus, hipStream_t s) {
     p.tiles_x = (p.W + TW - 1) / TW;
     p.tiles_y = (p.N * (p.H + 1) - 1 + TH - 1) / TH;
     p.h1_magic = (unsigned)((((unsigned long long)1 << 32) / (unsigned)(p.H + 1)) + 1ull);
-    static const int run_max = env_int("SNCAL_BBX_RUNS", RUN_MAX);
+    static_assert(RUN_MAX == 8, "env.hpp gives SNCAL_BBX_RUNS' default as a literal: keep the two equal");
+    const int run_max = env_int(ENV_BBX_RUNS);
     p.run_max = run_max < 1 ? 1 : run_max;
-    static const int dbg = env_int("SNCAL_BBX_DBG", 0);
-    p.dbg = dbg;
+    p.dbg = env_int(ENV_BBX_DBG);
     if (!opt_in_lds<&bblockx3_kernel>(160 * 1024)) return SNCAL_ERR_HIP;
     const int n_wgs = persistent_grid(n_cus);
-    static const char* trace_file = getenv("SNCAL_BBX_TRACE");
-    TraceScope trace(trace_file, (size_t)n_wgs * NW * 8, s);
+    TraceScope trace(env_str(ENV_BBX_TRACE), (size_t)n_wgs * NW * 8, s);
     p.trace = trace.words;
     if (!p.ticket) { set_error("launch_bblockx3: no ticket words"); return SNCAL_ERR_ARG; }
     SNCAL_LAUNCH(bblockx3_kernel, dim3((unsigned)n_wgs), dim3(64 * (NW + 2)), (size_t)LDS_BYTES, s, p);

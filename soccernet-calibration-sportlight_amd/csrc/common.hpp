@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "../../include/sncal.h"
+#include "env.hpp"
 
 namespace sncal {
 
@@ -23,12 +24,6 @@ void set_error(const char* fmt, ...);
 #define SNCAL_CHECK_LAUNCH() SNCAL_CHECK_HIP(hipGetLastError())
 
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-// integer switch from the environment (tuning aids, A-B references); callers that want one read per process keep the result in a static
-static inline int env_int(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
 
 // solve.hip: release the scratch block(s) sncal_calibrate keeps per (device, stream) -- one stream's, or all of them
 int release_solve_scratch(hipStream_t st, bool all);

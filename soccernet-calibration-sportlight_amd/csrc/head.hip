@@ -291,8 +291,7 @@ template <int M2, int NSRC, int KS1>
 void launch_one(const HeadParams& q, unsigned blocks, hipStream_t s) {
     const size_t lds = (size_t)(NSRC * HEAD_SRC_LDS + (2 * KS1 + M2 + 1) * 1024);
     // gather by MFMA: two gather sources whose worst-case boxes hold at most 16 pixels each (one DMA piece, K slots 16 s .. 16 s + 15)
-    static const int gm_env = env_int("SNCAL_HEAD_GM", 1);      // tuning aid: 0 = VALU gather
-    bool gm = NSRC == 2 && gm_env != 0;
+    bool gm = NSRC == 2 && env_int(ENV_HEAD_GM) != 0;      // tuning aid: 0 = VALU gather
     for (int s2 = 0; s2 < NSRC && gm; ++s2) {
         const int bh = (int)(q.sy[s2] * (HEAD_TH - 1)) + 3, bwid = (int)(q.sx[s2] * 15) + 3;
         if (bh * bwid > 16) gm = false;

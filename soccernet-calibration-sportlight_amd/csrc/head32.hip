@@ -191,8 +191,7 @@ __global__ __launch_bounds__(256, 4) void head32_kernel(const HeadParams p) {
 // applies when: two gather sources whose per-wave boxes (one output row x 32 columns) hold at most 16 pixels, K1 = ks16 * 16 with an
 // instantiated depth, LC a multiple of 8 and at most 64.  Returns false (nothing launched) otherwise: the 16 x 16 x 32 kernel runs.
 bool head32_applies(const HeadParams& p) {
-    static const int enabled = env_int("SNCAL_HEAD32", 1);      // tuning aid: 0 = head.hip
-    if (!enabled || p.nsrc != 2 || !p.w0_32 || !p.w1_32 || p.ks16 != 13 || p.LC > 64 || p.LC % 8) return false;
+    if (!env_int(ENV_HEAD32) || p.nsrc != 2 || !p.w0_32 || !p.w1_32 || p.ks16 != 13 || p.LC > 64 || p.LC % 8) return false;
     return head_boxes_fit(p.sx[0]) && head_boxes_fit(p.sx[1]);
 }
 void head32_decode_parts(int h, int w, int* row_parts, int* col_parts) { *row_parts = (w + 31) / 32; *col_parts = (h + 3) / 4; }
@@ -207,8 +206,7 @@ bool launch_head32(const HeadParams& p, hipStream_t s) {
     HeadParams q = p;
     const unsigned blocks = head_set_tiling(q, 32, 4);
     const int rb = (p.LC + 31) / 32;
-    static const char* trace_file = getenv("SNCAL_HEAD_TRACE");
-    TraceScope trace(trace_file, (size_t)(blocks / 97 + 1) * 8, s);
+    TraceScope trace(env_str(ENV_HEAD_TRACE), (size_t)(blocks / 97 + 1) * 8, s);
     q.trace = trace.words;
     const size_t lds = (size_t)(H32_SRC + (13 + rb * 2 + 1) * 1024);
     if (p.dec_row && p.dec_col && rb == 2)       // decode-fused form: 32 KB of LDS for the tile's log-probabilities

@@ -310,10 +310,7 @@ __global__ __launch_bounds__(256, 2) void headx3_kernel(const HeadParams p) {
 }
 
 // applies to the keypoint network's head: two gather sources whose per-wave boxes hold at most 16 pixels, K1 = 13 x 16, 33..64 classes
-bool headx3_enabled() {
-    static const int enabled = env_int("SNCAL_HEADX3", 1);      // 0 = the split head on the generic fp32 kernels
-    return enabled != 0;
-}
+bool headx3_enabled() { return env_int(ENV_HEADX3) != 0; }      // 0 = the split head on the generic fp32 kernels
 bool headx3_applies(const HeadParams& p) {
     if (!headx3_enabled() || p.nsrc != 2 || !p.w0_32 || !p.w0_32_lo || !p.w1_32 || !p.w1_32_lo || p.ks16 != KS || p.LC != 64 || p.Cd % 8) return false;
     return head_boxes_fit(p.sx[0]) && head_boxes_fit(p.sx[1]);
@@ -324,8 +321,7 @@ bool launch_headx3(const HeadParams& p, hipStream_t s) {
     opt_in_lds<&headx3_kernel<0>, &headx3_kernel<1>>(X_LDS);
     HeadParams q = p;
     // the folded branches' boxes through LDS (kernel prologue): at most four source rows per tile, both boxes within one stage-1 weight buffer
-    static const int stage = env_int("SNCAL_HEAD_STAGE", 1);
-    q.stage_folds = stage != 0 && p.Cd % 16 == 0 ? 1 : 0;
+    q.stage_folds = env_int(ENV_HEAD_STAGE) != 0 && p.Cd % 16 == 0 ? 1 : 0;
     {
         int bytes = 0;
         for (int f = 0; f < p.nfold; ++f) {
@@ -336,8 +332,7 @@ bool launch_headx3(const HeadParams& p, hipStream_t s) {
         if (bytes > W0_BUF) q.stage_folds = 0;
     }
     const unsigned blocks = head_set_tiling(q, 32, 4);
-    static const char* trace_file = getenv("SNCAL_HEAD_TRACE");
-    TraceScope trace(trace_file, (size_t)(blocks / 97 + 1) * 8, s);
+    TraceScope trace(env_str(ENV_HEAD_TRACE), (size_t)(blocks / 97 + 1) * 8, s);
     q.trace = trace.words;
     if (p.dec_row && p.dec_col) SNCAL_LAUNCH((headx3_kernel<1>), dim3(blocks), dim3(256), (size_t)X_LDS, s, q);
     else SNCAL_LAUNCH((headx3_kernel<0>), dim3(blocks), dim3(256), (size_t)X_LDS, s, q);

@@ -42,7 +42,7 @@ void conv_params(const sncal_hrnet& net, const Op& op, int sb, char* ws, const M
     p.halo_w_magic = 0xFFFFFFFFu / (unsigned)((16 * m.twf - 1) * L.stride + L.k) + 1u;
     p.tiles_x = m.tiles_x; p.tiles_y = m.tiles_y;
     p.epi_lds = m.epi_lds ? 1 : 0;
-    { static const int abl = env_int("SNCAL_ABLATE", 0); p.ablate = abl; }
+    p.ablate = env_int(ENV_ABLATE);
     p.nblk = L.nblk;
     p.n_work = (unsigned)(p.tiles_x * p.tiles_y * sb * L.nblk);
     p.per_xcd = (p.n_work + 7) / 8;
@@ -142,7 +142,7 @@ int run_conv(const sncal_hrnet& net, const Launch& e, const Call& c) {
     ConvParams p;
     conv_params(net, op, c.sb, c.ws, e.m[0], p);
     // tuning aid: SNCAL_CONV_TRACE=<layer name> dumps per-workgroup phase timestamps of that layer's last launch to conv_trace.bin
-    static const char* trace_name = getenv("SNCAL_CONV_TRACE");
+    const char* trace_name = env_str(ENV_CONV_TRACE);
     const bool traced = trace_name && net.layers[op.conv].name == trace_name;
     TraceScope trace(traced ? "conv_trace.bin" : nullptr, (size_t)8 * ((p.n_work + 7) / 8) * 16, c.stream);
     p.trace = trace.words;
@@ -184,14 +184,11 @@ int run_tt(sncal_hrnet& net, Launch& e, const Call& c) {
     tp.queue = net.d_tickets + TICKET_TT;
     // tuning aid: SNCAL_TT_TRACE=<file> dumps the per-team phase timestamps of the LAST launch with 3 members
     // (SNCAL_TT_TRACE_CFG64=1: of the last launch of the 64-channel tile instead)
-    static const char* trace_file = getenv("SNCAL_TT_TRACE");
-    static const bool trace_cfg64 = getenv("SNCAL_TT_TRACE_CFG64") && atoi(getenv("SNCAL_TT_TRACE_CFG64")) != 0;
-    static const int trace_nth = env_int("SNCAL_TT_TRACE_NTH", -1);      // only the n-th such launch of the process
-    static int trace_seen = 0;
-    const bool traced = trace_file && (trace_cfg64 ? e.plan.cfg == 1 : n == 3) && (trace_nth < 0 || trace_seen++ == trace_nth);
+    const char* trace_file = env_str(ENV_TT_TRACE);
+    const bool traced = trace_file && (env_flag(ENV_TT_TRACE_CFG64) ? e.plan.cfg == 1 : n == 3);
     TraceScope trace(traced ? trace_file : nullptr, (size_t)e.plan.n_wgs * 2 * 256, stream);
     tp.trace = trace.words;
-    { static const int abl = env_int("SNCAL_TT_ABLATE", 0); tp.ablate = abl; }
+    tp.ablate = env_int(ENV_TT_ABLATE);
     launch_conv_tt(tp, e.plan.n_wgs, fp8 ? 1 : x3 ? 2 : 0, stream, e.plan.cfg);
     SNCAL_CHECK_LAUNCH();
     return SNCAL_OK;
@@ -503,8 +500,8 @@ extern "C" int sncal_hrnet_create(const sncal_hrnet_desc* desc, int dtype, sncal
     net->ge = dtype == SNCAL_BF16 ? 8 : 4;
     net->esize = dtype == SNCAL_BF16 ? 2 : 4;
     net->variants = dtype == SNCAL_BF16 ? conv_variants_bf16(&net->nvariants) : net->x3 ? conv_variants_x3(&net->nvariants) : conv_variants_f32(&net->nvariants);
-    if (const char* e = getenv("SNCAL_SUBBATCH")) { const int v = atoi(e); if (v > 0) net->subbatch = v; }
-    if (const char* e = getenv("SNCAL_FUSED_HEAD")) net->fused_enabled = atoi(e) != 0;
+    if (env_int(ENV_SUBBATCH) > 0) net->subbatch = env_int(ENV_SUBBATCH);
+    net->fused_enabled = env_flag(ENV_FUSED_HEAD);
     if (!build_graph(*net)) { delete net; return SNCAL_ERR_STATE; }
     *out = net;
     return SNCAL_OK;

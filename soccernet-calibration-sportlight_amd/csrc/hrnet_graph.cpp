@@ -217,6 +217,7 @@ struct Builder {
         int x = conv(P + "conv2", t_stem, true);
         for (int b = 0; b < d.stage1_blocks; ++b) x = bottleneck(fmt("%slayer1.%d", P.c_str(), b), x);
         std::vector<int> ys{x};
+        const bool group_convs = env_flag(ENV_GROUP_CONVS);      // read per net: tests toggle it
         for (int si = 0; si < 3; ++si) {
             const int nb = d.num_branches[si];
             const std::string tn = fmt("%stransition%d", P.c_str(), si + 1);
@@ -236,7 +237,6 @@ struct Builder {
                 // Branch 0 keeps block order (its conv pairs are pattern-matched into the fused BasicBlock kernel of the
                 // bf16 path).  The other branches are emitted depth-major: the same-depth convs of branches 1..nb-1 are
                 // independent and adjacent, so the executor can put them into ONE grouped launch (conv.hpp).
-                const bool group_convs = !(getenv("SNCAL_GROUP_CONVS") && atoi(getenv("SNCAL_GROUP_CONVS")) == 0);     // read per net: tests toggle it
                 bool plain = true;
                 for (int br = 0; br < nb; ++br)
                     for (int b = 0; b < d.num_blocks[si]; ++b)
@@ -270,7 +270,7 @@ struct Builder {
                     }
                     if (has_up) {
                         std::vector<int> ups;
-                        const bool grp = !(getenv("SNCAL_GROUP_CONVS") && atoi(getenv("SNCAL_GROUP_CONVS")) == 0) && nb - i - 1 >= 2;
+                        const bool grp = group_convs && nb - i - 1 >= 2;
                         const int gid = grp ? net.n_launch_groups++ : -1;      // the 1x1 convs of one fuse-up sum are independent
                         for (int j = i + 1; j < nb; ++j) {
                             ups.push_back(conv(fmt("%s.fuse_layers.%d.%d.0", mn.c_str(), i, j), xs[j], false));

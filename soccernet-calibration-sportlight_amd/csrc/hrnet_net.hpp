@@ -168,7 +168,7 @@ struct sncal_hrnet {
     // generic fp32 kernels -- the 784 -> 784 product at 270x480 (31 % of the reference's MACs) shrinks ninefold
     bool has_split = false, use_split = false;
     // wide 3x3 stride-1 convolutions (96 / 192 / 384 channels) on the two-team persistent kernel (conv_tt.hip), bf16 path
-    bool use_conv_tt = getenv("SNCAL_CONV_TT") ? atoi(getenv("SNCAL_CONV_TT")) != 0 : true;
+    bool use_conv_tt = sncal::env_flag(sncal::ENV_CONV_TT);
     std::vector<sncal::Schedule> schedules;      // per sub-batch size at the current layout (SB and the last sub-batch's), dropped with the layout
     int n_cus = 0;                        // compute units of the device (queried at finalize)
     // C5: fp8 (OCP e4m3) arithmetic for the wide 3x3 stride-1 convolutions, everything else as the bf16 engine
@@ -181,9 +181,9 @@ struct sncal_hrnet {
     unsigned* d_amax = nullptr;               // calibration: per-tensor max |x| (float bit patterns)
     std::vector<char> need_bf16;              // per tensor: some active consumer reads the bf16 tensor
     std::vector<int> producer;                // per tensor: active op that writes it
-    bool fuse_bblock = getenv("SNCAL_FUSE_BBLOCK") ? atoi(getenv("SNCAL_FUSE_BBLOCK")) != 0 : true;   // 48-channel BasicBlocks as one kernel (bblock.hip), bf16 path
+    bool fuse_bblock = sncal::env_flag(sncal::ENV_FUSE_BBLOCK);   // 48-channel BasicBlocks as one kernel (bblock.hip), bf16 path
     // split engines, layer1 (bneckx3.hip): bit 0 = conv3 of a Bottleneck + conv1 of the next as one pass, bit 1 = block 0's downsample branch inside its conv3
-    int fuse_bneck = sncal::env_int("SNCAL_FUSE_BNECK", 3);
+    int fuse_bneck = sncal::env_int(sncal::ENV_FUSE_BNECK);
     sncal::DevBuf head_packed[sncal::HPK_COUNT];
     int head_ks16 = 0;
     float *d_hb0 = nullptr, *d_hb1 = nullptr;

@@ -72,10 +72,7 @@ Prep prep_in(const sncal_hrnet& net, const Schedule& s, const Op& op) {
     return L.fp8_on ? PREP_QUANT_FP8 : PREP_SPLIT_F32;
 }
 
-bool profile_detail() {          // tuning aid: one profile row per layer shape / two-team launch kind
-    static const bool detail = getenv("SNCAL_PROFILE_DETAIL") != nullptr;
-    return detail;
-}
+bool profile_detail() { return env_flag(ENV_PROFILE_DETAIL); }      // tuning aid: one profile row per layer shape / two-team launch kind
 
 // the generic kernel's variant, tile shape and dynamic LDS size for one convolution op at this layout (no launch)
 int choose_conv(const sncal_hrnet& net, const Op& op, int sb, Member& m) {
@@ -92,7 +89,7 @@ int choose_conv(const sncal_hrnet& net, const Op& op, int sb, Member& m) {
     m.lds = 0;
     m.twf = 1;
     double best_score = -1;
-    static const double three_gain = getenv("SNCAL_THREE_GAIN") ? atof(getenv("SNCAL_THREE_GAIN")) : 1.15;     // tuning aid
+    const double three_gain = 1.15;     // of a third co-resident workgroup (was a tuning aid)
     for (int v = 0; v < net.nvariants; ++v) {
         const ConvVariant& V = net.variants[v];
         if (V.ks != L.k || V.stride != L.stride || V.mi != L.mi || V.g != L.g) continue;
@@ -157,7 +154,7 @@ int tt_cfg(const sncal_hrnet& net, const Op* ops, int n, int sb) {
     const ConvLayer& L0 = net.layers[ops[0].conv];
     if (!L0.x3_on) return 0;
     if (n == 1 && L0.x3_blk == 64) return 1;
-    const int per_team = env_int("SNCAL_TT_SMALL_ITEMS", 2);      // (read per plan: tests run both tiles in one process; 0 = never)
+    const int per_team = env_int(ENV_TT_SMALL_ITEMS);      // (read per plan: tests run both tiles in one process; 0 = never)
     long items = 0;
     for (int i = 0; i < n; ++i) {
         const Tensor& ti = net.tensors[ops[i].in];
@@ -354,18 +351,16 @@ void profile_launch(const sncal_hrnet& net, const Schedule& s, Launch& e) {
 // completes them), else fused with the log-softmax (the (B,C,h,w) tensor is never written; its workspace slot serves as the much smaller
 // scratch), else after a plain softmax.
 DecodeAt decode_at(const sncal_hrnet& net, const Schedule& s) {
-    static const bool fuse_decode = !(getenv("SNCAL_FUSE_DECODE") && atoi(getenv("SNCAL_FUSE_DECODE")) == 0);
-    static const bool head_decode = !(getenv("SNCAL_HEAD_DECODE") && atoi(getenv("SNCAL_HEAD_DECODE")) == 0);
     const int C = net.desc.num_classes, sb = s.sb;
     const Tensor& th = net.tensors[net.t_heat];
-    if (!fuse_decode || net.desc.head_softmax) return DEC_NONE;
+    if (net.desc.head_softmax) return DEC_NONE;
     for (const Launch& e : s.launches) {
         const Op& op = net.ops[e.op];
         if (e.kind == LK_HEAD) {
             const Tensor& to = net.tensors[op.out];
             HeadParams hp;
             head_params(net, op, sb, hp);
-            if (head_decode && C > 32 && C <= 64 && (net.x3 ? headx3_applies(hp) : head32_applies(hp)) &&
+            if (C > 32 && C <= 64 && (net.x3 ? headx3_applies(hp) : head32_applies(hp)) &&
                 head32_decode_scratch(sb, C, to.H, to.W) <= to.bytes && th.H == to.H && th.W == to.W) return DEC_HEAD;
         }
         if (e.kind == LK_TAIL) {

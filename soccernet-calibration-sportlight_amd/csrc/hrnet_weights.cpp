@@ -34,10 +34,6 @@ void choose_packing(sncal_hrnet& net, ConvLayer& L) {
     for (int v = 0; v < net.nvariants; ++v) {
         const ConvVariant& V = net.variants[v];
         if (V.ks != L.k || V.stride != L.stride) continue;
-        { static const int force_mi_s2 = env_int("SNCAL_FORCE_MI_S2", 0);     // tuning aids
-          if (force_mi_s2 && L.k == 3 && L.stride == 2 && L.cin_phys >= 48 && V.mi != force_mi_s2 && cout_frags % force_mi_s2 == 0) continue; }
-        { static const int force_g_s2 = env_int("SNCAL_FORCE_G_S2", 0);
-          if (force_g_s2 && L.k == 3 && L.stride == 2 && L.cin_phys >= 48 && V.g != force_g_s2) continue; }
         const ConvPackShape s{L.cin, L.cin_phys, L.cout, L.k, ge, V.mi, V.g};
         const int chunks = s.chunks(), nblk = s.nblk();
         const int nks = conv_nks(V.ks, V.g);
@@ -160,12 +156,10 @@ int derive_head_slices(sncal_hrnet& net) {
 // (running_var ~ 0 -> scale gamma / sqrt(eps) = 316 gamma) into its weights.  So the engine refuses what it cannot represent instead of
 // clamping it silently (x3_split_host saturates): any folded weight beyond 65504, or a layer whose weights sit so low that most of its
 // weight mass has lost more than half of the 22 bits (|w| < 2^-14: hi itself is subnormal).  The caller falls back to dtype fp32
-// (load_model does it by itself and says so).  SNCAL_X3_RANGE_CHECK=0 switches the refusal off (tests of the run-time range flag).
+// (load_model does it by itself and says so).  Nothing switches the refusal off.
 int x3_range_check(const sncal_hrnet& net) {
 #if SNCAL_X3_F16
     if (!net.x3) return SNCAL_OK;
-    static const bool off = getenv("SNCAL_X3_RANGE_CHECK") && atoi(getenv("SNCAL_X3_RANGE_CHECK")) == 0;
-    if (off) return SNCAL_OK;
     for (const ConvLayer& L : net.layers) {
         if (!L.is_set || L.w.empty()) continue;
         const size_t per = L.w.size() / (size_t)L.cout;

@@ -532,11 +532,6 @@ extern "C" int sncal_calibrate_workspace(int B, const sncal_voter_cfg* cfg, size
     return SNCAL_OK;
 }
 
-static bool env_off(const char* name) {      // NAME=0 switches a default off (the tuning aids / A-B references below)
-    const char* v = getenv(name);
-    return v && atoi(v) == 0;
-}
-
 static int calibrate_impl(const float* d_kpts, const float* d_line_pts, int B, const sncal_voter_cfg* cfg,
                           sncal_camera* d_out, void* d_ws, size_t ws_bytes, bool own_ws, void* stream) {
     SNCAL_CHECK_ARG(B >= 0 && cfg, "sncal_calibrate: bad arguments");
@@ -554,7 +549,7 @@ static int calibrate_impl(const float* d_kpts, const float* d_line_pts, int B, c
     hipStream_t st = sncal::as_stream(stream);
     // Every workgroup of the default path is ONE wavefront (first_pass_task_kernel above says why); SNCAL_SOLVE_WAVE_WGS=0 (tuning
     // aid / A-B reference, also what the byte-identity test compares with): round 4's paired 256-thread calibrate_kernel
-    static const bool wave_wgs = !env_off("SNCAL_SOLVE_WAVE_WGS");
+    const bool wave_wgs = sncal::env_flag(sncal::ENV_SOLVE_WAVE_WGS);
     const bool paired = cfg->algorithm <= 1;
     // scratch: the first pass's per-frame slots, then the voter's per-(frame, threshold) slots -- the caller's workspace
     // (sncal_calibrate_ws) or the stream's own block (sncal_calibrate)
@@ -584,8 +579,7 @@ static int calibrate_impl(const float* d_kpts, const float* d_line_pts, int B, c
     if (defer) {
         // one wavefront per (frame, threshold, camera) of the pending frames, then the selection in the reference's order.
         // SNCAL_SOLVE_TASKS=0 (tuning aid / A-B reference): the four-wave voter_kernel, thresholds one after the other
-        static const bool tasks = !env_off("SNCAL_SOLVE_TASKS");
-        if (tasks) {
+        if (sncal::env_flag(sncal::ENV_SOLVE_TASKS)) {
             VoterShared* slots = reinterpret_cast<VoterShared*>(scratch + fp_bytes);
             hipLaunchKernelGGL(voter_task_kernel, dim3((unsigned)(B * cfg->n_conf_threshs * VT_TASKS)), dim3(64), 0, st, d_kpts, d_line_pts, B, *cfg,
                                (const sncal_camera*)d_out, slots);
@@ -689,8 +683,8 @@ extern "C" int sncal_calibrate_sweep(const float* d_kpts, const float* d_line_pt
 }
 
 static int env_schedule() {      // SNCAL_SOLVE_SCHEDULE=converged: the two single-camera entries on the run-to-convergence minimisers
-    static const int v = (getenv("SNCAL_SOLVE_SCHEDULE") && std::string(getenv("SNCAL_SOLVE_SCHEDULE")) == "converged") ? SCHED_CONVERGED : SCHED_OPENCV;
-    return v;
+    const char* v = sncal::env_str(sncal::ENV_SOLVE_SCHEDULE);
+    return v && !strcmp(v, "converged") ? SCHED_CONVERGED : SCHED_OPENCV;
 }
 
 static int launch_pnp(const double* d_K, const double* d_pts3d, const double* d_pts2d, const int32_t* d_npts, int B, int N,
