@@ -61,7 +61,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 
 // element tag of the bf16x3 engine's generic convolutions: fp32 tensors staged exactly like the float variant, multiplied in split-bf16
-// arithmetic (x = hi + lo bf16, y = hi.hi + hi.lo + lo.hi in fp32 -- conv_tt_body.inc MODE 2 has the numbers).  The packed weights hold
+// arithmetic (x = hi + lo bf16, y = hi.hi + hi.lo + lo.hi in fp32 -- conv_tt_kernel.hpp MODE 2 has the numbers).  The packed weights hold
 // [4 hi | 4 lo] bf16 in the 16 bytes where the float variant holds 4 fp32; a B fragment (4 fp32 of one k-group) is split in registers.
 struct x3_t {};
 template <typename T> struct Elem;
@@ -726,7 +726,7 @@ __device__ __forceinline__ void conv_body(const ConvParams& p, const unsigned w)
             if (p.relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
             if constexpr (Elem<T>::X3) {
                 x3_track(amax, v0, v1); x3_track(amax, v2, v3);              // every OUTPUT is tracked where it is produced (x3.hpp)
-                // [16 hi | 16 lo] bf16 per pixel and 16-channel group (conv_tt_body.inc): this lane's 4 channels are 8 + 8 bytes
+                // [16 hi | 16 lo] bf16 per pixel and 16-channel group (conv_tt_kernel.hpp): this lane's 4 channels are 8 + 8 bytes
                 if (p.out_twin) {
                     const float v[4] = {v0, v1, v2, v3};
                     x3h4 th, tl;

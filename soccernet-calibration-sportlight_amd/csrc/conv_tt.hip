@@ -32,84 +32,33 @@
 // half-wave) then touches 16 distinct 16-byte bank slots (enumerated against MI355X_MICROARCH.md "LDS"), without the 50 % pitch padding of the generic kernel; the
 // rotation is applied on the DMA's per-lane SOURCE address, the LDS destination stays lane-linear.
 // Work items (tile x 96-channel block, cost = Cin / 32 stages) of up to three member convolutions are dealt to the
-// 2 x 256 teams on the host (conv_tt_plan in hrnet.cpp): contiguous slices per XCD, longest-processing-time first.
-#include "persist.hpp"
-#include "conv_tt.hpp"
-#include "x3.hpp"
-#include <cstddef>
+// 2 x 256 teams on the host (tt_plan_items, conv_tt.hpp): contiguous slices per XCD, longest-processing-time first.
+#include "conv_tt_kernel.hpp"
 
 namespace sncal {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((address_space(3))) void lds_void;
-
-// member m's parameters straight from the kernel-argument segment, by scalar loads at a computed offset (selecting among three
-// by-value copies of the argument keeps ~80 SGPRs alive and spills; a dynamically indexed argument is copied to scratch)
-__device__ __forceinline__ TTMember load_member(int m) {
-    TTMember r;
-#if defined(__HIP_DEVICE_COMPILE__)
-    static_assert(sizeof(TTMember) % 4 == 0 && offsetof(TTParams, m) == 0, "the members must open the kernel-argument segment");
-    const __attribute__((address_space(4))) unsigned* src =
-        (const __attribute__((address_space(4))) unsigned*)__builtin_amdgcn_kernarg_segment_ptr() + m * (int)(sizeof(TTMember) / 4);
-    unsigned* dst = reinterpret_cast<unsigned*>(&r);
-#pragma unroll
-    for (unsigned i = 0; i < sizeof(TTMember) / 4; ++i) dst[i] = src[i];
-#else
-    (void)m;
-    r = TTMember{};
-#endif
-    return r;
-}
-
-// ---- tile configurations: (MB, NB) = (3, 2): 96 output channels x 8 stacked rows x 32 columns, every mode;
-//      (2, 3): 64 x 12 x 32 for the bf16x3 engine's 48-channel branch (25 % instead of 50 % of padded rows)
-#define TT_CFG_NS c32
-#define TT_CFG_MB 3
-#define TT_CFG_NB 2
-#include "conv_tt_body.inc"
-#undef TT_CFG_NS
-#undef TT_CFG_MB
-#undef TT_CFG_NB
-#define TT_CFG_NS c23
-#define TT_CFG_MB 2
-#define TT_CFG_NB 3
-#include "conv_tt_body.inc"
-#undef TT_CFG_NS
-#undef TT_CFG_MB
-#undef TT_CFG_NB
-
-// (3, 1): 96 x 4 x 32, split arithmetic only -- SMALL launches (round 5).  Below about two items per team the launch lasts as long as its
+// ---- the instantiated (tile, mode) pairs.  TT_TILE_96x8 runs every mode; TT_TILE_64x12 is the bf16x3 engine's 48-channel branch (25 %
+//      instead of 50 % of padded rows).
+// TT_TILE_96x4, split arithmetic only -- SMALL launches (round 5).  Below about two items per team the launch lasts as long as its
 // longest item (twelve stages on the 384-channel branch) while most teams hold three-stage items or nothing: at batch 8, 98 us per
 // grouped launch for 40 us of work per team.  Half the rows per item = twice the items at half a stage's multiplies each; the weight
 // stream per stage is the same (L2 serves it; at these sizes nothing is bandwidth-bound).
-#define TT_CFG_NS c31
-#define TT_CFG_MB 3
-#define TT_CFG_NB 1
-#include "conv_tt_body.inc"
-#undef TT_CFG_NS
-#undef TT_CFG_MB
-#undef TT_CFG_NB
+struct TTKernel { TTTile tile; int mode; void (*kernel)(const TTParams); };
+static const TTKernel tt_kernels[] = {
+    {TT_TILE_96x8, 0, conv_tt_kernel<3, 2, 0>}, {TT_TILE_96x8, 1, conv_tt_kernel<3, 2, 1>}, {TT_TILE_96x8, 2, conv_tt_kernel<3, 2, 2>},
+    {TT_TILE_64x12, 2, conv_tt_kernel<2, 3, 2>}, {TT_TILE_96x4, 2, conv_tt_kernel<3, 1, 2>},
+};
 
-void launch_conv_tt(const TTParams& p, int n_wgs, int mode, hipStream_t s, int cfg) {
-    opt_in_lds<&c32::conv_tt_kernel<0>, &c32::conv_tt_kernel<1>, &c32::conv_tt_kernel<2>, &c23::conv_tt_kernel<2>, &c31::conv_tt_kernel<2>>(160 * 1024);
-    if (cfg == 2) {                                    // 96 output channels x 4 rows x 32 columns (split arithmetic, small launches)
-        const size_t lds = (size_t)2 * c31::TEAM_BYTES + 64 + 2 * TT_TABLE_MAX * 4;
-        SNCAL_LAUNCH(c31::conv_tt_kernel<2>, dim3((unsigned)n_wgs), dim3(512), lds, s, p);
-        return;
-    }
-    if (cfg == 1) {                                    // 64 output channels x 12 rows x 32 columns (bf16x3: the 48-channel branch)
-        const size_t lds = (size_t)2 * c23::TEAM_BYTES + 64 + 2 * TT_TABLE_MAX * 4;
-        SNCAL_LAUNCH(c23::conv_tt_kernel<2>, dim3((unsigned)n_wgs), dim3(512), lds, s, p);
-        return;
-    }
-    const size_t lds = (size_t)2 * c32::TEAM_BYTES + 64 + 2 * TT_TABLE_MAX * 4;
-    if (mode == 1) SNCAL_LAUNCH(c32::conv_tt_kernel<1>, dim3((unsigned)n_wgs), dim3(512), lds, s, p);
-    else if (mode == 2) SNCAL_LAUNCH(c32::conv_tt_kernel<2>, dim3((unsigned)n_wgs), dim3(512), lds, s, p);
-    else SNCAL_LAUNCH(c32::conv_tt_kernel<0>, dim3((unsigned)n_wgs), dim3(512), lds, s, p);
+int launch_conv_tt(const TTParams& p, int n_wgs, int mode, hipStream_t s, TTTile tile) {
+    if (!opt_in_lds<&conv_tt_kernel<3, 2, 0>, &conv_tt_kernel<3, 2, 1>, &conv_tt_kernel<3, 2, 2>, &conv_tt_kernel<2, 3, 2>, &conv_tt_kernel<3, 1, 2>>(160 * 1024))
+        return SNCAL_ERR_HIP;
+    for (const TTKernel& k : tt_kernels)
+        if (k.tile == tile && k.mode == mode) {
+            SNCAL_LAUNCH(k.kernel, dim3((unsigned)n_wgs), dim3(512), (size_t)TT_TILES[tile].lds_bytes, s, p);
+            return SNCAL_OK;
+        }
+    set_error("conv_tt: no kernel for tile %d in mode %d", (int)tile, mode);
+    return SNCAL_ERR_ARG;
 }
 
 }  // namespace sncal

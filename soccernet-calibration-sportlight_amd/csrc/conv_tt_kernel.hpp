@@ -1,22 +1,37 @@
-// Body of the two-team kernel, included by conv_tt.hip once per tile configuration (TT_CFG_NS / TT_CFG_MB / TT_CFG_NB).
-namespace TT_CFG_NS {
-// tile of this instantiation: MB 32-channel blocks x (4 NB) stacked rows x 32 columns per team; a wave owns NB rows
-constexpr int MB = TT_CFG_MB, NB = TT_CFG_NB, NT = 18;          // 32-channel blocks, 32-pixel blocks (= tile rows) per wave, K = 16 steps per stage
-constexpr int COUT_BLK = 32 * MB, TILE_H = 4 * NB;
-constexpr int NKS = 9, MI = 2 * MB;                     // taps; 1 KB weight pieces per tap
-constexpr int W_BYTES = NKS * MI * 1024;            // one stage of weights, fragment order [k-step][mi][lane] x 16 B
-constexpr int HP = 36;                              // halo row pitch in pixels (34 used)
-constexpr int HROWS = TILE_H + 2;
-constexpr int HALO_PIECES = (HROWS * HP * 64 + 1023) / 1024;    // DMA pieces of 1 KB
-constexpr int HV = (HALO_PIECES + 3) / 4;           // ... per wave
-constexpr int H_BYTES = HALO_PIECES * 1024;
-constexpr int TEAM_BYTES = W_BYTES + H_BYTES;       // (3, 2): 78848, two teams = 157696 B of the CU's 163840; (2, 3): 69632
-// weight pieces per wave: wave tw owns a CONTIGUOUS block [wp_first(tw), wp_first(tw + 1)), because the wave also stages its epilogue there
-__device__ __host__ constexpr int wp_first(int tw) { return tw * (NKS * MI) / 4; }
-constexpr int EPI_PITCH = COUT_BLK + 4;             // floats per staged pixel row
-constexpr int EPI_GROUPS = COUT_BLK / 8, EPI_ITEMS = 32 * EPI_GROUPS, EPI_ITERS = EPI_ITEMS / 64;
-static_assert(wp_first(4) == NKS * MI && 32 * EPI_PITCH * 4 <= (NKS * MI / 4) * 1024 && EPI_ITEMS % 64 == 0 && 2 * TEAM_BYTES + 64 + 2 * TT_TABLE_MAX * 4 <= 160 * 1024,
-              "a wave's epilogue staging must fit its own block of the weight region; two teams fit the CU's LDS");
+// The two-team kernel (conv_tt.hip has the design): one template over the tile shape (MB, NB -- TTShape<MB, NB>, conv_tt.hpp, owns the
+// geometry) and the arithmetic mode.
+#pragma once
+#include "persist.hpp"
+#include "conv_tt.hpp"
+#include "x3.hpp"
+#include <cstddef>
+
+namespace sncal {
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef __attribute__((address_space(3))) void lds_void;
+
+// member m's parameters straight from the kernel-argument segment, by scalar loads at a computed offset (selecting among three
+// by-value copies of the argument keeps ~80 SGPRs alive and spills; a dynamically indexed argument is copied to scratch)
+__device__ __forceinline__ TTMember load_member(int m) {
+    TTMember r;
+#if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(sizeof(TTMember) % 4 == 0 && offsetof(TTParams, m) == 0, "the members must open the kernel-argument segment");
+    const __attribute__((address_space(4))) unsigned* src =
+        (const __attribute__((address_space(4))) unsigned*)__builtin_amdgcn_kernarg_segment_ptr() + m * (int)(sizeof(TTMember) / 4);
+    unsigned* dst = reinterpret_cast<unsigned*>(&r);
+#pragma unroll
+    for (unsigned i = 0; i < sizeof(TTMember) / 4; ++i) dst[i] = src[i];
+#else
+    (void)m;
+    r = TTMember{};
+#endif
+    return r;
+}
 
 // bf16x3: channel (inside its 32-channel block) of the first of the 4 accumulator registers of quad q in lane half hi.  The natural MFMA
 // order is 8 q + 4 hi; the x3 weights are packed with rows permuted (ttx3_pack_weights, conv_tt.hpp) so that it is 16 (q / 2) + 8 hi +
@@ -30,6 +45,145 @@ static_assert([] {
     return true;
 }(), "the epilogue's channel of an accumulator register is the packer's channel of that MFMA row (h32_row_channel, pack.hpp)");
 
+// The MULTIPLY phase of one stage: the wave's MB x NB accumulators += the stage in LDS.  aptr: this lane's 16 bytes of the first weight
+// piece; bptr[dx][k]: the lane-dependent part of its B fragment addresses (the kernel has the layout); near_end() runs shortly before the
+// last MFMAs are issued (the team hands the CU's multiply token on there).
+template <int MB, int NB, int MODE, class F>
+__device__ __forceinline__ void tt_multiply_stage(f32x16 (&acc)[MB][NB], const char* const aptr, const char* (&bptr)[3][4], F&& near_end) {
+    using S = TTShape<MB, NB>;
+    constexpr bool FP8 = MODE == 1, X3 = MODE == 2;
+    constexpr int NKS = S::NKS, NT = S::NT, HP = S::HP;
+    // pin the accumulators where they are: without this hipcc copies the 96 registers on entry (two reaching
+    // definitions: the start value of a new item / the previous stage) and spills some of the originals around the phase
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+        for (int jr = 0; jr < NB; ++jr) asm volatile("" : "+v"(acc[mb][jr]));
+    if constexpr (FP8) {
+        // fp8 stage = 64 input channels: 9 K = 64 steps (one per tap) x 6 v_mfma_scale_f32_32x32x64_f8f6f4 with unit block
+        // scales (E8M0 127).  Lane l holds 32 consecutive K bytes of row / column l & 31: channels 32 (l >> 5) .. + 31 of
+        // the tap = two 16-byte slots of the pixel, two lane-linear 1 KB pieces of the weights (layout probed on hardware:
+        // tools/dev/mx_probe.hip).
+        i32x8 a[2][MB], b[2][NB];
+        auto load_frags = [&](int s, int buf) {
+            const int dy = s / 3, dx = s - dy * 3;
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb) {
+                const i32x4 lo = *reinterpret_cast<const i32x4*>(aptr + ((s * MB + mb) * 2 + 0) * 1024);
+                const i32x4 hi4 = *reinterpret_cast<const i32x4*>(aptr + ((s * MB + mb) * 2 + 1) * 1024);
+                a[buf][mb] = i32x8{lo[0], lo[1], lo[2], lo[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+            }
+#pragma unroll
+            for (int jr = 0; jr < NB; ++jr) {
+                const i32x4 lo = *reinterpret_cast<const i32x4*>(bptr[dx][(jr + dy) & 3] + (jr + dy) * HP * 64);
+                const i32x4 hi4 = *reinterpret_cast<const i32x4*>(bptr[dx][(jr + dy + 1) & 3] + (jr + dy) * HP * 64);
+                b[buf][jr] = i32x8{lo[0], lo[1], lo[2], lo[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+            }
+        };
+        load_frags(0, 0);
+#pragma unroll
+        for (int t = 0; t < NKS; ++t) {
+            const int cur = t & 1;
+            if (t + 1 < NKS) {
+                load_frags(t + 1, cur ^ 1);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                for (int jr = 0; jr < NB; ++jr)
+                    acc[mb][jr] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[cur][mb], b[cur][jr], acc[mb][jr], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+            // anchor the step: hipcc sinks the scaled MFMAs of ALL steps below the last reads otherwise (sched_barrier does
+            // not hold them), keeps nine steps of fragments alive and spills ~290 registers
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                for (int jr = 0; jr < NB; ++jr) asm volatile("" : "+v"(acc[mb][jr]) :: "memory");
+            if (t + 1 < NKS) __builtin_amdgcn_sched_barrier(0);
+        }
+        near_end();
+    } else if constexpr (X3) {
+        // 9 taps x (10 fragment reads, 18 MFMAs): K-step h = 0 holds the hi parts, h = 1 the lo parts of the stage's 16 channels;
+        // acc += w_lo.x_hi + w_hi.x_lo + w_hi.x_hi (small terms first).  Fragments of tap s + 1 are fetched while tap s multiplies.
+        x3h8 a[2][2][MB], b[2][2][NB];
+        // the 2 (MB + NB) fragment reads of a tap in three parts, one per term group of the tap before it (below)
+        constexpr int NFR = 2 * (MB + NB);
+        auto load_part = [&](int sidx, int buf, int part) __attribute__((always_inline)) {
+            const int dy = sidx / 3, dx = sidx - dy * 3;
+#pragma unroll
+            for (int i = part * NFR / 3; i < (part + 1) * NFR / 3; ++i) {
+                const int h = i / (MB + NB), r = i - h * (MB + NB);
+                if (r < MB) a[buf][h][r] = *reinterpret_cast<const x3h8*>(aptr + ((2 * sidx + h) * MB + r) * 1024);
+                else b[buf][h][r - MB] = *reinterpret_cast<const x3h8*>(bptr[dx][(r - MB + dy + 2 * h) & 3] + (r - MB + dy) * HP * 64);
+            }
+        };
+#pragma unroll
+        for (int part = 0; part < 3; ++part) load_part(0, 0, part);
+#pragma unroll
+        for (int sidx = 0; sidx < NKS; ++sidx) {
+            const int cur = sidx & 1;
+            if (sidx == NKS - 1) near_end();
+            // Term by term over the MB x NB accumulators, NOT three terms per accumulator in a row, and every group fenced: an
+            // instruction between two MFMAs on the SAME accumulator costs ~43 clk (MI355X_MICROARCH.md), between MFMAs on different ones
+            // ~6 -- and the next tap's fragment reads sit between these MFMAs (left alone, hipcc's scheduler clusters the three
+            // MFMAs of an accumulator and drops the reads in between).  Per accumulator the order of the terms is unchanged (small
+            // terms first): same bits.
+#pragma unroll
+            for (int term = 0; term < 3; ++term) {
+                constexpr int NR = NFR / 3 + 1;
+                if (sidx + 1 < NKS) load_part(sidx + 1, cur ^ 1, term);
+#pragma unroll
+                for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                    for (int jr = 0; jr < NB; ++jr)
+                        acc[mb][jr] = X3_MFMA_32x32x16(a[cur][term == 0 ? 1 : 0][mb], b[cur][term == 1 ? 1 : 0][jr], acc[mb][jr]);
+                if (sidx + 1 < NKS) {                          // one fragment read behind each of the group's first MFMAs
+#pragma unroll
+                    for (int i = 0; i < NR; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    }
+                    __builtin_amdgcn_sched_group_barrier(0x008, MB * NB - NR, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    } else {
+        // 18 K = 16 steps (tap, channel half) x 6 MFMAs of 32 x 32 x 16; fragments of step t + 1 are fetched while step t
+        // multiplies.  `near_end` runs before the last two steps (the token is handed on while ~400 clk of MFMAs are queued).
+        bf16x8 a[2][MB], b[2][NB];
+        auto load_frags = [&](int t, int buf) {
+            const int s = t >> 1, h = t & 1, dy = s / 3, dx = s - dy * 3;
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb) a[buf][mb] = *reinterpret_cast<const bf16x8*>(aptr + (t * MB + mb) * 1024);
+#pragma unroll
+            for (int jr = 0; jr < NB; ++jr)
+                b[buf][jr] = *reinterpret_cast<const bf16x8*>(bptr[dx][(jr + dy + 2 * h) & 3] + (jr + dy) * HP * 64);
+        };
+        load_frags(0, 0);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const int cur = t & 1;
+            if (t == NT - 2) near_end();
+            if (t + 1 < NT) load_frags(t + 1, cur ^ 1);
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                for (int jr = 0; jr < NB; ++jr)
+                    acc[mb][jr] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][mb], b[cur][jr], acc[mb][jr], 0, 0, 0);
+            if (t + 1 < NT) {                                  // one fragment read behind each of the first five MFMAs of the step
+#pragma unroll
+                for (int i = 0; i < MB + NB; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                }
+                __builtin_amdgcn_sched_group_barrier(0x008, MB * NB - (MB + NB), 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+}
+
 // FP8 = false: bf16 operands, v_mfma_f32_32x32x16_bf16, stages of 32 input channels.
 // FP8 = true (BASELINE config C5): OCP e4m3 operands -- the input is the e4m3 twin of the activation tensor (per-tensor scale),
 // the weights carry one scale per output channel -- on v_mfma_scale_f32_32x32x64_f8f6f4 with unit block scales: stages of 64
@@ -42,8 +196,11 @@ static_assert([] {
 // |dlogp| 5e-6 mean / 1.4e-4 max, identical keypoint indices on every row.  The operand tensors are "split twins": per pixel and
 // 16-channel group [16 hi | 16 lo] bf16 -- byte for byte a bf16 tensor of 2 C pseudo-channels, so the halo / weight staging of the
 // bf16 mode is used unchanged (a stage = 16 real channels); only the MFMA pairing and the fp32 epilogue differ.
-template <int MODE>
+template <int MB, int NB, int MODE>
 __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
+    using S = TTShape<MB, NB>;
+    constexpr int COUT_BLK = S::COUT_BLK, W_BYTES = S::W_BYTES, HP = S::HP, HROWS = S::HROWS, HALO_PIECES = S::HALO_PIECES, HV = S::HV;
+    constexpr int TEAM_BYTES = S::TEAM_BYTES, EPI_PITCH = S::EPI_PITCH, EPI_GROUPS = S::EPI_GROUPS, EPI_ITERS = S::EPI_ITERS;
     constexpr bool FP8 = MODE == 1, X3 = MODE == 2;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
@@ -245,14 +402,18 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
         // (weights first: requesting the halo pieces first -- they come from HBM / the Infinity Cache, the weights from L2 -- was measured
         // 1.3 % slower on the fp16x3 step, round 4)
         const unsigned wbase = (unsigned)((nb * M.chunks + cc) * W_BYTES);
-        const int i1 = wp_first(tw + 1);
-        for (int i = wp_first(tw); i < i1; ++i)
+        const int i1 = S::wp_first(tw + 1);
+        for (int i = S::wp_first(tw); i < i1; ++i)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void*)(s_w + i * 1024), 16, (unsigned)(lane * 16), wbase + i * 1024, 0, 0);
         const unsigned cbase = (unsigned)(cc * 64);
 #pragma unroll
         for (int jj = 0; jj < HV; ++jj)
-            if (tw + 4 * jj < HALO_PIECES)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_void*)(s_h + (tw + 4 * jj) * 1024), 16, hv[jj], cbase, 0, 0);
+            if (tw + 4 * jj < HALO_PIECES) {
+                // (a named copy: with hv[jj] -- an array whose bound depends on the template parameters -- as the builtin's argument, hipcc
+                // 7.2's HOST pass silently emits no stub for the kernel and the library has an undefined symbol)
+                const unsigned voff = hv[jj];
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_in, (lds_void*)(s_h + (tw + 4 * jj) * 1024), 16, voff, cbase, 0, 0);
+            }
     };
 
     // (+ residual) (ReLU) -> bf16, through a wave-private LDS transpose so that every lane stores 8 consecutive channels.
@@ -277,7 +438,7 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
         estamp();
         int lane_l = lane;
         asm volatile("" : "+v"(lane_l));
-        float* const stg = reinterpret_cast<float*>(s_w + wp_first(tw) * 1024);
+        float* const stg = reinterpret_cast<float*>(s_w + S::wp_first(tw) * 1024);
         estamp();
 #pragma unroll
         for (int jr = 0; jr < NB; ++jr) {
@@ -399,7 +560,7 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
                 if (has_res) rr[jr][e] = __builtin_amdgcn_raw_buffer_load_b128(rs_res, voff[jr][e], soff[jr], 0);     // wave-uniform branch
             }
         }
-        float* const stg = reinterpret_cast<float*>(s_w + wp_first(tw) * 1024);      // this wave's own block of the weight region
+        float* const stg = reinterpret_cast<float*>(s_w + S::wp_first(tw) * 1024);      // this wave's own block of the weight region
         estamp();
 #pragma unroll
         for (int jr = 0; jr < NB; ++jr) {
@@ -463,138 +624,6 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
             }
         }
         estamp();
-    };
-
-    auto multiply_stage = [&](auto&& near_end) {
-        // pin the accumulators where they are: without this hipcc copies the 96 registers on entry (two reaching
-        // definitions: the start value of a new item / the previous stage) and spills some of the originals around the phase
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-            for (int jr = 0; jr < NB; ++jr) asm volatile("" : "+v"(acc[mb][jr]));
-        if constexpr (FP8) {
-            // fp8 stage = 64 input channels: 9 K = 64 steps (one per tap) x 6 v_mfma_scale_f32_32x32x64_f8f6f4 with unit block
-            // scales (E8M0 127).  Lane l holds 32 consecutive K bytes of row / column l & 31: channels 32 (l >> 5) .. + 31 of
-            // the tap = two 16-byte slots of the pixel, two lane-linear 1 KB pieces of the weights (layout probed on hardware:
-            // tools/dev/mx_probe.hip).
-            i32x8 a[2][MB], b[2][NB];
-            auto load_frags = [&](int s, int buf) {
-                const int dy = s / 3, dx = s - dy * 3;
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb) {
-                    const i32x4 lo = *reinterpret_cast<const i32x4*>(aptr + ((s * MB + mb) * 2 + 0) * 1024);
-                    const i32x4 hi4 = *reinterpret_cast<const i32x4*>(aptr + ((s * MB + mb) * 2 + 1) * 1024);
-                    a[buf][mb] = i32x8{lo[0], lo[1], lo[2], lo[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-                }
-#pragma unroll
-                for (int jr = 0; jr < NB; ++jr) {
-                    const i32x4 lo = *reinterpret_cast<const i32x4*>(bptr[dx][(jr + dy) & 3] + (jr + dy) * HP * 64);
-                    const i32x4 hi4 = *reinterpret_cast<const i32x4*>(bptr[dx][(jr + dy + 1) & 3] + (jr + dy) * HP * 64);
-                    b[buf][jr] = i32x8{lo[0], lo[1], lo[2], lo[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-                }
-            };
-            load_frags(0, 0);
-#pragma unroll
-            for (int t = 0; t < NKS; ++t) {
-                const int cur = t & 1;
-                if (t + 1 < NKS) {
-                    load_frags(t + 1, cur ^ 1);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-                    for (int jr = 0; jr < NB; ++jr)
-                        acc[mb][jr] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a[cur][mb], b[cur][jr], acc[mb][jr], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-                // anchor the step: hipcc sinks the scaled MFMAs of ALL steps below the last reads otherwise (sched_barrier does
-                // not hold them), keeps nine steps of fragments alive and spills ~290 registers
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-                    for (int jr = 0; jr < NB; ++jr) asm volatile("" : "+v"(acc[mb][jr]) :: "memory");
-                if (t + 1 < NKS) __builtin_amdgcn_sched_barrier(0);
-            }
-            near_end();
-        } else if constexpr (X3) {
-            // 9 taps x (10 fragment reads, 18 MFMAs): K-step h = 0 holds the hi parts, h = 1 the lo parts of the stage's 16 channels;
-            // acc += w_lo.x_hi + w_hi.x_lo + w_hi.x_hi (small terms first).  Fragments of tap s + 1 are fetched while tap s multiplies.
-            x3h8 a[2][2][MB], b[2][2][NB];
-            // the 2 (MB + NB) fragment reads of a tap in three parts, one per term group of the tap before it (below)
-            constexpr int NFR = 2 * (MB + NB);
-            auto load_part = [&](int sidx, int buf, int part) __attribute__((always_inline)) {
-                const int dy = sidx / 3, dx = sidx - dy * 3;
-#pragma unroll
-                for (int i = part * NFR / 3; i < (part + 1) * NFR / 3; ++i) {
-                    const int h = i / (MB + NB), r = i - h * (MB + NB);
-                    if (r < MB) a[buf][h][r] = *reinterpret_cast<const x3h8*>(aptr + ((2 * sidx + h) * MB + r) * 1024);
-                    else b[buf][h][r - MB] = *reinterpret_cast<const x3h8*>(bptr[dx][(r - MB + dy + 2 * h) & 3] + (r - MB + dy) * HP * 64);
-                }
-            };
-#pragma unroll
-            for (int part = 0; part < 3; ++part) load_part(0, 0, part);
-#pragma unroll
-            for (int sidx = 0; sidx < NKS; ++sidx) {
-                const int cur = sidx & 1;
-                if (sidx == NKS - 1) near_end();
-                // Term by term over the MB x NB accumulators, NOT three terms per accumulator in a row, and every group fenced: an
-                // instruction between two MFMAs on the SAME accumulator costs ~43 clk (MI355X_MICROARCH.md), between MFMAs on different ones
-                // ~6 -- and the next tap's fragment reads sit between these MFMAs (left alone, hipcc's scheduler clusters the three
-                // MFMAs of an accumulator and drops the reads in between).  Per accumulator the order of the terms is unchanged (small
-                // terms first): same bits.
-#pragma unroll
-                for (int term = 0; term < 3; ++term) {
-                    constexpr int NR = NFR / 3 + 1;
-                    if (sidx + 1 < NKS) load_part(sidx + 1, cur ^ 1, term);
-#pragma unroll
-                    for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-                        for (int jr = 0; jr < NB; ++jr)
-                            acc[mb][jr] = X3_MFMA_32x32x16(a[cur][term == 0 ? 1 : 0][mb], b[cur][term == 1 ? 1 : 0][jr], acc[mb][jr]);
-                    if (sidx + 1 < NKS) {                          // one fragment read behind each of the group's first MFMAs
-#pragma unroll
-                        for (int i = 0; i < NR; ++i) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                        }
-                        __builtin_amdgcn_sched_group_barrier(0x008, MB * NB - NR, 0);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        } else {
-            // 18 K = 16 steps (tap, channel half) x 6 MFMAs of 32 x 32 x 16; fragments of step t + 1 are fetched while step t
-            // multiplies.  `near_end` runs before the last two steps (the token is handed on while ~400 clk of MFMAs are queued).
-            bf16x8 a[2][MB], b[2][NB];
-            auto load_frags = [&](int t, int buf) {
-                const int s = t >> 1, h = t & 1, dy = s / 3, dx = s - dy * 3;
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb) a[buf][mb] = *reinterpret_cast<const bf16x8*>(aptr + (t * MB + mb) * 1024);
-#pragma unroll
-                for (int jr = 0; jr < NB; ++jr)
-                    b[buf][jr] = *reinterpret_cast<const bf16x8*>(bptr[dx][(jr + dy + 2 * h) & 3] + (jr + dy) * HP * 64);
-            };
-            load_frags(0, 0);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int cur = t & 1;
-                if (t == NT - 2) near_end();
-                if (t + 1 < NT) load_frags(t + 1, cur ^ 1);
-#pragma unroll
-                for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-                    for (int jr = 0; jr < NB; ++jr)
-                        acc[mb][jr] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[cur][mb], b[cur][jr], acc[mb][jr], 0, 0, 0);
-                if (t + 1 < NT) {                                  // one fragment read behind each of the first five MFMAs of the step
-#pragma unroll
-                    for (int i = 0; i < MB + NB; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, MB * NB - (MB + NB), 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
     };
 
     // Both teams run the same program -- per stage: LOAD (DMA, and at an item boundary the previous tile's epilogue), team
@@ -806,7 +835,7 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
             if (lane == 0) old = __hip_atomic_fetch_add(w_early, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             if (lane == 0 && old == 4u * st + 3u) __hip_atomic_store(w_token, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         } else
-        multiply_stage([&]() {
+        tt_multiply_stage<MB, NB, MODE>(acc, aptr, bptr, [&]() {
             unsigned old = 0;
             if (lane == 0) old = __hip_atomic_fetch_add(w_early, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             if (lane == 0 && old == 4u * st + 3u) __hip_atomic_store(w_token, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -844,4 +873,4 @@ __global__ __launch_bounds__(512, 2) void conv_tt_kernel(const TTParams P) {
     if (trc && tid == team * 256) trc[255] = __builtin_amdgcn_s_memrealtime();      // the team's finish time, 100 MHz chip-wide clock (tools/tt_finish.py)
 }
 
-}  // namespace TT_CFG_NS
+}  // namespace sncal

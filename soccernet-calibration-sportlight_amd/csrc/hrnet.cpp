@@ -79,55 +79,18 @@ void tt_member(const sncal_hrnet& net, const Op& op, const Member& mem, int sb, 
     }
 }
 
-// The work items of the member convolutions as eight queues, one per XCD.  Workgroup b runs on XCD b % 8 (observed
-// dispatch rule, used for speed only): every member's items -- tile-major, the 96-channel blocks of a tile adjacent --
-// are cut into 8 contiguous slices, one per XCD, so that neighbouring tiles (shared halo rows) and the blocks of one
-// tile (same input) meet in one L2; inside an XCD's queue the members follow each other, most expensive first
-// (longest-processing-time order: the teams, which take the next item when they finish one, end within one cheap item
-// of each other).  Rounds 2-4 dealt the items to the teams HERE (static lists); a workgroup whose CU was held by a
-// camera-solve wavefront then started when the first other workgroup had finished, and the launch lasted twice as long.
+// The work lists of a two-team launch (tt_plan_items, conv_tt.hpp) on the device: static per layout, uploaded by the first launch.
 int tt_build_plan(const sncal_hrnet& net, const TTMember* mem, int n, TTPlanDev& out, hipStream_t stream) {
-    const int tile_h = out.cfg == 1 ? 12 : out.cfg == 2 ? 4 : TT_TH, cout_blk = out.cfg == 1 ? 64 : TT_COUT;
-    const int n_wgs = net.n_cus;
-    const int n_xcd = n_wgs >= 8 ? 8 : 1;                  // (fewer than 8 workgroups: every workgroup reads queue b % 8, so only queue 0.. exist)
-    std::vector<std::vector<TTItem>> per_xcd(8);
-    int order[TT_MAX_MEMBERS] = {0, 1, 2};
-    std::sort(order, order + n, [&](int a, int b) { return mem[a].chunks > mem[b].chunks; });
-    // (Interleaving the members' items, so that the memory-heavy 96-channel tiles do not all run at the tail of the launch, measured
-    // 1.4 % SLOWER than member after member: 193.3 vs 190.6 us per grouped launch; the two teams of a workgroup walking the classes in
-    // OPPOSITE order measured 1.7 % slower on the fp16x3 launches, round 4.)
-    for (int oi = 0; oi < n; ++oi) {
-        const TTMember& m = mem[order[oi]];
-        const int tiles_y = (m.N * (m.H + 1) + tile_h - 1) / tile_h, tiles_x = (m.W + TT_TW - 1) / TT_TW, nblk = (m.cout + cout_blk - 1) / cout_blk;
-        const long total = (long)tiles_y * tiles_x * nblk;
-        for (long i = 0; i < total; ++i) {
-            const int x = n_xcd == 8 ? (int)(i * 8 / total) : 0;
-            TTItem it;
-            it.member = (uint16_t)order[oi]; it.nb = (uint16_t)(i % nblk);
-            const long tile = i / nblk;
-            it.col0 = (int32_t)(tile % tiles_x) * TT_TW; it.row0 = (int32_t)(tile / tiles_x) * tile_h; it.pad_ = 0;
-            per_xcd[x].push_back(it);
-        }
-    }
-    // (Measured and not kept, round 5: the tickets of a member's slice S-way interleaved -- S = 4, 8, 16, 64 -- so that the items that share
-    // halo lines are not drawn at the same instant: 32.87 / 33.06 / 32.95 / 33.10 ms per step of two-team launches against 32.85 in
-    // tile-major order, FETCH_SIZE 434 against 410 MB per launch.  The queue's extra HBM reads over round 4's static deal -- 412 against
-    // 310 MB per grouped launch by PMC -- are not concurrent misses of neighbouring tickets.)
-    std::vector<TTItem> flat;
-    std::vector<uint32_t> first(9, 0);
-    for (int x = 0; x < 8; ++x) { first[x] = (uint32_t)flat.size(); flat.insert(flat.end(), per_xcd[x].begin(), per_xcd[x].end()); }
-    first[8] = (uint32_t)flat.size();
-    if (flat.empty()) flat.push_back(TTItem{0, 0, 0, 0, 0});
-    SNCAL_CHECK_HIP(hipMalloc((void**)&out.items, flat.size() * sizeof(TTItem)));
-    SNCAL_CHECK_HIP(hipMalloc((void**)&out.first, first.size() * 4));
+    const TTPlan plan = tt_plan_items(mem, n, out.cfg, net.n_cus);
+    SNCAL_CHECK_HIP(hipMalloc((void**)&out.items, plan.items.size() * sizeof(TTItem)));
+    SNCAL_CHECK_HIP(hipMalloc((void**)&out.first, sizeof plan.first));
     // on the forward's OWN stream, then a wait for that stream only: a plain hipMemcpy runs on the legacy null stream, which synchronises with
     // the pipeline's CU-masked (blocking) solve streams -- a new layout (the tail batch of a directory) then waited for every solve in flight
-    SNCAL_CHECK_HIP(hipMemcpyAsync(out.items, flat.data(), flat.size() * sizeof(TTItem), hipMemcpyHostToDevice, stream));
-    SNCAL_CHECK_HIP(hipMemcpyAsync(out.first, first.data(), first.size() * 4, hipMemcpyHostToDevice, stream));
-    SNCAL_CHECK_HIP(hipStreamSynchronize(stream));       // (the host vectors die here; once per layout)
-    out.n_wgs = n_wgs;
-    // fewer than 8 pairs of items per workgroup in an XCD's list: the kernel's three-pairs-ahead ticket pipeline would starve most workgroups
-    out.lazy = flat.size() < (size_t)3 * (size_t)n_wgs ? 1 : 0;      // fewer than 1.5 pairs per workgroup
+    SNCAL_CHECK_HIP(hipMemcpyAsync(out.items, plan.items.data(), plan.items.size() * sizeof(TTItem), hipMemcpyHostToDevice, stream));
+    SNCAL_CHECK_HIP(hipMemcpyAsync(out.first, plan.first, sizeof plan.first, hipMemcpyHostToDevice, stream));
+    SNCAL_CHECK_HIP(hipStreamSynchronize(stream));       // (the host plan dies here; once per layout)
+    out.n_wgs = net.n_cus;
+    out.lazy = plan.lazy;
     return SNCAL_OK;
 }
 
@@ -185,11 +148,12 @@ int run_tt(sncal_hrnet& net, Launch& e, const Call& c) {
     // tuning aid: SNCAL_TT_TRACE=<file> dumps the per-team phase timestamps of the LAST launch with 3 members
     // (SNCAL_TT_TRACE_CFG64=1: of the last launch of the 64-channel tile instead)
     const char* trace_file = env_str(ENV_TT_TRACE);
-    const bool traced = trace_file && (env_flag(ENV_TT_TRACE_CFG64) ? e.plan.cfg == 1 : n == 3);
+    const bool traced = trace_file && (env_flag(ENV_TT_TRACE_CFG64) ? e.plan.cfg == TT_TILE_64x12 : n == 3);
     TraceScope trace(traced ? trace_file : nullptr, (size_t)e.plan.n_wgs * 2 * 256, stream);
     tp.trace = trace.words;
     tp.ablate = env_int(ENV_TT_ABLATE);
-    launch_conv_tt(tp, e.plan.n_wgs, fp8 ? 1 : x3 ? 2 : 0, stream, e.plan.cfg);
+    const int rc = launch_conv_tt(tp, e.plan.n_wgs, fp8 ? 1 : x3 ? 2 : 0, stream, e.plan.cfg);
+    if (rc) return rc;
     SNCAL_CHECK_LAUNCH();
     return SNCAL_OK;
 }

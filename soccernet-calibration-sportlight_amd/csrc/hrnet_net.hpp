@@ -57,7 +57,7 @@ struct ConvLayer {
     float* d_oscale = nullptr;  // allocated with PK_TT_FP8, filled by sncal_hrnet_calibrate_fp8
     int stage = 0;              // 2..4 for model.stageN.* layers, 0 otherwise
     bool fp8_on = false;
-    int x3_blk = TT_COUT;       // PK_TT_X3: blocks of 96 (tile 96 x 8 x 32) or, for widths that are no multiple of 96, 64 (64 x 12 x 32)
+    int x3_blk = TT_COUT;       // PK_TT_X3: blocks of 96 (TT_TILE_96x8, TT_TILE_96x4) or, for widths that are no multiple of 96, 64 (TT_TILE_64x12): ttx3_block
     bool x3_on = false;
     // internal layers of the fused head: t_i = W0[:, col_off : col_off + cin] . branch_i  (derived at finalize)
     bool derived = false;
@@ -130,13 +130,13 @@ struct Member {                     // what the schedule resolved for one op a l
     Forms out;                      // the forms of the op's output that the launch writes (neither: it stays in LDS)
     Prep prep = PREP_NONE;          // LK_TT, LK_BBLOCKX3: the helper in front of the launch for this op's input
 };
-struct TTPlanDev { TTItem* items = nullptr; uint32_t* first = nullptr; int n_wgs = 0; int lazy = 0; int cfg = 0; };
+struct TTPlanDev { TTItem* items = nullptr; uint32_t* first = nullptr; int n_wgs = 0; int lazy = 0; TTTile cfg = TT_TILE_96x8; };
 struct Prof { std::string kernel; double flops = 0, bytes = 0; };
 struct Launch {
     LaunchKind kind = LK_CONV;
     int op = 0, n = 1;              // covers the ops [op, op + n), all active
     Member m[3];
-    TTPlanDev plan;                 // LK_TT: work lists (cfg set by the schedule, uploaded by the first launch)
+    TTPlanDev plan;                 // LK_TT: work lists (cfg, the tile, set by the schedule; uploaded by the first launch)
     Prof prof, prof_kp;             // profile row; LK_TAIL: prof_kp when the call wants keypoints only
 };
 struct Schedule {

@@ -147,20 +147,20 @@ Prof conv_prof(const sncal_hrnet& net, const Op& op, int sb, const ConvVariant* 
 
 void add_prof(Prof& sum, const Prof& member) { sum.kernel = member.kernel; sum.flops += member.flops; sum.bytes += member.bytes; }
 
-// Work-list tile of a two-team launch: 0 = 96 x 8 x 32, 1 = 64 x 12 x 32 (bf16x3, 48-channel branch), 2 = 96 x 4 x 32.  Small launches of the
+// Work-list tile of a two-team launch: TT_TILE_96x8, TT_TILE_64x12 (bf16x3, 48-channel branch) or TT_TILE_96x4.  Small launches of the
 // split-arithmetic engine (round 5): below two 8-row items per team the launch lasts as long as its longest item while most teams hold short
-// ones or nothing -- the 96 x 4 x 32 tile (conv_tt.hip, c31) halves the items instead
-int tt_cfg(const sncal_hrnet& net, const Op* ops, int n, int sb) {
+// ones or nothing -- the 96 x 4 x 32 tile (conv_tt.hip) halves the items instead
+TTTile tt_cfg(const sncal_hrnet& net, const Op* ops, int n, int sb) {
     const ConvLayer& L0 = net.layers[ops[0].conv];
-    if (!L0.x3_on) return 0;
-    if (n == 1 && L0.x3_blk == 64) return 1;
+    if (!L0.x3_on) return TT_TILE_96x8;
+    if (n == 1 && L0.x3_blk == TT_TILES[TT_TILE_64x12].cout_blk) return TT_TILE_64x12;
     const int per_team = env_int(ENV_TT_SMALL_ITEMS);      // (read per plan: tests run both tiles in one process; 0 = never)
     long items = 0;
     for (int i = 0; i < n; ++i) {
         const Tensor& ti = net.tensors[ops[i].in];
-        items += (long)((sb * (ti.H + 1) + TT_TH - 1) / TT_TH) * ((ti.W + TT_TW - 1) / TT_TW) * ((net.layers[ops[i].conv].cout + TT_COUT - 1) / TT_COUT);
+        items += tt_grid(sb, ti.H, ti.W, net.layers[ops[i].conv].cout, TT_TILE_96x8).items();
     }
-    return items < (long)per_team * 2 * net.n_cus ? 2 : 0;
+    return items < (long)per_team * 2 * net.n_cus ? TT_TILE_96x4 : TT_TILE_96x8;
 }
 
 // ---- the schedule builder: fusion predicates, asked once per (layout, sub-batch size) --------------------------------
@@ -290,9 +290,7 @@ void profile_launch(const sncal_hrnet& net, const Schedule& s, Launch& e) {
         case LK_TT: {
             for (int k = 0; k < e.n; ++k) add_prof(r, conv_prof(net, ops[k], sb, nullptr));
             const ConvLayer& L0 = net.layers[op.conv];
-            r.kernel = L0.fp8_on ? "conv_tt<fp8,k3,s1,8x32x96>" : e.plan.cfg == 1 ? "conv_tt<" SNCAL_X3_NAME ",k3,s1,12x32x64>" :
-                       e.plan.cfg == 2 ? "conv_tt<" SNCAL_X3_NAME ",k3,s1,4x32x96>" : L0.x3_on ? "conv_tt<" SNCAL_X3_NAME ",k3,s1,8x32x96>" :
-                       "conv_tt<bf16,k3,s1,8x32x96>";
+            r.kernel = fmt("conv_tt<%s,k3,s1,%s>", L0.fp8_on ? "fp8" : L0.x3_on ? SNCAL_X3_NAME : "bf16", TT_TILES[e.plan.cfg].label);
             if (profile_detail()) {      // one profile row per launch kind
                 r.kernel += fmt("@%d members%s%s%s", e.n, op.res >= 0 ? "+res" : "", e.m[0].out.dense ? "+f32" : "", e.m[0].out.twin ? "+twin" : "");
             }

@@ -52,7 +52,7 @@ __device__ __forceinline__ void xcd_share(int n, int xcd, int& lo, int& hi) {
 // Leaving a ticket queue (one lane per leaver, `per_wg` leavers in every workgroup of the launch).  The queue is `n_words` device words,
 // the last of them the count of leavers.  Every leaver holds exactly one failing ticket, so once all of them have been counted nobody
 // touches the words any more and the last one re-arms them for the next launch on this stream.  (conv_tt counts its leavers per XCD:
-// conv_tt_body.inc.)
+// conv_tt_kernel.hpp.)
 __device__ __forceinline__ void ticket_leave(unsigned* words, int n_words, unsigned per_wg) {
     if (atomicAdd(words + n_words - 1, 1u) == gridDim.x * per_wg - 1u) {
 #pragma unroll

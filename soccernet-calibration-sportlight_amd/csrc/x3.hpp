@@ -73,7 +73,7 @@ __device__ __forceinline__ float x3_relu_clamp(float v) {
 // lo = (f16)(x - (float)hi) are two instructions: 5 VALU instructions per pair instead of 7 (9 with a separate ReLU).  x - hi is exact in
 // fp32 (both are multiples of ulp32(x), |x - hi| <= ulp16(x) / 2), so the fused form rounds the same number once: identical bits on 2^24
 // values incl. fp16 subnormals, the clamp boundary, infinities and signed zeros (tools/dev/fma_mix_probe.hip).  Epilogues are VALU work of a
-// LOADING wave beside a multiplying partner (~6-14 clk per instruction there): conv_tt_body.inc, bblockx3.hip, headx3.hip, bneckx3.hip.
+// LOADING wave beside a multiplying partner (~6-14 clk per instruction there): conv_tt_kernel.hpp, bblockx3.hip, headx3.hip, bneckx3.hip.
 // `lob` = x3_lower(relu): the lower clamp bound as a run-time (wave-uniform) operand, so that one copy of an epilogue serves layers with
 // and without ReLU.
 __device__ __forceinline__ float x3_lower(bool relu) {

@@ -10,8 +10,13 @@ for f in glob.glob(d + '/**/*counter_collection.csv', recursive=True):
         if 'conv_shared_s2_kernel' in k:
             k, m = 'conv_shared_s2<fp16x3,k3,NI2,G3>', None
         elif 'conv_tt_kernel' in k:
-            mode = 'fp8' if ('ILb1' in k or '<true>' in k or 'ILi1E' in k or 'kernel<1>' in k) else 'fp16x3' if ('ILi2E' in k or 'kernel<2>' in k) else 'bf16'
-            k = 'conv_tt<%s,k3,s1,%s>' % (mode, '12x32x64' if 'c23' in k else '4x32x96' if 'c31' in k else '8x32x96')
+            # conv_tt_kernel<MB, NB, MODE>, demangled or mangled: the tile is 4 NB rows x 32 columns x 32 MB channels (csrc/conv_tt.hpp TTShape)
+            t = re.search(r'conv_tt_kernel(?:<(\d), (\d), (\d)>|ILi(\d)ELi(\d)ELi(\d)E)', k)
+            if t:
+                mb, nb, mode = (int(g) for g in t.groups() if g is not None)
+                k = 'conv_tt<%s,k3,s1,%dx32x%d>' % (('bf16', 'fp8', 'fp16x3')[mode % 3], 4 * nb, 32 * mb)
+            else:                               # a truncated name, or a counter file of a build before the three-parameter template
+                k = k[:48]
         elif m:
             ty = {'DF16b': 'bf16', 'NS_4x3_tE': 'fp16x3'}.get(m.group(1), 'f32')
             k = 'conv<%s,k%s,s%s,NI%s,MI%s,G%s>' % ((ty,) + m.groups()[1:])
