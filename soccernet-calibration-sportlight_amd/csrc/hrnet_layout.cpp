@@ -24,9 +24,13 @@ int sncal::layout(sncal_hrnet& net, int sb, int H, int W) {
         if (net.x3 && net.fused_enabled && dims_ok && net.desc.upscale == 2 && net.head_packed[HPK_W0_32_LO].p && net.head_ks16 == 13 && net.head_m2 == 4 &&
             headx3_enabled()) {
             // fp16x3: the fused split-arithmetic head (headx3.hip) when its gather boxes fit: branches 2 and 3 against the head's width
-            // (the scales head_params will hand headx3_applies, before the tensors have their shapes)
+            // (the scales head_params will hand headx3_applies, before the tensors have their shapes).  headx3 gathers exactly TWO sources:
+            // head_ks16 == 13 alone does not say so -- widths 144 / 160 / 320 / 400 fold only branch 0 (64 + 144 = 208 = 13 x 16) and
+            // gather three -- so the head op's own source count decides with it; otherwise the split formulation below serves the head
+            int nsrc = 0;
+            for (const Op& op : net.ops) if (op.type == OP_HEAD) nsrc = op.head_nsrc;
             const int w2 = half(half(bw)), w3 = half(w2);
-            net.use_fused = head_boxes_fit(align_corners_ratio(w2, sw)) && head_boxes_fit(align_corners_ratio(w3, sw));
+            net.use_fused = nsrc == 2 && head_boxes_fit(align_corners_ratio(w2, sw)) && head_boxes_fit(align_corners_ratio(w3, sw));
         }
         net.use_split = !net.use_fused && net.has_split && net.dtype == SNCAL_F32 && dims_ok;
     }

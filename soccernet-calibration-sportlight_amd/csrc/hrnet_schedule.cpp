@@ -242,6 +242,13 @@ int plan_group(const sncal_hrnet& net, size_t i, int n, int sb, Launch& e) {
         e.kind = LK_TT; e.n = n; e.plan.cfg = tt_cfg(net, ops, n, sb);
         return SNCAL_OK;
     }
+    // A member the two-team kernel serves never joins a grouped launch of the GENERIC kernel: a group too wide for the tables (288 + 480
+    // = 768 channels) or with a member past the kernel's widths (288 + 480 + 576) is taken apart -- the first member alone, the rest tried
+    // again -- so that every eligible layer keeps its kernel.  (Without this the members that happened to pick one generic variant went out
+    // as LK_GROUP: 288- and 480-channel layers on the generic kernel in some layouts and on the two-team kernel in others.  No packaged
+    // config gets here: their eligible members always fit one two-team launch.)
+    for (int k = 0; k < n; ++k)
+        if (tt_eligible(net, ops[k], sb)) return SNCAL_OK;
     // the chain-starting stride-2 convolutions of one input tensor (schedule_fuse_section): one launch, tile-major (conv.hpp)
     if (ops[0].shared_in && !net.x3) return SNCAL_OK;        // (the other engines run them one by one)
     Member m[3];

@@ -239,6 +239,11 @@ def test_argument_validation_and_empty_batches_without_a_gpu():
     h = ctypes.c_void_p()
     assert lib.sncal_hrnet_create(ctypes.byref(desc), 1, ctypes.byref(h)) == ERR_ARG               # zeroed descriptor
     assert lib.sncal_hrnet_forward(None, None, 1, 540, 960, None, None, 540, 960, None, 0, None) == ERR_ARG
+    # a branch width that is no multiple of 16 is refused at create, never padded in silence (tests/width_cases.py: the accepted families)
+    import width_cases as wc
+    narrow = sncal_amd.hrnet._desc(wc.width_config((40, 80, 160, 320)))
+    assert lib.sncal_hrnet_create(ctypes.byref(narrow), 1, ctypes.byref(h)) == ERR_ARG and b'width 40 must be a multiple of 16' in lib.sncal_last_error()
+    assert not h.value
 
 
 def test_jpeg_host_parser_survives_damaged_streams():

@@ -116,6 +116,68 @@ def test_odd_input_size_stem_interpolation(sncal, cuda):
     assert np.abs(heat.cpu().numpy() - ref).max() <= 2e-4
 
 
+def _width_family_against_the_oracle(sncal, cuda, name, cfg, seed):
+    """One width family of tests/width_cases.py, 2 frames of 72x104 (head 36x52), every engine against hr.forward on the CPU: the bounds of
+    this file (fp32-class engines 2e-4 on the log-probabilities, bf16 0.6) and the decoded keypoints = the oracle decode of the engine's own
+    heat.  Returns {engine: max |logp - ref|}."""
+    sd = hr.seeded_state_dict(cfg, seed, 4.0)
+    x = hr.seeded_input(2, 72, 104, seed + 1)
+    ref = hr.forward(sd, x, cfg).numpy()
+    assert ref.shape == (2, 58, 36, 52) and np.isfinite(ref).all()
+    errs = {}
+    for dtype, tol in (('fp32', 2e-4), ('fp16x3', 2e-4), ('bf16', 0.6)):
+        net = sncal.HRNetHeatmap(cfg, dtype=dtype, device=cuda)
+        net.load_state_dict(sd)
+        heat, kp = net.forward(x.to(cuda), want_heat=True, decode_size=(540, 960))
+        heat, kp = heat.cpu().numpy(), kp.cpu().numpy()
+        errs[dtype] = float(np.abs(heat - ref).max())
+        print(f'WIDTH-ORACLE {name} {dtype}: max |logp - oracle| {errs[dtype]:.3e} (bound {tol:g}), oracle range {ref.min():.2f} .. {ref.max():.2f}')
+        assert errs[dtype] <= tol, (name, dtype, errs[dtype])
+        assert np.array_equal(kp, od.keypoint_decode(heat, (540, 960))), (name, dtype)
+        del net
+    return errs
+
+
+@pytest.mark.parametrize('name', ['W64', 'P64', 'Q64', 'M96'])
+def test_width_families_match_the_oracle(sncal, cuda, name):
+    """Branch widths beyond W18 / W32 / W48 at reduced depth (one module per stage, one BasicBlock per branch; tests/width_cases.py), whole
+    network against the CPU oracle.  tests/test_width_kernels_gpu.py checks the same networks launch by launch; here the launches are chained.
+    Measured max |logp - oracle| on an MI355X (fp32 / fp16x3 / bf16), log-probabilities of about -12 .. -0.5:
+        W64  7.6e-6 / 8.6e-6 / 0.033
+        P64  7.6e-6 / 1.0e-5 / 0.050
+        Q64  1.1e-5 / 1.9e-5 / 0.048
+        M96  1.4e-5 / 2.1e-5 / 0.064"""
+    import width_cases as wc
+    _width_family_against_the_oracle(sncal, cuda, name, wc.reduced(name), {'W64': 41, 'P64': 43, 'Q64': 45, 'M96': 47}[name])
+
+
+def test_w64_at_the_reference_depth_matches_the_oracle(sncal, cuda):
+    """64 / 128 / 256 / 512 at the depth of the reference's own families (stage1 of 4 blocks, modules 1 / 4 / 3, 4 blocks per branch: 117 M
+    weights, three engines loaded one after the other -- the time of this test is its weight packing and upload).
+    Measured max |logp - oracle| on an MI355X (fp32 / fp16x3 / bf16): 7.2e-5 / 1.98e-4 / 0.43 on log-probabilities down to -48 (the fp16x3 figure is the
+    engine's drift over 300 layers against a bound of 2e-4: deterministic inputs, no margin to give away; the CPU oracle's own fp32 run is 4.0e-5
+    from a float64 run of the same oracle, and does not move with the thread count)"""
+    import width_cases as wc
+    _width_family_against_the_oracle(sncal, cuda, 'W64 full depth', wc.reference_depth('W64'), 51)
+
+
+@pytest.mark.parametrize('name,dtype', [('P64', 'fp16x3'), ('M96', 'bf16')])
+def test_width_families_frames_are_independent(sncal, cuda, name, dtype):
+    """A batch of 5 frames equals each frame run alone, bit for bit (as test_batch_and_subbatch_consistency): the partial last 64-channel
+    blocks of P64 on the split engine, the 3- and 5-block launches of M96 on bf16 -- stacked frames share tiles, never values."""
+    import width_cases as wc
+    cfg = wc.reduced(name)
+    net = sncal.HRNetHeatmap(cfg, dtype=dtype, device=cuda)
+    net.load_state_dict(hr.seeded_state_dict(cfg, 61, 4.0))
+    x = hr.seeded_input(5, 72, 104, 62).to(cuda)
+    heat, kp = net.forward(x, want_heat=True, decode_size=(540, 960))
+    heat, kp = heat.clone(), kp.clone()
+    assert torch.isfinite(heat).all()
+    for i in range(5):
+        h1, k1 = net.forward(x[i:i + 1].contiguous(), want_heat=True, decode_size=(540, 960))
+        assert torch.equal(h1[0], heat[i]) and torch.equal(k1[0], kp[i]), i
+
+
 def test_load_model_predict_surface(sncal, cuda, tmp_path):
     """argus-style checkpoint dict -> load_model(...).predict(x) -> (B,57,3) on the device (D2)."""
     cfg = hr.load_config('hrnet_w18')

@@ -141,11 +141,12 @@ def bilinear_up(src_nhwc, H, W, weight_round):
     return out
 
 
-def check(name, got, ref, rel, abs_, stats, kernel, flip_slack=None, flip_fraction=0.0):
+def check(name, got, ref, rel, abs_, stats, kernel, flip_slack=None, flip_fraction=0.0, label=None):
     """|got - ref| <= rel |ref| + abs_ everywhere.  flip_slack (same shape, optional): where an INTERNAL bf16 rounding sits between
     two matrix products (the head's hidden vector) kernel and reference may round a few hidden values to different neighbours;
     then at most `flip_fraction` of the elements may exceed the tight tolerance, none may exceed tight + flip_slack, and the mean
-    error stays far below either (a systematic error -- one pixel position of every tile -- fails all three)."""
+    error stays far below either (a systematic error -- one pixel position of every tile -- fails all three).
+    `label`: the schedule's own label of the launch that wrote `got` (plan_ops()['kernel']); the row counts its checks per label."""
     err = (got - ref).abs()
     tol = rel * ref.abs() + abs_
     bad = err > tol
@@ -160,6 +161,8 @@ def check(name, got, ref, rel, abs_, stats, kernel, flip_slack=None, flip_fracti
     row['ops'] += 1
     row['elements'] += int(err.numel())
     row['max_abs_err'] = max(row['max_abs_err'], float(err.max()))
+    if label is not None:
+        row.setdefault('labels', {})[label] = row.get('labels', {}).get(label, 0) + 1
     if worst > row['worst_err_over_tol']:
         row['worst_err_over_tol'], row['worst_op'] = worst, name
     if bad.any():
@@ -190,6 +193,7 @@ def run_case(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, want_heat=True, ne
     net.forward(x, want_heat=want_heat, decode_size=(540, 960) if net.cfg.get('head', 'logsoftmax') == 'logsoftmax' else None)
     torch.cuda.synchronize()
     ops = net.plan_ops()
+    net.last_profile = net.get_profile()                    # the rows of this ONE forward (set_profiling clears them)
     net.set_profiling(0)
     taps = {}
     for op in ops:
@@ -223,6 +227,18 @@ def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag='', net=Non
     by_idx = {op['idx']: op for op in ops}
     label = ''
     fused_second = set()
+    # which kernel served which convolution, from the schedule's own labels (the first op of a launch carries the label, `launch` names
+    # the launch of every op it covers): stats['_case']['served'], one entry per active conv op that was checked
+    launch_label = {o['launch']: o['kernel'] for o in ops if o['active'] and o['kernel']}
+    launch_size = {}
+    for o in ops:
+        if o['active'] and o['launch'] >= 0:
+            launch_size[o['launch']] = launch_size.get(o['launch'], 0) + 1
+    served = []
+
+    def serve(o, forms):
+        served.append(dict(op=o['idx'], name=o['name'], cin=o['cin'], cout=o['cout'], ksize=o['ksize'], stride=o['stride'], fp8=bool(o['fp8']),
+                           kernel=launch_label.get(o['launch'], ''), launch=o['launch'], members=launch_size.get(o['launch'], 0), forms=forms))
 
     def T(op, tid):
         return taps[(op['idx'], tid)]
@@ -254,7 +270,8 @@ def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag='', net=Non
                 got = nchw(taps[(nxt['idx'], nxt['out'])])
                 # the intermediate tile is rounded to bf16 between the two convolutions: where kernel and reference round a mid value to
                 # different neighbours (their fp32 sums differ in the last bits) the output moves by ulp(mid) x |w2| ~ 4e-4 per flip
-                check(op['name'] + ' + conv2', got, ref, rel_out, 4e-3, stats, 'bblock48_fused')
+                check(op['name'] + ' + conv2', got, ref, rel_out, 4e-3, stats, 'bblock48_fused', label=launch_label.get(op['launch'], label))
+                serve(op, ['lds']), serve(nxt, ['dense'])
                 continue
             if label == 'bblockx3_fused' and op['kernel'] == 'bblockx3_fused':
                 # fp16x3, fused 48-channel BasicBlock (bblockx3.hip): x (split twin) -> conv1 + shift, ReLU -> mid (split in LDS, never in
@@ -279,6 +296,7 @@ def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag='', net=Non
                     check(name + ' [split twin out]', _split_twin_value(taps[(nxt['idx'], to['twin'])]), y, 1e-5 + 2.0 ** -16, abs_out + slack, stats, 'bblockx3_fused split out')
                     checked = True
                 assert checked, name
+                serve(op, ['lds']), serve(nxt, ['dense'] * bool(to['alive'] and nxt['writes_out']) + ['twin'] * bool(nxt['writes_twin']))
                 continue
             if label == 'bneck_tail_ds_x3' and op['kernel'] == 'bneck_tail_ds_x3':
                 # fp16x3, layer1 block 0 (bneckx3.hip): this op is the downsample branch, the next one the conv3 that adds it; one launch
@@ -293,7 +311,8 @@ def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag='', net=Non
                 slack = X3_SLACK * (conv_ref(h2.abs(), w3.abs(), 1) + conv_ref(x0.abs(), w.abs(), 1))
                 to = net.plan_tensor(nxt['out'])
                 got = nchw(taps[(nxt['idx'], nxt['out'])])
-                check(f"{nxt['name']} + downsample {to['H']}x{to['W']} 64+64->256", got, y, rel_out, abs_out + slack, stats, 'bneck_tail_ds_x3')
+                check(f"{nxt['name']} + downsample {to['H']}x{to['W']} 64+64->256", got, y, rel_out, abs_out + slack, stats, 'bneck_tail_ds_x3', label=launch_label.get(op['launch'], label))
+                serve(op, ['lds']), serve(nxt, ['dense'])
                 continue
             if op['fp8']:
                 tw = net.plan_tensor(ti['twin'])
@@ -334,32 +353,39 @@ def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag='', net=Non
             to = net.plan_tensor(op['out'])
             kern = 'conv_tt<fp8,k3,s1,8x32x96>' if op['fp8'] else ('conv_tt<fp16x3,k3,s1,12x32x64>' if op['cout'] % 96 else 'conv_tt<fp16x3,k3,s1,8x32x96>') if op.get('x3') else label
             name = f"{op['name']} {to['H']}x{to['W']} {op['cin']}->{op['cout']}" + ('+res' if op['res'] >= 0 else '')
+            real = launch_label.get(op['launch'], label)                # the schedule's label of the launch that really served this op
+            forms = []
             checked = False
             gen_twin = bool(op.get('x3g')) and op['writes_twin']
             if gen_twin:
-                check(name + ' [split twin out]', _split_twin_value(T(op, to['twin'])), y, 1e-5 + 2.0 ** -16, abs_out + fp8_slack, stats, kern + ' split out')
+                check(name + ' [split twin out]', _split_twin_value(T(op, to['twin'])), y, 1e-5 + 2.0 ** -16, abs_out + fp8_slack, stats, kern + ' split out', label=real)
                 checked = True
+                forms.append('twin')
             if to['alive'] and op['writes_out']:
                 got = nchw(T(op, op['out']))[:, op['out_coff']:op['out_coff'] + op['cout']]
                 if op['out_f32']:
-                    check(name, got, y, 1e-5 if f32_engine else 2.0 ** -9, abs_out, stats, kern)     # fp32 logits of bf16 operands
+                    check(name, got, y, 1e-5 if f32_engine else 2.0 ** -9, abs_out, stats, kern, label=real)     # fp32 logits of bf16 operands
                 else:
-                    check(name, got, y, rel_out, abs_out + fp8_slack, stats, kern)
+                    check(name, got, y, rel_out, abs_out + fp8_slack, stats, kern, label=real)
                 checked = True
+                forms.append('dense')
             if op.get('x3') and op['writes_twin']:
                 # split twin written by the epilogue: [16 hi | 16 lo] bf16 per 16-channel group; hi + lo reproduces y to 2^-17
                 raw = T(op, to['twin'])                                                  # fp32-typed storage, (N,H,W,C)
                 pr = raw.view(X3_T).reshape(raw.shape[0], raw.shape[1], raw.shape[2], raw.shape[3] // 16, 2, 16).to(torch.float32)
                 got_t = (pr[..., 0, :] + pr[..., 1, :]).reshape(raw.shape).permute(0, 3, 1, 2)
-                check(name + ' [split twin out]', got_t, y, 1e-5 + 2.0 ** -16, abs_out + fp8_slack, stats, kern + ' split out')
+                check(name + ' [split twin out]', got_t, y, 1e-5 + 2.0 ** -16, abs_out + fp8_slack, stats, kern + ' split out', label=real)
                 checked = True
+                forms.append('twin')
             if op['fp8'] and op['writes_twin']:
                 tw_o = net.plan_tensor(to['twin'])
                 got8 = e4m3_decode(T(op, to['twin'])).permute(0, 3, 1, 2) * tw_o['scale']
                 ref8 = e4m3_round(bf16r(y) / tw_o['scale']) * tw_o['scale']
-                check(name + ' [e4m3 out]', got8, ref8, E4M3_ULP, tw_o['scale'] * 2.0 ** -9 + 1e-3 + fp8_slack, stats, kern + ' e4m3 out')
+                check(name + ' [e4m3 out]', got8, ref8, E4M3_ULP, tw_o['scale'] * 2.0 ** -9 + 1e-3 + fp8_slack, stats, kern + ' e4m3 out', label=real)
                 checked = True
+                forms.append('e4m3')
             assert checked, name
+            serve(op, forms)
         elif op['type'] == 'upsample_add':
             to = net.plan_tensor(op['out'])
             wr = (lambda t: t) if f32_engine else bf16r
@@ -393,8 +419,13 @@ def verify_plan(sncal, cuda, cfg, sd, x, dtype, fp8_layers=None, tag='', net=Non
             check('softmax head', got, ref, 1e-5, 1e-5, stats, 'softmax_nchw')
     pairs, skipped = producer_reader_identity(net, ops, taps)
     twins = twin_value_identity(net, ops, taps, dtype, stats, skipped)
+    # no convolution went unchecked: every active conv op has exactly one entry in `served`, with at least one output form compared
+    conv_active = [o['idx'] for o in ops if o['active'] and o['type'] == 'conv']
+    assert sorted(e['op'] for e in served) == conv_active, (sorted(set(conv_active) - {e['op'] for e in served}), len(served), len(conv_active))
+    assert all(e['forms'] and e['kernel'] for e in served), [e for e in served if not (e['forms'] and e['kernel'])][:3]
     stats['_case'] = dict(tag=tag, dtype=dtype, fp8_layers=fp8_layers, frames=int(B), input=list(x.shape[2:]),
-                          reader_pairs=pairs, lds_intermediates=len(skipped), **twins)
+                          reader_pairs=pairs, lds_intermediates=len(skipped), **twins, conv_ops_active=len(conv_active), conv_ops_checked=len(served),
+                          served=served, profile_launches={p['kernel']: p['launches'] for p in getattr(net, 'last_profile', [])})
     return stats
 
 
@@ -813,14 +844,24 @@ def test_every_launch_of_the_fp16x3_engine_w48_1080p_and_odd_sizes(sncal, cuda):
 
 
 def test_every_launch_of_the_fp16x3_engine_w18_and_line_net(sncal, cuda):
-    """W18 (18 / 36 / 72 / 144 channels: no two-team tiles, every convolution on the generic split-arithmetic kernel) and the line
+    """The packaged hrnet_w18 (16 / 32 / 64 / 128 channels: by x3_shape_ok every 3x3 stride-1 convolution of stages 2-4 qualifies for the
+    two-team kernel, and as no width is a multiple of 96 each runs alone on the 64 x 12 x 32 tile -- the 16- and 32-channel branches in one
+    padded 64-channel block; stem, layer1, transitions, stride-2 and 1x1 convolutions on the generic split-arithmetic kernel) and the line
     network's head configuration."""
     from oracle import hrnet_ref as hr
+    import width_cases as wc
     cfg = hr.load_config('hrnet_w18')
     sd = hr.seeded_state_dict(cfg, 3, 4.0)
     stats = verify_plan(sncal, cuda, 'hrnet_w18', sd, _frames(3, 135, 240, 22, cuda), 'fp16x3', tag='w18 135x240 fp16x3')
     _report(stats, 'fp16x3_w18_135x240')
     assert any(k.startswith('conv<fp16x3') for k in stats)
+    # which kernel served the branch convolutions, by the schedule's own label
+    x3n = sncal._lib.lib().sncal_x3_name().decode()
+    wide = [e for e in stats['_case']['served'] if e['ksize'] == 3 and e['stride'] == 1 and '.stage' in e['name']]
+    assert len(wide) == 2 * 2 * (2 + 3 + 4) and {e['cout'] for e in wide} == {16, 32, 64, 128}, len(wide)      # 2 blocks x 2 convolutions per branch
+    for e in wide:
+        want, alone = wc.expected_kernel('x3', x3n, e['cin'], e['cout'])
+        assert e['kernel'] == want == f'conv_tt<{x3n},k3,s1,12x32x64>' and alone and e['members'] == 1, e
     sd = _weights('line_hrnet_w48')
     stats = verify_plan(sncal, cuda, 'line_hrnet_w48', sd, _frames(2, 540, 960, 23, cuda), 'fp16x3', tag='line w48 540p fp16x3')
     _report(stats, 'fp16x3_line_w48_540p')
