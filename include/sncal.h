@@ -672,6 +672,40 @@ int sncal_keypoint_labels(const double* d_points, int total_points, const int* d
                           double* d_labels, unsigned char* d_label_present, unsigned char* d_swapped, void* d_ws,
                           size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Extremity metric: detected line ends against the annotation, per frame, a batch and n_t thresholds in one launch
+ * replaces evaluate_detection_prediction and the two-labelling choice    baseline/evaluate_extremities.py:37-116, 192-216
+ *          scale_points                                                  baseline/evaluate_extremities.py:119-134
+ *          get_line_data's `points` (peaks form)                         src/utils/export_line_result.py:115-124
+ * (named after the metric, not the line model: tests/test_validate_line_host.py pins the set of line-model entry points)
+ *   d_gt_points, total_points, d_gt_offsets   the annotations, packed as sncal_keypoint_labels takes them: (total_points, 2) fp64
+ *              normalised, (B, n_classes + 1) int32 offsets, n_classes = 28 in that entry point's class order.  A class with at least
+ *              one point counts n = its point count; its first and last point are multiplied by (img_w - 1, img_h - 1).  A class
+ *              without points, or whose range leaves [0, total_points], is absent.
+ *   the prediction, exactly one of two forms:
+ *     d_peaks  (B, C, 2, 3) fp32 rows [x, y, p] in map cells, channel k = class 3 + k (LINE_CLS order), C <= 23.  Slot i is kept when
+ *              p >= p_threshold; its pixel is (x * scale, y * scale) in fp32, widened; n = kept slots (0 = absent), slot order kept,
+ *              one kept slot is both first and last.  (Rows that are pixels already -- sncal_line_decode with its scale -- take scale 1.)
+ *     d_pred_points, pred_total, d_pred_offsets   packed and scaled like the annotations (the extremities_<id>.json files)
+ *   ts         HOST array of n_t <= 8 pixel thresholds, read inside the call
+ * 'Circle central' (class 0) is removed from both sides.  'Goal unknown' and 'Line unknown' are not: annotated, they are false
+ * negatives, as in the reference.  Per frame two labellings: prediction class c against annotation class c (0), or against the
+ * point-symmetric class (1: mirror_labels on the annotation).  Under each: a class only detected adds fp += n_pred, a class only
+ * annotated adds fn += n_gt (under the prediction-side name), a class on both sides takes d1 = |gt first - pred first|,
+ * d2 = |gt last - pred last| -- or the crossed pair when both crossed distances are <= -- and each adds tp when < t, else fp.
+ * acc = float32(tp) / float32(tp + fp + fn), 0 for an empty frame; labelling 0 is kept only when acc0 > acc1 (a tie is mirrored),
+ * per threshold.  Of the kept labelling:
+ *   d_frame (n_t, B, 4) int32 [tp, fp, fn, labelling];  d_class (n_t, B, 28, 3) int32 [tp, fp, fn] per prediction-side class;
+ *   d_err (n_t, B, 28, 2) fp64 [d1, d2], NaN where the class is not on both sides.
+ * Counts are exact below 2^24 per frame (the reference's confusion matrix is float32).  One wavefront per frame, plain stores, no
+ * atomics: two runs write the same bits.  B == 0 returns SNCAL_OK without touching a pointer.  Asynchronous on `stream`; the
+ * library allocates nothing.
+ * ---------------------------------------------------------------------------------------------- */
+int sncal_extremity_counts(const double* d_gt_points, int total_points, const int* d_gt_offsets, const float* d_peaks, int C,
+                           float scale, float p_threshold, const double* d_pred_points, int pred_total, const int* d_pred_offsets,
+                           int B, int n_classes, int img_w, int img_h, const double* ts, int n_t, int* d_frame, int* d_class,
+                           double* d_err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -329,3 +329,77 @@ class AccMetric:
 
     def epoch_complete(self, state):
         state.metrics[f'{_prefix(state)}{self.name}'] = self.compute()
+
+
+class ExtremityMetric:
+    """The dev-kit's extremity metric (baseline/evaluate_extremities.py:156-261) with the counting on the device
+    (sncal_extremity_counts, csrc/extremity.hip).  update() queues one launch for the batch, all thresholds at once, and keeps its
+    three result tensors on the device, as AccMetric does; compute() reads everything once.
+
+    thresholds      pixel thresholds (at most 8): each is scored as the reference's -t would score it
+    conf_threshold  a decoded peak is a detection when p >= conf_threshold (get_line_data's prob_thre)
+    scale           what turns the peaks' x, y into pixels: 4 for peaks in map cells (mask_heat_points_gauss), 1 for
+                    EHMPredictionTransform's output, which carries its scale already
+    img_size        (W, H) the annotations are scaled to, by (W - 1, H - 1) as scale_points does"""
+    name = 'ext'
+    better = 'max'
+
+    def __init__(self, thresholds: Sequence[float] = (5, 10, 20), conf_threshold: float = 0.2, scale: float = 4,
+                 img_size: Tuple[int, int] = (960, 540), device: str = 'cuda:0'):
+        self.thresholds = tuple(thresholds)
+        if not 1 <= len(self.thresholds) <= 8:
+            raise _lib.SncalError(f'{len(self.thresholds)} thresholds (1..8)')
+        self.conf_threshold = conf_threshold
+        self.scale = scale
+        self.img_size = tuple(int(v) for v in img_size)
+        self.device = device
+        self.reset()
+
+    def reset(self):
+        self._batches = []          # per update: (frame (T,B,4), cls (T,B,28,3), err (T,B,28,2)) on the device
+        self._missing = []          # per missing frame: how many scored frames came before it
+        self._scored = 0
+
+    def update(self, step_output: dict):
+        """step_output: {'prediction' (B,C,2,3) peaks, 'annot': the B raw annotations (normalised dicts) or their packed tuple}."""
+        from .extremities import extremity_counts
+        peaks = step_output['prediction'].detach().to(torch.float32).contiguous()
+        self._keep(extremity_counts(step_output['annot'], peaks=peaks, img_size=self.img_size, ts=self.thresholds, scale=self.scale,
+                                    p_threshold=self.conf_threshold))
+
+    def update_annots(self, gt_annots, pred_annots):
+        """The packed form: predictions as normalised dicts (the extremities_<id>.json files)."""
+        from .extremities import extremity_counts
+        self._keep(extremity_counts(gt_annots, pred_annots=pred_annots, img_size=self.img_size, ts=self.thresholds, device=self.device))
+
+    def _keep(self, out):
+        self._batches.append(out)
+        self._scored += out[0].shape[1]
+
+    def add_missing(self, n: int):
+        """n frames without a prediction: accuracy, precision and recall 0 each (:175-179)."""
+        self._missing += [self._scored] * int(n)
+
+    @property
+    def total_frames(self) -> int:
+        return self._scored + len(self._missing)
+
+    def _read(self):
+        if not self._batches:
+            T = len(self.thresholds)
+            return np.zeros((T, 0, 4), np.int32), np.zeros((T, 0, 28, 3), np.int32), np.zeros((T, 0, 28, 2), np.float64)
+        return tuple(torch.cat([b[i] for b in self._batches], dim=1).cpu().numpy() for i in range(3))
+
+    def compute(self) -> dict:
+        """{threshold: extremities.aggregate()'s dict}: mean / population std / median of the per-frame accuracy, precision and recall
+        (precision over the frames with tp + fp > 0, recall over those with tp + fn > 0), the per-class table from the summed
+        per-class confusion (numpy's nan for a zero denominator) and 'errors' {class: [distances, in frame order]}."""
+        from .extremities import aggregate_counts
+        frame, cls, err = self._read()
+        return {t: aggregate_counts(frame[i], cls[i], err[i], self._missing) for i, t in enumerate(self.thresholds)}
+
+    def epoch_complete(self, state, computed: dict = None):
+        p = _prefix(state)
+        for t, res in (computed if computed is not None else self.compute()).items():
+            for key in ('acc', 'precision', 'recall'):
+                state.metrics[f'{p}{self.name}_{key}@{t:g}'] = res['accuracy' if key == 'acc' else key]['mean']

@@ -34,7 +34,7 @@ from .annotations import get_extreme_points, get_intersections, keypoint_labels_
 from .evaluate import scale_points
 from .jpeg import JpegDecoder, check_reduce, probe, reduced_size
 from .lines import LINE_CLS
-from .metrics import AccMetric, EvalAImetric, EvalAISweep, L2metric
+from .metrics import AccMetric, EvalAImetric, EvalAISweep, ExtremityMetric, L2metric
 from .prediction import CameraCreator, parse_range
 
 
@@ -49,6 +49,7 @@ class ValidationResult(dict):
     frames = 0
     skipped: List[str] = []
     params: Dict[str, float] = {}           # validate(sweep=): the grid point this result belongs to
+    extremities: Dict[float, dict] = None   # validate_line(extremities=): ExtremityMetric.compute()'s dict per threshold
 
 
 class SweepResults(list):
@@ -232,10 +233,11 @@ def train_batches(folder: str, batch_size: int, transform, shuffle: bool = True,
         frames.close()
 
 
-def list_line_split(folder: str, input_size=(960, 540)):
+def list_line_split(folder: str, input_size=(960, 540), annots: bool = False):
     """EHMDataset.__init__ (line/dataset.py:54-67): (image names, labels) of the frames whose annotation sort_anno finds usable;
-    labels are get_extreme_points' dicts.  Sorted by name (the reference takes os.listdir's order)."""
-    names, labels = [], []
+    labels are get_extreme_points' dicts.  Sorted by name (the reference takes os.listdir's order).  annots=True: a third list, the
+    kept frames' annotations as they are on disk ({class: [{'x', 'y'}, ...]}, what the extremity metric scores against)."""
+    names, labels, raw = [], [], []
     for fname in sorted(os.listdir(folder)):
         if 'info' in fname or not fname.endswith('.json'):
             continue
@@ -249,25 +251,29 @@ def list_line_split(folder: str, input_size=(960, 540)):
         if usable:
             names.append(img)
             labels.append(get_extreme_points(res, img_size=input_size))
-    return names, labels
+            raw.append(annot)
+    return (names, labels, raw) if annots else (names, labels)
 
 
 def line_folder_batches(folder: str, batch_size: int, device, num_keypoint_pairs: int, input_size, decoder_threads: int,
-                        skipped: List[str], reduce: int = 1) -> Iterator[dict]:
+                        skipped: List[str], reduce: int = 1, annots: bool = False) -> Iterator[dict]:
     """The line model's batch dicts {'image', 'keypoints', 'line_para', 'img_name'} of a split folder (no 'keypoint_maps': the
-    loss rebuilds them).  A frame is taken when its size at 1 / reduce is input_size (W, H): a 1920x1080 split goes into the
-    960x540 network with reduce=2.  That is libjpeg's scaled decode (cv2.imread's IMREAD_REDUCED_COLOR_2), NOT the cv2.resize of
+    loss rebuilds them); with annots=True also 'annot', the frames' annotations as they are on disk.  A frame is taken when its size
+    at 1 / reduce is input_size (W, H): a 1920x1080 split goes into the 960x540 network with reduce=2.  That is libjpeg's scaled decode (cv2.imread's IMREAD_REDUCED_COLOR_2), NOT the cv2.resize of
     line/dataset.py:73, which is not built -- a declared deviation; a frame of any other size is skipped."""
-    names, labels = list_line_split(folder, input_size)
+    names, labels, *raw = list_line_split(folder, input_size, annots=annots)
     frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped, frame_size=(input_size[1], input_size[0]),
                              reduce=reduce)
     try:
         for keep, image in frames:
             pairs = [line_keypoints(labels[j], num_keypoint_pairs) for j in keep]
-            yield {'image': image,
-                   'keypoints': torch.from_numpy(np.stack([p[0] for p in pairs])),
-                   'line_para': torch.tensor([p[1] for p in pairs], dtype=torch.float64),
-                   'img_name': [names[j] for j in keep]}
+            batch = {'image': image,
+                     'keypoints': torch.from_numpy(np.stack([p[0] for p in pairs])),
+                     'line_para': torch.tensor([p[1] for p in pairs], dtype=torch.float64),
+                     'img_name': [names[j] for j in keep]}
+            if annots:
+                batch['annot'] = [raw[0][j] for j in keep]
+            yield batch
     finally:
         frames.close()
 
@@ -373,7 +379,7 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
 
 
 def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, loss=None, conf_threshold: float = 0.2,
-                  decoder_threads: int = 0, input_size=(960, 540), reduce: int = 1):
+                  decoder_threads: int = 0, input_size=(960, 540), reduce: int = 1, extremities: Sequence[float] = None):
     """Score a line-model checkpoint (EHMMetaModel) -> {'val_loss', 'val_acc'} as floats (a ValidationResult): the two numbers
     line/train_config.yaml logs and monitors.
 
@@ -384,6 +390,14 @@ def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, 
     reduce  folder form only.  A 1920x1080 split is taken with reduce=2: libjpeg's scaled decode (cv2.imread with
             IMREAD_REDUCED_COLOR_2), which is NOT the cv2.resize of line/dataset.py:73 -- a declared deviation.
             The labels are normalised coordinates and do not change; a frame whose reduced size is not input_size is skipped
+    extremities  None (default): the two keys above, nothing else runs.  A tuple of pixel thresholds, e.g. (5, 10, 20): the
+            dev-kit's extremity metric (baseline/evaluate_extremities.py; metrics.ExtremityMetric, one more launch per batch) on the
+            decoded peaks with p >= conf_threshold, against each frame's RAW annotation scaled to input_size: the keys
+            'val_ext_acc@t', 'val_ext_precision@t', 'val_ext_recall@t', the means over the frames, are added, and the per-class table and
+            error lists are left in .extremities.  The folder form reads the annotations itself; in the iterable form every batch
+            dict must carry 'annot', the B annotations {class: [{'x', 'y'}, ...]} in normalised coordinates (SncalError otherwise).
+            The frames sort_anno drops are not scored here, as they are not in val_acc, and neither is a frame the decoder
+            refuses: the dev-kit's scorer run over the folders (extremities.evaluate_extremities) scores every annotation file
 
     val_loss is the mean of the step losses weighted by step size, as in validate(); val_acc is AccMetric's value (the plain mean
     of the per-batch a@20 * 1.15, so it depends on batch_size, as in the reference).  A frame the decoder refuses (folder form) is
@@ -397,19 +411,25 @@ def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, 
     try:
         model._loss()
         acc = AccMetric(num_keypoints=len(LINE_CLS), conf_threshold=conf_threshold)
+        # the prediction transform has applied its scale: the peaks are pixels already
+        ext = None if extremities is None else ExtremityMetric(extremities, conf_threshold=conf_threshold, scale=1, img_size=input_size)
         skipped: List[str] = []
         if isinstance(data, (str, os.PathLike)):
             batches = line_folder_batches(os.fspath(data), batch_size, model.device, acc.num_keypoints, input_size, decoder_threads, skipped,
-                                          reduce=reduce)
+                                          reduce=reduce, annots=ext is not None)
         loss_sum = torch.zeros((), dtype=torch.float64, device=model.device)
         frames = 0
         for batch in (batches if batches is not None else data):
+            if ext is not None and 'annot' not in batch:
+                raise _lib.SncalError("validate_line(extremities=...): every batch dict must carry 'annot', the frames' raw annotations")
             out = model.val_step(batch)
             acc.num_keypoints = out['prediction'].shape[1]          # the channel count is the network's
             B = out['prediction'].shape[0]
             frames += B
             loss_sum = loss_sum + out['loss'].to(torch.float64) * B
             acc.update(out)
+            if ext is not None:
+                ext.update({'prediction': out['prediction'], 'annot': batch['annot']})
         model.check_range()
     finally:
         if batches is not None:
@@ -419,7 +439,13 @@ def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, 
     state = _State('val')
     state.metrics['val_loss'] = float(loss_sum.item()) / frames if frames else float('nan')
     acc.epoch_complete(state)
+    detail = None
+    if ext is not None:
+        detail = ext.compute()
+        ext.epoch_complete(state, detail)
     res = ValidationResult({k: float(v) for k, v in state.metrics.items()})
+    if detail is not None:
+        res.extremities = detail
     res.frames, res.skipped = frames + len(skipped), list(skipped)
     return res
 
@@ -438,6 +464,8 @@ def main(argv=None):
     ap.add_argument('--sweep-max-rmse', default=None, metavar='START:STOP:STEP',
                     help="sweep camera.max_rmse over Hydra's range(start, stop, step), stop excluded (optimize_valid.yaml: 10:70:4); one solve per batch")
     ap.add_argument('--sweep-max-rmse-rel', default=None, metavar='START:STOP:STEP', help='the same for camera.max_rmse_rel (optimize_valid.yaml: 4:16:2)')
+    ap.add_argument('--extremities', default=None, metavar='T[,T...]',
+                    help="with --line: also the dev-kit's extremity metric at these pixel thresholds, e.g. 5,10,20")
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--dtype', default=None, choices=['fp16x3', 'bf16x3', 'fp32', 'bf16', 'fp8'])
     a = ap.parse_args(argv)
@@ -448,11 +476,16 @@ def main(argv=None):
         cal = default_calibrator(None)             # an axis that is not swept keeps the calibrator's value
         sweep = {'max_rmse': parse_range(a.sweep_max_rmse) if a.sweep_max_rmse is not None else [cal.max_rmse],
                  'max_rmse_rel': parse_range(a.sweep_max_rmse_rel) if a.sweep_max_rmse_rel is not None else [cal.max_rmse_rel]}
+    ext = None
+    if a.extremities is not None:
+        if not a.line:
+            ap.error("--extremities is the line model's metric: it goes with --line")
+        ext = tuple(float(t) for t in a.extremities.split(','))
     if not torch.cuda.is_available():
         raise _lib.SncalError('no GPU visible: this package has no CPU path')
     model = load_model(a.model, device=a.device, dtype=a.dtype)
     if a.line:
-        res = validate_line(model, a.data, batch_size=a.batch_size or 8, reduce=a.reduce)
+        res = validate_line(model, a.data, batch_size=a.batch_size or 8, reduce=a.reduce, extremities=ext)
     else:
         res = validate(model, a.data, default_calibrator(a.lines_file), batch_size=a.batch_size or 16, reduce=a.reduce, sweep=sweep)
     if sweep is not None:

@@ -1,0 +1,259 @@
+"""GPU: sncal_extremity_counts (csrc/extremity.hip) and what stands on it -- ExtremityMetric, validate_line(extremities=), the
+folder scorer -- against tests/golden/extremities.npz, captured from the reference's own functions (tools/make_golden_extremities.py).
+Counts, labellings and per-class rows are integers and must be identical.  A distance is two fp64 squares, one sum and one square
+root, uncontracted on both sides, so at most 2 ulp could separate the kernel from numpy (one for the sum, one for the root); the
+measured maximum over both sets and both forms is 0 ulp (profiles/extremities.md), and the test asks for equality."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import extremities_cases as xc
+from oracle import hrnet_ref as hr
+
+pytestmark = pytest.mark.gpu
+
+ULP = 0          # measured: 0.  The reasoned bound was 2
+
+
+@pytest.fixture(scope='module')
+def gold():
+    return xc.load()
+
+
+def run(sncal, cuda, c, form, idx=None, ts=None):
+    """The kernel on the frames `idx` of a case, in one of the two prediction forms -> numpy (frame, cls, err)."""
+    idx = list(range(c['B'])) if idx is None else list(idx)
+    gt = [c['gt'][i] for i in idx]
+    kw = dict(img_size=c['size'], ts=c['ts'] if ts is None else ts, scale=c['scale'], p_threshold=c['p_threshold'])
+    if form == 'peaks':
+        out = sncal.extremities.extremity_counts(gt, peaks=torch.from_numpy(c['peak_rows'][idx]).to(cuda), **kw)
+    else:
+        out = sncal.extremities.extremity_counts(gt, pred_annots=[c['pred'][i] for i in idx], device=cuda, **kw)
+    assert [o.dtype for o in out] == [torch.int32, torch.int32, torch.float64] and all(o.is_cuda for o in out)
+    return tuple(o.cpu().numpy() for o in out)
+
+
+def ulps(a, b):
+    """Largest distance in units of the last place between the finite entries of two fp64 arrays with the same NaN pattern."""
+    fin = ~np.isnan(a)
+    assert np.array_equal(fin, ~np.isnan(b)), 'NaN pattern differs'
+    if not fin.any():
+        return 0
+    return int(np.abs(a[fin].view(np.int64) - b[fin].view(np.int64)).max())
+
+
+@pytest.fixture(scope='module')
+def full_a(sncal, cuda, gold):
+    """Set A through the kernel once per form: what the batch-shape tests compare against."""
+    c = xc.case(gold, 'A')
+    return c, {form: run(sncal, cuda, c, form) for form in xc.FORMS}
+
+
+@pytest.mark.parametrize('key', ['A', 'B'])
+@pytest.mark.parametrize('form', xc.FORMS)
+def test_kernel_equals_the_reference_capture(sncal, cuda, gold, key, form):
+    c = xc.case(gold, key)
+    frame, cls, err = run(sncal, cuda, c, form)
+    want = c[form]
+    T, B = len(c['ts']), c['B']
+    assert frame.shape == (T, B, 4) and cls.shape == (T, B, 28, 3) and err.shape == (T, B, 28, 2)
+    assert np.array_equal(frame, want['frame']), np.argwhere(frame != want['frame'])[:5]
+    assert np.array_equal(cls, want['cls']), np.argwhere(cls != want['cls'])[:5]
+    worst = ulps(err, want['err'])
+    print(f'set {key}, {form} form: max |d_err - reference| = {worst} ulp over {int((~np.isnan(err)).sum())} distances')
+    assert worst <= ULP
+    again = run(sncal, cuda, c, form)                                  # no atomics: a second run writes the same bits
+    assert all(a.tobytes() == b.tobytes() for a, b in zip((frame, cls, err), again))
+
+
+@pytest.mark.parametrize('form', xc.FORMS)
+def test_a_frame_does_not_depend_on_its_batch(sncal, cuda, full_a, form):
+    c, full = full_a
+    ref = full[form]
+    for idx in ([9], [3, 7, 0, 23, 12], [i % 24 for i in range(65)]):             # B = 1, 5 and 65: set A repeated
+        got = run(sncal, cuda, c, form, idx)
+        assert got[0].shape[1] == len(idx)
+        for pos, b in enumerate(idx):
+            for g, r in zip(got, ref):
+                assert g[:, pos].tobytes() == r[:, b].tobytes(), (len(idx), pos, b)
+
+
+@pytest.mark.parametrize('form', xc.FORMS)
+def test_thresholds_are_scored_independently(sncal, cuda, full_a, form):
+    c, full = full_a
+    ref = full[form]
+    one = run(sncal, cuda, c, form, ts=(10.0,))
+    eight = run(sncal, cuda, c, form, ts=(20.0, 1.0, 5.0, 2.5, 40.0, 10.0, 80.0, 0.0))
+    for g, r in zip(one, ref):
+        assert g.shape[0] == 1 and g[0].tobytes() == r[1].tobytes()
+    for at, i in ((2, 0), (5, 1), (0, 2)):
+        for g, r in zip(eight, ref):
+            assert g.shape[0] == 8 and g[at].tobytes() == r[i].tobytes()
+    assert not eight[0][7, :, 0].any()                                 # t = 0 hits nothing
+    with pytest.raises(sncal._lib.SncalError, match='n_t'):
+        run(sncal, cuda, c, form, ts=tuple(range(9)))
+
+
+def test_empty_batch(sncal, cuda):
+    frame, cls, err = sncal.extremities.extremity_counts([], pred_annots=[], device=cuda)
+    assert frame.shape == (3, 0, 4) and cls.shape == (3, 0, 28, 3) and err.shape == (3, 0, 28, 2)
+
+
+@pytest.mark.parametrize('form', xc.FORMS)
+def test_metric_over_uneven_batches_and_missing_frames(sncal, cuda, gold, form):
+    c = xc.case(gold, 'A')
+    m = sncal.ExtremityMetric(thresholds=c['ts'], conf_threshold=c['p_threshold'], scale=c['scale'], img_size=c['size'], device=cuda)
+    for lo, hi in ((0, 10), (10, 24)):
+        if form == 'peaks':
+            m.update({'prediction': torch.from_numpy(c['peak_rows'][lo:hi]).to(cuda), 'annot': c['gt'][lo:hi]})
+        else:
+            m.update_annots(c['gt'][lo:hi], c['pred'][lo:hi])
+    m.add_missing(2)
+    res = m.compute()
+    assert list(res) == list(c['ts']) and m.total_frames == 26
+    for i, t in enumerate(c['ts']):
+        agg, table = xc.agg_array(res[t])
+        assert xc.same(agg, gold[f'A.{form}.agg_missing2'][i]) and xc.same(table, c[form]['per_class'][i])
+        # the error lists: every distance of the kept labelling, frame by frame
+        want = c[form]['err'][i]
+        n = int((~np.isnan(want)).sum())
+        assert sum(len(v) for v in res[t]['errors'].values()) == n > 0
+        for name, v in res[t]['errors'].items():
+            w = want[:, sncal.annotations.ANNOT_CLASSES.index(name)]
+            assert ulps(np.array(v), w[~np.isnan(w)]) <= ULP
+    state = sncal.validate._State('val')
+    m.epoch_complete(state)
+    assert state.metrics['val_ext_acc@10'] == res[10.0]['accuracy']['mean'] == float(gold[f'A.{form}.agg_missing2'][1, 0, 0])
+    assert state.metrics['val_ext_recall@5'] == res[5.0]['recall']['mean'] and len(state.metrics) == 9
+    m.reset()
+    assert m.total_frames == 0 and np.isnan(m.compute()[5.0]['accuracy']['mean'])
+
+
+def test_folder_scorer_equals_the_reference_aggregates(sncal, cuda, gold, tmp_path, capsys):
+    c = xc.case(gold, 'A')
+    removed = [int(v) for v in gold['A.folder.removed']]
+    os.makedirs(tmp_path / 'data' / 'test')
+    os.makedirs(tmp_path / 'pred' / 'test')
+    for b in range(c['B']):
+        with open(tmp_path / 'data' / 'test' / f'{b:05d}.json', 'w') as f:
+            json.dump(c['gt'][b], f)
+        if b not in removed:
+            sncal.extremities.save_extremities(c['pred'][b], sncal.extremities.extremities_path(str(tmp_path / 'pred' / 'test'), f'{b:05d}.jpg'))
+    res = sncal.extremities.evaluate_extremities(str(tmp_path / 'data'), str(tmp_path / 'pred'), split='test',
+                                                 threshold=int(gold['A.folder.threshold']), resolution=c['size'], batch_size=7)
+    agg, table = xc.agg_array(res)
+    assert res['frames'] == 24 and xc.same(agg, gold['A.folder.agg']) and xc.same(table, gold['A.folder.per_class'])
+    assert capsys.readouterr().out.splitlines() == [str(s) for s in gold['A.folder.lines']]
+    # the command line takes the reference's flags
+    res2 = sncal.extremities.main(['-s', str(tmp_path / 'data'), '-p', str(tmp_path / 'pred'), '-t', '10', '--split', 'test',
+                                   '--resolution_width', '960', '--resolution_height', '540'])
+    assert xc.same(xc.agg_array(res2)[0], agg)
+    with open(tmp_path / 'pred' / 'test' / 'extremities_00000.json', 'w') as f:
+        json.dump({'No such line': [{'x': 0.5, 'y': 0.5}]}, f)
+    with pytest.raises(KeyError):
+        sncal.extremities.evaluate_extremities(str(tmp_path / 'data'), str(tmp_path / 'pred'), verbose=False)
+
+
+# ---- validate_line(extremities=) on the W18 line golden (64 x 96 input, heat 16 x 24, fp32 engine) -------------------------------
+
+LOSS = {'num_refinement_stages': 0, 'gmse_w': 1.0, 'awing_w': 1.0, 'sigma': 4}
+SIZE = (96, 64)
+
+
+@pytest.fixture(scope='module')
+def line_model(sncal, cuda, tmp_path_factory, gold_dir):
+    g = np.load(os.path.join(gold_dir, 'line_w18_64x96.npz'))
+    cfg = hr.load_config('line_hrnet_w18')
+    bare = {k: v for k, v in cfg.items() if k not in ('head', 'upscale')}
+    ck = {'model_name': 'EHMMetaModel',
+          'params': {'nn_module': {'hrnet_config': bare, 'num_refinement_stages': 0, 'num_heatmaps': 23}, 'loss': dict(LOSS),
+                     'prediction_transform': {'scale': 4, 'sigma': 6}, 'device': 'cuda:0'},
+          'nn_state_dict': hr.seeded_state_dict(cfg, int(g['seed']), float(g['head_gain']))}
+    path = str(tmp_path_factory.mktemp('line_ext') / 'line.pth')
+    torch.save(ck, path)
+    return sncal.load_model(path, loss=None, optimizer=None, device='cuda:0', dtype='fp32'), g
+
+
+def _batches(sncal, g):
+    """Two batches of 64 x 96 frames with random line annotations (normalised polylines of 2..4 points) and the labels made of them."""
+    rng = np.random.Generator(np.random.PCG64(29))
+    lines = [sncal.lines.LINE_CLS[i] for i in range(23)]
+    B, H, W = int(g['batch']), int(g['hw'][0]), int(g['hw'][1])
+    out = []
+    for i, b in enumerate((B, B + 1)):
+        annots = []
+        for _ in range(b):
+            a = {name: [{'x': float(x), 'y': float(y)} for x, y in rng.uniform(0.05, 0.95, (int(rng.integers(2, 5)), 2))]
+                 for name in lines if rng.uniform() < 0.5}
+            a['Circle central'] = [{'x': 0.5, 'y': 0.5}] * 5
+            annots.append(a)
+        kp = np.zeros((b, 23, 2, 3), dtype=np.float32)
+        kp[..., :2] = -1
+        for j, a in enumerate(annots):
+            for k, name in enumerate(lines):
+                if name in a:
+                    kp[j, k] = [(a[name][0]['x'] * W, a[name][0]['y'] * H, 1), (a[name][-1]['x'] * W, a[name][-1]['y'] * H, 1)]
+        out.append({'image': hr.seeded_input(b, H, W, int(g['seed']) + 7 + i), 'keypoints': torch.from_numpy(kp.reshape(b, -1)),
+                    'line_para': torch.full((b, 23, 2), float('nan'), dtype=torch.float64), 'annot': annots})
+    return out
+
+
+def test_validate_line_with_the_extremity_metric(sncal, cuda, line_model):
+    from sncal_amd import extremities as ex
+    model, g = line_model
+    batches = _batches(sncal, g)
+    ts, thr = (5, 10, 20), 0.01
+    plain = sncal.validate.validate_line(model, batches, conf_threshold=thr, input_size=SIZE)
+    assert sorted(plain) == ['val_acc', 'val_loss'] and plain.extremities is None          # the default: the two keys, as before
+    res = sncal.validate.validate_line(model, batches, conf_threshold=thr, input_size=SIZE, extremities=ts)
+    keys = [f'val_ext_{k}@{t}' for t in ts for k in ('acc', 'precision', 'recall')]
+    assert sorted(res) == sorted(['val_acc', 'val_loss'] + keys) and res.frames == plain.frames
+    assert res['val_loss'] == plain['val_loss'] and res['val_acc'] == plain['val_acc']
+    # the host function on the same decoded peaks (pixels already: scale 1) and the raw annotations scaled to the input size
+    preds, gts = [], []
+    for b in batches:
+        peaks = model.val_step(b)['prediction'].cpu().numpy()
+        preds += [ex.peaks_to_points(p, 1, thr) for p in peaks]
+        gts += [sncal.evaluate.scale_points(a, *SIZE) for a in b['annot']]
+    assert sum(len(p) for p in preds) > 0
+    frame, cls, err = ex.host_counts(preds, gts, ts)
+    for i, t in enumerate(ts):
+        want = ex.aggregate_counts(frame[i], cls[i], err[i])
+        got = res.extremities[t]
+        assert xc.same(*[xc.agg_array(r)[0] for r in (got, want)]) and xc.same(*[xc.agg_array(r)[1] for r in (got, want)])
+        assert res[f'val_ext_acc@{t}'] == want['accuracy']['mean'] and res[f'val_ext_precision@{t}'] == want['precision']['mean']
+        assert res[f'val_ext_recall@{t}'] == want['recall']['mean']
+        assert set(got['errors']) == set(want['errors'])
+        for name in want['errors']:
+            assert ulps(np.array(got['errors'][name]), np.array(want['errors'][name])) <= ULP
+    assert frame[..., :3].sum() > 0 and res.extremities[20]['frames'] == res.frames
+    # the iterable form needs the annotations in the batch dicts
+    bare = [{k: v for k, v in b.items() if k != 'annot'} for b in batches]
+    with pytest.raises(sncal._lib.SncalError, match="'annot'"):
+        sncal.validate.validate_line(model, bare, conf_threshold=thr, input_size=SIZE, extremities=ts)
+    assert sncal.validate.validate_line(model, bare, conf_threshold=thr) == plain
+
+
+def test_validate_line_folder_form_reads_the_annotations(sncal, cuda, line_model, gold_dir, tmp_path):
+    """960 x 540 frames from files: the folder form hands the raw annotations to the metric itself; off, the batch dicts are unchanged."""
+    import validate_line_ref as vr
+    model, g = line_model
+    jpg = np.load(os.path.join(gold_dir, 'jpeg_cases.npz'))
+    labels = [c for c in vr.label_cases(np.load(os.path.join(gold_dir, 'validate_line.npz'))) if c['usable']][:3]
+    for i, case in enumerate(labels):
+        with open(tmp_path / f'{i:05d}.json', 'w') as f:
+            json.dump({cls: [{'x': x, 'y': y} for x, y in pts] for cls, pts in case['points'].items()}, f)
+        with open(tmp_path / f'{i:05d}.jpg', 'wb') as f:
+            f.write(jpg['jpg.full'].tobytes())
+    off = next(iter(sncal.validate.line_folder_batches(str(tmp_path), 2, cuda, 23, (960, 540), 0, [])))
+    on = next(iter(sncal.validate.line_folder_batches(str(tmp_path), 2, cuda, 23, (960, 540), 0, [], annots=True)))
+    assert sorted(off) == ['image', 'img_name', 'keypoints', 'line_para'] and sorted(on) == sorted(list(off) + ['annot'])
+    assert on['annot'] == [json.load(open(tmp_path / n.replace('.jpg', '.json'))) for n in on['img_name']]
+    plain = sncal.validate.validate_line(model, str(tmp_path), batch_size=2)
+    res = sncal.validate.validate_line(model, str(tmp_path), batch_size=2, extremities=(10,))
+    assert sorted(plain) == ['val_acc', 'val_loss'] and all(res[k] == plain[k] for k in plain)
+    assert sorted(res) == ['val_acc', 'val_ext_acc@10', 'val_ext_precision@10', 'val_ext_recall@10', 'val_loss']
+    assert res.extremities[10]['frames'] == res.frames == 3 and 0.0 <= res['val_ext_acc@10'] <= 1.0

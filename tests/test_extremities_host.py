@@ -1,0 +1,201 @@
+"""CPU: the host restatement of the dev-kit's extremity metric (sncal_amd.extremities) against what tools/make_golden_extremities.py
+captured from the reference's own functions (tests/golden/extremities.npz): counts, labelling, per-class rows, errors and the
+aggregates; the JSON writer; the argument checks of sncal_extremity_counts, which need no device; the Python surface's own checks."""
+import ctypes
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+
+import extremities_cases as xc
+
+ROOT = xc.ROOT
+
+
+@pytest.fixture(scope='module')
+def gold():
+    return xc.load()
+
+
+@pytest.mark.parametrize('key', ['A', 'B'])
+@pytest.mark.parametrize('form', xc.FORMS)
+def test_host_function_and_aggregation_equal_the_capture(gold, key, form):
+    from sncal_amd import extremities as ex
+    c = xc.case(gold, key)
+    preds, gts = xc.pixels(c, form)
+    want = c[form]
+    frame, cls, err = ex.host_counts(preds, gts, c['ts'])
+    assert np.array_equal(frame, want['frame']) and np.array_equal(cls, want['cls'])
+    assert xc.same(err, want['err'])                                   # numpy on numpy: the same bits
+    assert (cls.sum(axis=2) == frame[..., :3]).all()                   # the per-class rows add up to the frame's
+    for i in range(len(c['ts'])):
+        agg, table = xc.agg_array(ex.aggregate_counts(frame[i], cls[i], err[i]))
+        assert xc.same(agg, want['agg'][i]) and xc.same(table, want['per_class'][i])
+
+
+def test_the_branches_the_fixture_was_built_for(gold):
+    from sncal_amd.annotations import ANNOT_CLASSES
+    cid = {c: i for i, c in enumerate(ANNOT_CLASSES)}
+    a = xc.case(gold, 'A')
+    for form in xc.FORMS:
+        f = a[form]['frame']
+        assert a['B'] == 24 and f.shape == (3, 24, 4) and set(f[..., 3].reshape(-1).tolist()) == {0, 1}
+        assert ((f[..., 0] + f[..., 1]) == 0).any() and ((f[..., 0] + f[..., 2]) == 0).any()          # precision / recall undefined
+        assert not f[:, 7, :2].any()                                                                    # the frame without a prediction
+    assert any(len(v) == 1 for p in a['pred'] for v in p.values())                                    # single-point predictions
+    assert not xc.same(a['packed']['err'], a['peaks']['err'])          # px / (W - 1) * (W - 1) is not always px: the forms differ in bits
+    assert np.array_equal(a['packed']['frame'], a['peaks']['frame'])
+    b = xc.case(gold, 'B')
+    assert b['size'] == (513, 257) and b['scale'] == 1.0
+    fr, cl, er = (b['packed'][k] for k in ('frame', 'cls', 'err'))
+    assert er[0, 0, cid['Side line top'], 0] == 5.0 and fr[0, 0].tolist() == [1, 1, 0, 0]              # exactly the threshold: not a hit
+    assert fr[2, 1].tolist() == [1, 1, 0, 0] and er[2, 1, cid['Side line top'], 1] == 10.0            # the reversed pair
+    assert fr[0, 2].tolist() == [2, 2, 2, 1] and cl[0, 2, cid['Big rect. right main']].tolist() == [2, 0, 0]      # a tie is mirrored
+    assert fr[0, 5].tolist() == [0, 0, 0, 1] and fr[0, 7, 2] == 40
+    assert cl[0, 9, cid['Goal unknown']].tolist() == [0, 0, 2] and cl[0, 9, cid['Line unknown']].tolist() == [0, 0, 1]
+    assert not cl[:, 8, cid['Circle central']].any() and np.isnan(er[:, 8, cid['Circle central']]).all()
+    k = cid['Big rect. left top'] - 3
+    assert b['peak_rows'][10, k, 1, 2] == np.float32(0.2) and b['peaks']['frame'][0, 10].tolist() == [2, 0, 0, 0]      # p == threshold: kept
+
+
+def test_host_function_has_the_reference_signature_and_types():
+    from sncal_amd import extremities as ex
+    gt = {'Side line top': [{'x': 0., 'y': 0.}, {'x': 10., 'y': 0.}], 'Circle central': [{'x': 1., 'y': 1.}]}
+    det = {'Side line top': [{'x': 10., 'y': 1.}, {'x': 0., 'y': 3.}], 'Middle line': [{'x': 5., 'y': 5.}]}
+    conf, per_class, errors = ex.evaluate_detection_prediction(det, gt)            # threshold=2.
+    assert conf.dtype == np.float32 and conf.tolist() == [[1, 2], [0, 0]]
+    assert errors == {'Side line top': [1.0, 3.0]} and set(per_class) == {'Side line top', 'Middle line'}
+    assert per_class['Side line top'].tolist() == [[1, 1], [0, 0]] and per_class['Middle line'].tolist() == [[0, 1], [0, 0]]
+    # both labellings empty or equal: the mirrored one is kept; strictly better: the plain one
+    assert ex.evaluate_frame({}, {}, 5)[3] == 1 and ex.evaluate_frame(det, gt, 5)[3] == 0
+    assert ex.frame_rates(0, 0, 0) == (0., None, None) and type(ex.frame_rates(1, 1, 0)[0]) is np.float32
+
+
+def test_missing_frames_and_empty_lists(gold):
+    from sncal_amd import extremities as ex
+    c = xc.case(gold, 'A')
+    w = c['packed']
+    res = ex.aggregate_counts(w['frame'][1], w['cls'][1], w['err'][1], missing_after=[24, 24])
+    assert xc.same(xc.agg_array(res)[0], gold['A.packed.agg_missing2'][1]) and res['frames'] == 26
+    removed = [int(v) for v in gold['A.folder.removed']]
+    keep = [b for b in range(24) if b not in removed]
+    res = ex.aggregate_counts(w['frame'][1][keep], w['cls'][1][keep], w['err'][1][keep], missing_after=[r - i for i, r in enumerate(removed)])
+    agg, table = xc.agg_array(res)
+    assert float(gold['A.folder.threshold']) == c['ts'][1]
+    assert xc.same(agg, gold['A.folder.agg']) and xc.same(table, gold['A.folder.per_class'])
+    assert ex.summary_lines(res, 'test') == [str(s) for s in gold['A.folder.lines']]
+    errs = res['errors']
+    assert set(errs) <= set(res['per_class']) and all(len(v) % 2 == 0 for v in errs.values())
+    empty = ex.aggregate([], np.zeros((28, 3), np.int64), {})
+    assert np.isnan(empty['accuracy']['mean']) and empty['per_class'] == {} and empty['frames'] == 0
+
+
+def test_json_writer_round_trips_through_scale_points(gold, tmp_path):
+    from sncal_amd import extremities as ex
+    from sncal_amd.evaluate import scale_points
+    c = xc.case(gold, 'A')
+    W, H = c['size']
+    for b in (0, 3, 7):
+        px = ex.peaks_to_points(c['peak_rows'][b], c['scale'], c['p_threshold'])
+        pred = ex.peaks_to_extremities(c['peak_rows'][b], c['size'], c['p_threshold'], scale=c['scale'])
+        path = ex.extremities_path(str(tmp_path), f'{b:05d}.jpg')
+        assert os.path.basename(path) == f'extremities_{b:05d}.json'
+        ex.save_extremities(pred, path)
+        text = open(path).read()
+        assert text == json.dumps(pred, indent=4) and json.loads(text) == pred
+        back = scale_points(json.loads(text), W, H)
+        assert set(back) == set(px) and (b != 7 or back == {})                    # classes without a kept peak are left out
+        for name, pts in px.items():
+            assert len(pts) == len(back[name])
+            for p, q in zip(pts, back[name]):
+                for k in 'xy':                                                    # one rounding each for the division and the product
+                    assert abs(p[k] - q[k]) <= 2 * np.spacing(abs(p[k]))
+    one = np.zeros((23, 2, 3), np.float32)
+    one[4, 1] = (10, 20, 0.2)                                                     # p == threshold: kept; its slot 0 is not
+    assert ex.peaks_to_extremities(one, (960, 540)) == {'Side line bottom': [{'x': 10 / 959, 'y': 20 / 539}]}
+
+
+def test_header_declares_the_entry_point_and_the_library_exports_it():
+    import sncal_amd
+    from sncal_amd.annotations import ANNOT_CLASSES
+    from sncal_amd.evaluate import SYMMETRIC
+    L = sncal_amd._lib.lib()
+    with open(os.path.join(ROOT, 'include', 'sncal.h')) as f:
+        text = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+    assert re.findall(r'\b(sncal_extremity_\w+)\s*\(', text) == ['sncal_extremity_counts']
+    assert hasattr(L, 'sncal_extremity_counts') and 'sncal_extremity_counts' in sncal_amd._lib.SIGNATURES
+    assert 'sncal_extremity_counts' not in sncal_amd._lib.MISSING and L.sncal_version() == 100
+    # the kernel's mirror table is SoccerPitch.symetric_classes in the class order of the packed annotations
+    with open(os.path.join(ROOT, 'soccernet-calibration-sportlight_amd', 'csrc', 'extremity.hip')) as f:
+        m = re.search(r'EX_SYM\[EX_NCLS\] = \{([^}]*)\}', f.read())
+    assert [int(v) for v in m.group(1).split(',')] == [ANNOT_CLASSES.index(SYMMETRIC[c]) for c in ANNOT_CLASSES]
+    assert sncal_amd.extremities.FIRST_LINE == 3 and len(ANNOT_CLASSES) == 28
+
+
+def test_argument_checks_need_no_device():
+    import sncal_amd
+    L = sncal_amd._lib.lib()
+    one = ctypes.c_void_p(16)                     # a non-null dummy pointer; never dereferenced on these paths
+    ts = (ctypes.c_double * 3)(5, 10, 20)
+
+    def call(gt=one, off=one, peaks=one, C=23, pp=None, po=None, B=1, n_cls=28, w=960, h=540, t=ts, n_t=3, fr=one, cl=one, er=one):
+        return L.sncal_extremity_counts(gt, 0, off, peaks, C, 4.0, 0.2, pp, 0, po, B, n_cls, w, h, t, n_t, fr, cl, er, None)
+    assert call(None, None, None, B=0, t=None, fr=None, cl=None, er=None) == 0          # B == 0: no pointer is touched
+    assert call(B=-1) == -1 and b'B=-1' in L.sncal_last_error()
+    assert call(n_cls=26) == -1 and b'n_classes=26' in L.sncal_last_error()
+    for n_t in (0, 9):
+        assert call(n_t=n_t) == -1 and b'n_t' in L.sncal_last_error()
+    assert call(w=0) == -1 and b'image' in L.sncal_last_error()
+    assert call(pp=one, po=one) == -1 and b'exactly one' in L.sncal_last_error()        # both forms
+    assert call(peaks=None) == -1 and b'exactly one' in L.sncal_last_error()            # neither
+    assert call(C=24) == -1 and b'C=24' in L.sncal_last_error()
+    assert call(C=0) == -1 and b'C=0' in L.sncal_last_error()
+    assert call(t=None) == -1 and b'null' in L.sncal_last_error()
+    assert call(off=None) == -1 and b'null' in L.sncal_last_error()
+    assert call(er=None) == -1 and b'null' in L.sncal_last_error()
+    assert call(peaks=None, pp=one, po=None) == -1 and b'null' in L.sncal_last_error()  # packed points without their offsets
+
+
+def test_python_surface_checks():
+    import sncal_amd
+    from sncal_amd import extremities as ex
+    err = sncal_amd._lib.SncalError
+    with pytest.raises(err, match='exactly one'):
+        ex.extremity_counts([{}])
+    with pytest.raises(err, match='exactly one'):
+        ex.extremity_counts([{}], peaks=object(), pred_annots=[{}])
+    with pytest.raises(KeyError):
+        ex.extremity_counts([{'No such line': [(0.1, 0.1)]}], pred_annots=[{}])
+    with pytest.raises(err, match='thresholds'):
+        sncal_amd.ExtremityMetric(thresholds=())
+    with pytest.raises(err, match='thresholds'):
+        sncal_amd.ExtremityMetric(thresholds=range(9))
+    m = sncal_amd.ExtremityMetric()
+    assert (m.thresholds, m.conf_threshold, m.scale, m.img_size) == ((5, 10, 20), 0.2, 4, (960, 540))
+    m.add_missing(2)
+    res = m.compute()
+    assert set(res) == {5, 10, 20} and m.total_frames == 2
+    assert res[10]['accuracy'] == {'mean': 0.0, 'std': 0.0, 'median': 0.0} and res[10]['recall']['mean'] == 0.0 and res[10]['per_class'] == {}
+    state = sncal_amd.validate._State('val')
+    m.epoch_complete(state)
+    assert sorted(state.metrics) == sorted(f'val_ext_{k}@{t}' for k in ('acc', 'precision', 'recall') for t in (5, 10, 20))
+    with pytest.raises(SystemExit):
+        sncal_amd.validate.main(['--data', 'x', '--model', 'y', '--extremities', '5,10,20'])         # goes with --line
+    with pytest.raises(err, match='invalid dataset path'):
+        ex.evaluate_extremities('/no/such/folder', '/nor/this')
+
+
+def test_list_line_split_hands_out_the_raw_annotations_on_request(tmp_path):
+    from sncal_amd import validate
+    good = {'Side line top': [{'x': 0.1, 'y': 0.2}, {'x': 0.8, 'y': 0.25}], 'Circle central': [{'x': 0.5, 'y': 0.5}]}
+    bad = {'Side line top': [{'x': 0.1, 'y': 0.2}]}                                # one point: sort_anno drops the frame
+    for name, annot in (('00000', good), ('00001', bad), ('00002', good)):
+        with open(tmp_path / f'{name}.json', 'w') as f:
+            json.dump(annot, f)
+        (tmp_path / f'{name}.jpg').write_bytes(b'')
+    plain = validate.list_line_split(str(tmp_path))
+    assert len(plain) == 2 and plain[0] == ['00000.jpg', '00002.jpg']
+    names, labels, raw = validate.list_line_split(str(tmp_path), annots=True)
+    assert names == plain[0] and raw == [good, good] and len(labels) == 2
