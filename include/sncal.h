@@ -422,11 +422,15 @@ int sncal_sweep_fold(const double* d_contrib, const int32_t* d_choice, int B, in
  *          (opencv-python==4.7.0.72, requirements.txt:5 -> libjpeg-turbo defaults: JDCT_ISLOW, fancy upsampling)
  * The serial part of a JPEG -- marker parsing and Huffman decoding -- runs on host threads into pinned memory;
  * everything with pixel parallelism runs on the device, bit-exactly as libjpeg-turbo computes it: dequantisation +
- * jidctint.c jpeg_idct_islow, jdsample.c h2v2/h2v1 fancy upsampling, jdcolor.c YCbCr->RGB.  The output (B,H,W,3) BGR
+ * jidctint.c jpeg_idct_islow (samples saturated to 0..255, as its SIMD forms do where jdmaster.c's clamp table would wrap),
+ * jdsample.c h2v2/h2v1 fancy upsampling, jdcolor.c YCbCr->RGB.  The output (B,H,W,3) BGR
  * is the input of sncal_hrnet_forward_u8.
  * Supported: 8-bit sequential DCT (SOF0/SOF1), Huffman, one interleaved scan, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0,
- * restart intervals.  Progressive / arithmetic / CMYK / 4:4:0 / multi-scan -> SNCAL_ERR_UNSUPPORTED; damaged
- * streams -> SNCAL_ERR_ARG; the message names the frame.  A file whose EXIF orientation tag asks for a rotation / flip (cv2.imread applies it)
+ * restart intervals, 0xFF fill bytes in front of markers.  A scan that ends early (with or without EOI) is decoded as libjpeg
+ * does: the MCU in which the data runs out is finished on zero bits, every later MCU keeps zero coefficients (flat grey) -- up to
+ * the next restart marker where the one due is in place, else to the end of the frame.
+ * Progressive / arithmetic / CMYK / 4:4:0 / multi-scan -> SNCAL_ERR_UNSUPPORTED; streams damaged inside their data (a wrong or
+ * missing restart marker, an invalid Huffman code, a coefficient index beyond 63) -> SNCAL_ERR_ARG; the message names the frame.  A file whose EXIF orientation tag asks for a rotation / flip (cv2.imread applies it)
  * -> SNCAL_ERR_UNSUPPORTED as well: the decoder never returns pixels cv2.imread would not.
  * Scaled decode (sncal_jpeg_create_scaled, scale_denom d = 2, 4, 8): libjpeg's own scale_num / scale_denom = 1 / d with every
  * other default kept, i.e. the array cv2.imread(path, cv2.IMREAD_REDUCED_COLOR_2 / _4 / _8) returns, ceil(H / d) x ceil(W / d).

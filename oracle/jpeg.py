@@ -6,9 +6,12 @@ itself is a third-party dependency that is NOT in /root/reference: opencv-python
 (/root/reference/requirements.txt:5), which bundles libjpeg-turbo 2.1.x and runs it with the library
 defaults -- dct_method JDCT_ISLOW, do_fancy_upsampling TRUE, output JCS_RGB swapped to BGR.  This file
 restates the published libjpeg-turbo algorithms for that configuration:
-    entropy decode      jdhuff.c   decode_mcu_slow / HUFF_EXTEND, restart handling jdhuff.c process_restart
-    inverse DCT         jidctint.c jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2), range limit jdmaster.c
-                        prepare_range_limit_table (index masked with RANGE_MASK = 1023)
+    entropy decode      jdhuff.c   decode_mcu_slow / HUFF_EXTEND, restart handling jdhuff.c process_restart; a scan
+                        or an interval that ends early: the starved MCU is finished on zero bits, later ones are
+                        skipped up to the next restart marker (insufficient_data); fill bytes in front of markers are skipped (jdmarker.c next_marker)
+    inverse DCT         jidctint.c jpeg_idct_islow (CONST_BITS 13, PASS1_BITS 2); samples saturated to 0..255 as the
+                        SIMD form (jidctint-sse2 / -avx2) does, which equals jdmaster.c's range limit table within
+                        its range and differs beyond, where the table's index wraps
     chroma upsampling   jdsample.c h2v2_fancy_upsample / h2v1_fancy_upsample (triangle filter, alternating bias),
                         bottom/top row replication of jdmainct.c (set_bottom_pointers)
     colour conversion   jdcolor.c  build_ycc_rgb_table / ycc_rgb_convert (16-bit fixed point)
@@ -131,6 +134,14 @@ class _Bits:
 
     def __init__(self, data: bytes):
         self.d, self.i, self.acc, self.n = data, 0, 0, 0
+        self.pad = 0                                   # how many of the n buffered bits are zeros fed behind the data
+
+    def _behind_ff(self, j):
+        """d[j] == 0xFF: (index, value) of the first byte behind the run of 0xFF.  Fill bytes may precede any marker
+        (T.81 B.1.1.2, jdmarker.c next_marker); the end of the data reads as EOI (jdatasrc.c fill_input_buffer)."""
+        while j < len(self.d) and self.d[j] == 0xFF:
+            j += 1
+        return j, (self.d[j] if j < len(self.d) else 0xD9)
 
     def _fill(self):
         while self.n <= 24:
@@ -138,15 +149,22 @@ class _Bits:
             if self.i < len(self.d):
                 b = self.d[self.i]
                 if b == 0xFF:
-                    nxt = self.d[self.i + 1] if self.i + 1 < len(self.d) else 0xD9
+                    j, nxt = self._behind_ff(self.i)
                     if nxt == 0:
-                        self.i += 2
+                        self.i = j + 1
                     else:
                         b = 0                          # marker: feed zeros, do not advance
+                        self.pad += 8
                 else:
                     self.i += 1
+            else:
+                self.pad += 8
             self.acc = ((self.acc << 8) | b) & 0xFFFFFFFFFF
             self.n += 8
+
+    def starved(self) -> bool:
+        """More bits have been taken than the scan held (jdhuff.c insufficient_data); the zeros sit at the low end."""
+        return self.n < self.pad
 
     def peek16(self) -> int:
         if self.n < 16:
@@ -162,12 +180,20 @@ class _Bits:
         self.n -= k
         return (self.acc >> self.n) & ((1 << k) - 1)
 
-    def restart(self, expect: int):
-        self.n = 0
-        self.acc = 0
-        if self.i + 1 >= len(self.d) or self.d[self.i] != 0xFF or self.d[self.i + 1] != 0xD0 + expect:
+    def restart(self, expect: int) -> bool:
+        """RSTn behind optional fill bytes: taken, True.  Where the scan's data ends instead (EOI, or no byte left) nothing is
+        taken and the MCUs that follow starve (jdmarker.c jpeg_resync_to_restart leaves a non-restart marker in place): False.
+        Anything else raises -- another RSTn, another marker, data; libjpeg would resynchronise by guessing."""
+        self.n = self.acc = self.pad = 0
+        if self.i >= len(self.d):
+            return False
+        j, m = self._behind_ff(self.i) if self.d[self.i] == 0xFF else (self.i, -1)
+        if m == 0xD0 + expect:
+            self.i = j + 1
+            return True
+        if m != 0xD9:
             raise JpegError("restart marker expected")
-        self.i += 2
+        return False
 
 
 def _build_lookup(counts: List[int], symbols: List[int]):
@@ -185,8 +211,10 @@ def _build_lookup(counts: List[int], symbols: List[int]):
 
 
 def decode_coefficients(frame: Dict) -> List[np.ndarray]:
-    """-> per component int16 array (block_rows, block_cols, 64) in natural order, quantised (jdhuff.c decode_mcu)."""
+    """-> per component int16 array (block_rows, block_cols, 64) in natural order, quantised (jdhuff.c decode_mcu).
+    frame["starved_mcu"]: raster index of the first MCU in which the scan's data ran out, None for a whole scan."""
     comps = frame["comps"]
+    frame["starved_mcu"] = None
     hmax = max(c["h"] for c in comps)
     vmax = max(c["v"] for c in comps)
     mcus_x = -(-frame["width"] // (8 * hmax))
@@ -201,15 +229,21 @@ def decode_coefficients(frame: Dict) -> List[np.ndarray]:
     bits = _Bits(frame["scan"])
     pred = [0] * len(comps)
     ri, rcount, rnext = frame["restart"], 0, 0
+    skipping = False                                    # jdhuff.c insufficient_data
     zz = [int(z) for z in ZIGZAG]
     for my in range(mcus_y):
         for mx in range(mcus_x):
             if ri and rcount == ri:
-                bits.restart(rnext)
+                if bits.restart(rnext):
+                    skipping = False                    # process_restart: insufficient_data ends with the marker that was due
+                elif skipping:
+                    return out                          # the scan is over: nothing more can be decoded
                 rnext = (rnext + 1) & 7
                 rcount = 0
                 pred = [0] * len(comps)
             rcount += 1
+            if skipping:
+                continue
             for ci, c in enumerate(comps):
                 dc, ac = looks[(0, c["td"])], looks[(1, c["ta"])]
                 for by in range(c["v"]):
@@ -233,15 +267,25 @@ def decode_coefficients(frame: Dict) -> List[np.ndarray]:
                             r, s = (e & 255) >> 4, e & 15
                             if s:
                                 k += r
-                                if k > 63:
-                                    raise JpegError("coefficient index out of range")
                                 v = bits.get(s)
-                                blk[zz[k]] = v if v >= (1 << (s - 1)) else v - (1 << s) + 1
+                                # on the zeros behind the data libjpeg has no such check: jpeg_natural_order's 16 spare
+                                # entries are all 63
+                                if k > 63 and not bits.starved():
+                                    raise JpegError("coefficient index out of range")
+                                blk[zz[min(k, 63)]] = v if v >= (1 << (s - 1)) else v - (1 << s) + 1
                                 k += 1
                             elif r == 15:
                                 k += 16
                             else:
                                 break
+            # jdhuff.c decode_mcu: the MCU in which the data ran out is finished on zero bits; every later one is skipped (its
+            # blocks stay zero) -- up to the next restart marker, if the scan has intervals and the marker that is due is there
+            if bits.starved():
+                if frame["starved_mcu"] is None:
+                    frame["starved_mcu"] = my * mcus_x + mx
+                if not ri:
+                    return out
+                skipping = True
     return out
 
 
@@ -285,8 +329,10 @@ def idct_islow(coef: np.ndarray, qt: np.ndarray) -> np.ndarray:
     R, Cn, _ = coef.shape
     x = (coef.astype(np.int64) * qt.astype(np.int64)).reshape(R, Cn, 8, 8)
     ws = _idct_1d(x.swapaxes(-1, -2), 11).swapaxes(-1, -2)          # pass 1: columns
-    y = _idct_1d(ws, 18) & 1023                                     # pass 2: rows; RANGE_MASK
-    px = np.where(y < 128, y + 128, np.where(y < 512, 255, np.where(y < 896, 0, y - 896)))
+    # pass 2: rows.  Saturated as libjpeg-turbo's SIMD transform does (packssdw, packsswb, + 128) -- what cv2 runs.  jidctint.c
+    # indexes jdmaster.c's table with (y & RANGE_MASK): the same for -512 <= y < 512, wrapped beyond, where only the zero bits
+    # that finish a starved MCU get (tools/make_golden_jpeg_streams.py holds every such case to libjpeg-turbo's frame)
+    px = np.clip(_idct_1d(ws, 18) + 128, 0, 255)
     return px.transpose(0, 2, 1, 3).reshape(R * 8, Cn * 8).astype(np.uint8)
 
 

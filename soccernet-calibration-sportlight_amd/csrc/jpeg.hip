@@ -6,7 +6,7 @@
 //   host   marker parsing + Huffman decode (bit-serial by construction; one frame per worker thread) into quantised
 //          int16 coefficient blocks in pinned memory -- 3 bytes per pixel for 4:2:0, the same size as the decoded frame
 //   device jpeg_idct_kernel    dequantise + jidctint.c jpeg_idct_islow, 8 lanes per 8x8 block (a column each, then a
-//                              row each, workspace in LDS), samples range-limited as jdmaster.c's table does
+//                              row each, workspace in LDS), samples saturated as libjpeg-turbo's SIMD transform does
 //          jpeg_colour_kernel  jdsample.c h2v2 / h2v1 fancy upsampling (triangle filter with libjpeg's alternating
 //                              rounding bias, edge replication) fused with jdcolor.c ycc_rgb_convert, 4 pixels a lane
 // Integer arithmetic end to end: the result is bit-identical to libjpeg-turbo's (tests/test_jpeg_gpu.py).
@@ -200,16 +200,24 @@ struct BitReader {                  // jdhuff.c jpeg_fill_bit_buffer: 0xFF00 -> 
     const uint8_t* end;
     uint64_t acc = 0;
     int n = 0;
+    int pad = 0;                    // how many of the n buffered bits are zeros fed behind the end of the scan's data
+    bool at_marker = false;         // p stands on a marker (found once: a long run of fill bytes is not walked again for every byte fed)
+    // first byte behind a run of 0xFF at q (q[0] == 0xFF): 0 = a stuffed data byte, else a marker's code; the stream's end reads as EOI
+    // (jdatasrc.c fill_input_buffer).  Any number of 0xFF fill bytes may precede a marker (T.81 B.1.1.2)
+    inline unsigned behind_ff(const uint8_t*& q) const {
+        while (q < end && *q == 0xFF) ++q;
+        return q < end ? *q : 0xD9;
+    }
     inline void fill() {
         while (n <= 56) {
             unsigned b = 0;
-            if (p < end) {
+            if (p < end && !at_marker) {
                 b = *p;
                 if (b == 0xFF) {
-                    const unsigned nx = (p + 1 < end) ? p[1] : 0xD9;
-                    if (nx == 0) p += 2; else b = 0;
+                    const uint8_t* q = p;
+                    if (behind_ff(q) == 0) p = q + 1; else { b = 0; pad += 8; at_marker = true; }
                 } else ++p;
-            }
+            } else pad += 8;
             acc = (acc << 8) | b;
             n += 8;
         }
@@ -217,11 +225,18 @@ struct BitReader {                  // jdhuff.c jpeg_fill_bit_buffer: 0xFF00 -> 
     inline unsigned peek16() { if (n < 16) fill(); return (unsigned)(acc >> (n - 16)) & 0xFFFFu; }
     inline void skip(int k) { n -= k; }
     inline int get(int k) { if (n < k) fill(); n -= k; return (int)((acc >> n) & ((1u << k) - 1)); }
-    bool restart(int expect) {
-        n = 0; acc = 0;
-        if (p + 1 >= end || p[0] != 0xFF || p[1] != 0xD0 + expect) return false;
-        p += 2;
-        return true;
+    // more bits have been taken than the scan held (jdhuff.c insufficient_data): the zeros are all at the buffer's low end
+    inline bool starved() const { return n < pad; }
+    // RSTn behind optional fill bytes.  +1 taken, 0 the scan's data ends here instead (EOI or the stream's end: the MCUs that follow
+    // starve), -1 anything else
+    int restart(int expect) {
+        n = 0; acc = 0; pad = 0; at_marker = false;
+        if (p >= end) return 0;
+        if (*p != 0xFF) return -1;
+        const uint8_t* q = p;
+        const unsigned m = behind_ff(q);
+        if (m == 0xD0u + expect) { p = q + 1; return 1; }
+        return m == 0xD9 ? 0 : -1;
     }
 };
 
@@ -245,15 +260,20 @@ Fail entropy_decode(const Header& h, int16_t* coef) {
     size_t off = 0;
     for (int c = 0; c < h.ncomp; ++c) { base[c] = coef + off; off += (size_t)h.bw[c] * h.bh[c] * 64; }
     int rcount = 0, rnext = 0;
+    bool skipping = false;          // jdhuff.c insufficient_data
     for (int my = 0; my < h.mcus_y; ++my)
         for (int mx = 0; mx < h.mcus_x; ++mx) {
             if (h.restart && rcount == h.restart) {
-                if (!br.restart(rnext)) JFAIL(SNCAL_ERR_ARG, "restart marker RST%d missing at MCU (%d,%d)", rnext, mx, my);
+                const int r = br.restart(rnext);
+                if (r < 0) JFAIL(SNCAL_ERR_ARG, "restart marker RST%d missing at MCU (%d,%d)", rnext, mx, my);
+                if (r > 0) skipping = false;            // jdhuff.c process_restart: insufficient_data ends with the marker that was due
+                else if (skipping) return ok();         // the scan is over: nothing more can be decoded
                 rnext = (rnext + 1) & 7;
                 rcount = 0;
                 pred[0] = pred[1] = pred[2] = 0;
             }
             ++rcount;
+            if (skipping) continue;
             for (int c = 0; c < h.ncomp; ++c) {
                 const Huff& dc = h.huff[0][h.comp[c].td];
                 const Huff& ac = h.huff[1][h.comp[c].ta];
@@ -271,8 +291,10 @@ Fail entropy_decode(const Header& h, int16_t* coef) {
                             s = rs & 15;
                             if (s) {
                                 k += r;
-                                if (k > 63) JFAIL(SNCAL_ERR_ARG, "coefficient index out of range at MCU (%d,%d)", mx, my);
-                                blk[kZigzag[k]] = (int16_t)huff_extend(br.get(s), s);
+                                const int v = huff_extend(br.get(s), s);
+                                // on the zeros behind the data libjpeg has no such check: jpeg_natural_order's 16 spare entries are all 63
+                                if (k > 63 && !br.starved()) JFAIL(SNCAL_ERR_ARG, "coefficient index out of range at MCU (%d,%d)", mx, my);
+                                blk[kZigzag[k > 63 ? 63 : k]] = (int16_t)v;
                                 ++k;
                             } else if (r == 15) {
                                 k += 16;
@@ -281,6 +303,12 @@ Fail entropy_decode(const Header& h, int16_t* coef) {
                             }
                         }
                     }
+            }
+            // jdhuff.c decode_mcu: the MCU in which the data ran out is finished on zero bits; every later one is skipped (its
+            // blocks stay zero) -- up to the next restart marker, if the scan has intervals and the marker that is due is there
+            if (br.starved()) {
+                if (!h.restart) return ok();
+                skipping = true;
             }
         }
     return ok();
@@ -357,8 +385,14 @@ __device__ __forceinline__ void idct8(const int (&x)[8], int (&o)[8]) {
     o[3] = (tmp13 + tmp0 + H) >> SHIFT; o[4] = (tmp13 - tmp0 + H) >> SHIFT;
 }
 
-// range_limit[(x) & RANGE_MASK] of jdmaster.c prepare_range_limit_table, centred on 128
-__device__ __forceinline__ unsigned range_limit(int x) {
+// A sample of the 8x8, 4x4 and 2x2 inverse transforms, centred on 128 and SATURATED to 0..255: libjpeg-turbo's SIMD transforms (what cv2
+// runs) narrow with packssdw / packsswb and then add 128.  jidctint.c / jidctred.c index jdmaster.c's table with (x & RANGE_MASK)
+// instead, which is the same for -512 <= x < 512 and wraps beyond; only a scan that ends early, finished on zero bits, gets there
+// (tests/test_jpeg_streams_gpu.py)
+__device__ __forceinline__ unsigned range_limit(int x) { return (unsigned)min(max(x + 128, 0), 255); }
+
+// range_limit[(x) & RANGE_MASK] of jdmaster.c prepare_range_limit_table, centred on 128: jpeg_idct_1x1, which has no SIMD form
+__device__ __forceinline__ unsigned range_limit_table(int x) {
     const int v = x & 1023;
     return v < 128 ? v + 128 : (v < 512 ? 255 : (v < 896 ? 0 : v - 896));
 }
@@ -504,7 +538,7 @@ __global__ __launch_bounds__(256) void jpeg_idct_scaled_kernel(const int16_t* __
     else if (S == 2) red_rows<2>(ws[ls], i, first, cnt, fd.bw[c], plane, Wp);
     else if (i < cnt) {                                 // jpeg_idct_1x1: the DC term alone
         const int k = first + i, by = k / fd.bw[c], bx = k - by * fd.bw[c];
-        plane[(size_t)by * Wp + bx] = (unsigned char)range_limit(((int)src[i * 64] * (int)q[0] + 4) >> 3);
+        plane[(size_t)by * Wp + bx] = (unsigned char)range_limit_table(((int)src[i * 64] * (int)q[0] + 4) >> 3);
     }
 }
 

@@ -16,6 +16,12 @@ for _k, _v in FIX.items():
 
 
 def range_limit(y):
+    """The 4x4 and 2x2 transforms: saturated, as libjpeg-turbo's SIMD forms (jidctred-sse2) do."""
+    return np.clip(y + 128, 0, 255)
+
+
+def range_limit_table(y):
+    """jpeg_idct_1x1 (plain C, no SIMD form): jdmaster.c's table, its index masked with RANGE_MASK."""
     y = y & 1023
     return np.where(y < 128, y + 128, np.where(y < 512, 255, np.where(y < 896, 0, y - 896)))
 
@@ -45,7 +51,7 @@ def idct_reduced(coef: np.ndarray, qt: np.ndarray, s: int) -> np.ndarray:
     if s == 8:
         return oj.idct_islow(coef, qt)
     if s == 1:
-        return range_limit((coef[..., 0].astype(np.int64) * int(qt[0]) + 4) >> 3).astype(np.uint8)
+        return range_limit_table((coef[..., 0].astype(np.int64) * int(qt[0]) + 4) >> 3).astype(np.uint8)
     p, s1, s2 = {4: (_pass4, 12, 19), 2: (_pass2, 13, 20)}[s]
     x = (coef.astype(np.int64) * qt.astype(np.int64)).reshape(R, C, 8, 8)
     ws = p(x.swapaxes(-1, -2), s1).swapaxes(-1, -2)                  # pass 1 over columns: (R, C, s rows, 8 columns)
@@ -67,16 +73,19 @@ def plan(height: int, width: int, samp, d: int) -> dict:
     return dict(out_hw=(-(-height * m // 8), -(-width * m // 8)), comp_block=block, comp_hw=hw, comp_up=up)
 
 
-def decode_bgr(data: bytes, d: int) -> np.ndarray:
-    """JPEG bytes -> (ceil(H / d), ceil(W / d), 3) uint8 BGR: cv2.imread(path, cv2.IMREAD_REDUCED_COLOR_<d>)."""
-    import sncal_amd
+def decode_bgr(data: bytes, d: int, coefs=None) -> np.ndarray:
+    """JPEG bytes -> (ceil(H / d), ceil(W / d), 3) uint8 BGR: cv2.imread(path, cv2.IMREAD_REDUCED_COLOR_<d>).
+    coefs: the coefficient blocks to transform, where they shall not be the library's host stage's (oracle.jpeg.decode_coefficients)."""
     frame = oj.parse(data)
+    if coefs is None:
+        import sncal_amd
+        coefs = sncal_amd.jpeg.entropy_decode(data)
     comps = frame['comps']
     samp = [(c['h'], c['v']) for c in comps] if len(comps) > 1 else [(1, 1)]
     pl = plan(frame['height'], frame['width'], samp, d)
     OH, OW = pl['out_hw']
     planes = []
-    for cf, c, s, (ph, pw), (uv, uh) in zip(sncal_amd.jpeg.entropy_decode(data), comps, pl['comp_block'], pl['comp_hw'], pl['comp_up']):
+    for cf, c, s, (ph, pw), (uv, uh) in zip(coefs, comps, pl['comp_block'], pl['comp_hw'], pl['comp_up']):
         p = idct_reduced(cf, frame['qt'][c['tq']], s)[:ph, :pw]
         fancy = d < 8 and pw > 2                                     # jinit_upsampler: do_fancy_upsampling && min_DCT_scaled_size > 1
         if (uv, uh) == (1, 2):

@@ -149,7 +149,9 @@ def test_directory_harness_skips_files_the_decoder_cannot_take(sncal, cuda, gold
 def test_directory_harness_survives_an_odd_first_file_and_a_stream_damaged_behind_its_headers(sncal, cuda, gold_dir, tmp_path):
     """The run's frame size is the modal size of the probeable head of the listing, not the first file's; a stream whose entropy
     data is corrupt passes the probe, fails inside the batch decode, and the per-frame re-decode drops only that frame.  (A stream
-    that merely ENDS early is decoded like libjpeg does it -- zero coefficients for the missing MCUs -- and is not an error.)
+    that merely ENDS early is not an error.  As in libjpeg, the MCU in which the data runs out is finished on zero bits, and every
+    later MCU is skipped: its coefficients stay zero and it comes out flat grey -- tests/test_jpeg_streams_host.py and
+    tests/test_jpeg_streams_gpu.py hold that to libjpeg-turbo's frames.)
     A run that lost more than max_skip_fraction of its frames raises."""
     g, _ = _cases(gold_dir)
     full = g['jpg.full'].tobytes()
