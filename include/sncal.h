@@ -96,7 +96,8 @@ int sncal_lines_to_points(const float* d_peaks, int B, float scale, double prob_
 typedef struct {
     int num_classes;            /* 58 keypoint net, 23 line net                                  */
     int stem_width;             /* 64                                                            */
-    int upscale;                /* 2: bilinear x2 of all branches + stem concat; 1: line net     */
+    int upscale;                /* head size / branch 0 size.  1: line net (branches only); 2, 4:   */
+                                /* all branches AND the stem, bilinear, concatenated (hrnet_w48x4: 4) */
     int head_softmax;           /* 0 = LogSoftmax(dim=1) head, 1 = Softmax(dim=1) head           */
     int stage1_blocks;          /* number of Bottleneck blocks in layer1                         */
     int stage1_channels;        /* Bottleneck planes (output = 4x)                               */
@@ -225,7 +226,8 @@ typedef struct {
     int cin, cout, ksize, stride, col_off;   /* col_off: first column of last_layer.0 of a head-internal slice               */
     int in, res, out, base;    /* tensor ids (-1 = none)                                                                       */
     int src[4], nsrc;          /* upsample_add sources                                                                         */
-    int head_direct, head_src[5], head_nsrc, head_fold[2], head_nfold;
+    int head_direct, head_src[5], head_nsrc, head_fold[3], head_nfold;   /* head_direct -1: no tensor sits at head resolution
+                                  (upscale 4); the stem then leads head_fold                                                   */
     int relu, out_coff, out_f32, fp8;        /* fp8: 1 = this conv runs in e4m3 at the current layout, 2 = in split bf16 on the two-team kernel (bf16x3), 3 = in split bf16 on the generic kernel */
     char kernel[96];           /* label of the launch that executed it in the last mode-1 profiled forward ("" = unknown or
                                   executed by the launch of an earlier op: grouped members, second conv of a fused block)      */

@@ -1,4 +1,4 @@
-// Parameters / launchers of the fused head kernels (head.hip, head32.hip, headx3.hip; their shared device pieces: head_frame.hpp).
+// Parameters / launchers of the fused head kernels (head.hip, head32.hip, headx3.hip, headx4.hip; their shared device pieces: head_frame.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -56,6 +56,22 @@ void head32_decode_parts(int h, int w, int* row_parts, int* col_parts);
 bool launch_headx3(const HeadParams& p, hipStream_t s);
 bool headx3_applies(const HeadParams& p);
 bool headx3_enabled();                                     // SNCAL_HEADX3 (0 = the split head on the generic fp32 kernels)
+
+// headx4.hip: the fp16x3 head at upscale 4.  No tensor sits at head resolution there, so the stem joins branches 0 and 1 as a third
+// blended source of stage 1's K (concat order: stem | branch 0 | branch 1); h.direct is null, h.Cd 0, h.nfold 0 and h.fold unused; h.src
+// are the two gathered products as in headx3.
+constexpr int HEADX4_FOLD = 3;
+struct HeadX4Params {
+    HeadParams h;
+    const void* fold[HEADX4_FOLD];     // [N][Hf][Wf][Cf] fp32
+    int Cf[HEADX4_FOLD], Hf[HEADX4_FOLD], Wf[HEADX4_FOLD];
+    float fsy[HEADX4_FOLD], fsx[HEADX4_FOLD];
+};
+bool launch_headx4(const HeadX4Params& p, hipStream_t s);    // false = does not apply, nothing launched
+bool headx4_applies(const HeadX4Params& p);
+// the shape half of headx4_applies, for the layout (before the tensors have their shapes): blended sources of fc[] channels at the
+// align_corners scales fsy[] / fsx[] towards the head, two gathered products at horizontal scales gsx[]
+bool headx4_fits(const int* fc, const float* fsy, const float* fsx, const float* gsx);
 
 // tiles of tile_w x tile_h head pixels and their magic reciprocals (head_tile, head_frame.hpp); returns the block count
 inline unsigned head_set_tiling(HeadParams& q, int tile_w, int tile_h) {

@@ -298,16 +298,27 @@ int run_upadd(const sncal_hrnet& net, const Launch& e, const Call& c) {
 int run_head(const sncal_hrnet& net, const Launch& e, const Call& c) {
     const Op& op = net.ops[e.op];
     const Tensor& to = net.tensors[op.out];
-    HeadParams hp;
-    head_params(net, op, c.sb, hp);
-    hp.direct = c.ws + net.tensors[op.head_direct].offset;
+    HeadX4Params hp4;
+    HeadParams& hp = hp4.h;
+    if (op.head_direct < 0) {      // upscale 4: every source is interpolated
+        headx4_params(net, op, c.sb, hp4);
+        for (int f = 0; f < op.head_nfold; ++f) hp4.fold[f] = c.ws + net.tensors[op.head_fold[f]].offset;
+    } else {
+        head_params(net, op, c.sb, hp);
+        hp.direct = c.ws + net.tensors[op.head_direct].offset;
+        for (int s2 = 0; s2 < op.head_nfold; ++s2) hp.fold[s2] = c.ws + net.tensors[op.head_fold[s2]].offset;
+    }
     for (int s2 = 0; s2 < op.head_nsrc; ++s2) hp.src[s2] = c.ws + net.tensors[op.head_src[s2]].offset;
-    for (int s2 = 0; s2 < op.head_nfold; ++s2) hp.fold[s2] = c.ws + net.tensors[op.head_fold[s2]].offset;
     hp.logits = reinterpret_cast<float*>(c.ws + to.offset);
     if (c.dec == DEC_HEAD) {      // log-softmax and the decode's partial maxima in place of the logits
         int rp, cp;
         head32_decode_parts(to.H, to.W, &rp, &cp);
         hp.dec_row = hp.logits; hp.dec_col = hp.logits + (size_t)c.sb * (net.desc.num_classes - 1) * to.H * rp; hp.dec_C = net.desc.num_classes;
+    }
+    if (op.head_direct < 0) {      // (the layout chose this head by headx4_fits; the rest of headx4_applies holds for every plan it packs)
+        if (!net.x3 || !launch_headx4(hp4, c.stream)) { set_error("upscale-4 head: configuration not served by headx4 (set SNCAL_FUSED_HEAD=0)"); return SNCAL_ERR_STATE; }
+        SNCAL_CHECK_LAUNCH();
+        return SNCAL_OK;
     }
     if (!net.x3) return launch_head_fused(hp, net.head_m2, c.stream);
     if (!launch_headx3(hp, c.stream)) { set_error("fp16x3 head: configuration not served by headx3 (set SNCAL_HEADX3=0)"); return SNCAL_ERR_STATE; }
@@ -380,7 +391,7 @@ int forward_impl(sncal_hrnet* net, const float* d_x, const unsigned char* d_x8, 
     SNCAL_CHECK_ARG(d_heat || d_kpts, "sncal_hrnet_forward: need d_heat or d_kpts");
     SNCAL_CHECK_ARG(!(d_kpts && net->desc.head_softmax), "sncal_hrnet_forward: keypoint decode needs a log-softmax head");
     hipStream_t stream = as_stream(stream_);
-    const int SB = std::max(1, std::min(B, net->subbatch));
+    const int SB = sub_batch(*net, B, H, W);
     int rc = layout(*net, SB, H, W);
     if (rc) return rc;
     if (ws_bytes < net->lay_bytes) { set_error("workspace too small: %zu < %zu", ws_bytes, net->lay_bytes); return SNCAL_ERR_WORKSPACE; }
@@ -445,7 +456,7 @@ extern "C" int sncal_hrnet_create(const sncal_hrnet_desc* desc, int dtype, sncal
     SNCAL_CHECK_ARG(dtype == SNCAL_F32 || dtype == SNCAL_BF16 || dtype == SNCAL_FP8 || dtype == SNCAL_BF16X3, "sncal_hrnet_create: dtype %d", dtype);
     SNCAL_CHECK_ARG(desc->stem_width == 64, "stem_width must be 64 (layer1 input is hard-coded, hrnet.py:273)");
     SNCAL_CHECK_ARG(desc->num_classes >= 2 && desc->num_classes <= 64, "num_classes %d out of range", desc->num_classes);
-    SNCAL_CHECK_ARG(desc->upscale == 1 || desc->upscale == 2, "upscale must be 1 or 2");
+    SNCAL_CHECK_ARG(desc->upscale == 1 || desc->upscale == 2 || desc->upscale == 4, "upscale must be 1, 2 or 4");
     for (int s = 0; s < 3; ++s) {
         SNCAL_CHECK_ARG(desc->num_branches[s] == s + 2, "stage%d must have %d branches", s + 2, s + 2);
         SNCAL_CHECK_ARG(desc->num_modules[s] >= 1 && desc->num_blocks[s] >= 1, "stage%d: modules/blocks", s + 2);
@@ -589,7 +600,7 @@ extern "C" int sncal_hrnet_output_size(const sncal_hrnet* net, int H, int W, int
 extern "C" int sncal_hrnet_workspace(const sncal_hrnet* cnet, int B, int H, int W, size_t* bytes) {
     SNCAL_CHECK_ARG(cnet && bytes && B >= 0 && H >= 32 && W >= 32, "sncal_hrnet_workspace: bad arguments");
     sncal_hrnet* net = const_cast<sncal_hrnet*>(cnet);
-    const int sb = std::max(1, std::min(B, net->subbatch));
+    const int sb = sub_batch(*net, B, H, W);
     int rc = layout(*net, sb, H, W);
     if (rc) return rc;
     if (net->finalized) {         // the schedule the first forward of this shape would build (host work only): sncal_plan_op.launch
@@ -630,7 +641,7 @@ extern "C" int sncal_hrnet_calibrate_fp8_workspace(sncal_hrnet* net, int B, int 
     SNCAL_CHECK_ARG(net && bytes && B >= 0 && H >= 32 && W >= 32, "sncal_hrnet_calibrate_fp8_workspace: bad arguments");
     SNCAL_CHECK_ARG(net->fp8, "sncal_hrnet_calibrate_fp8_workspace: the network was not created with SNCAL_FP8");
     net->calibrating = true; drop_layout(*net);         // the layout sncal_hrnet_calibrate_fp8's forward will use
-    const int rc = layout(*net, std::max(1, std::min(B, net->subbatch)), H, W);
+    const int rc = layout(*net, sub_batch(*net, B, H, W), H, W);
     const size_t n = net->lay_bytes;
     net->calibrating = false; drop_layout(*net);
     if (rc) return rc;
@@ -721,7 +732,7 @@ extern "C" int sncal_hrnet_plan_op(const sncal_hrnet* net, int idx, sncal_plan_o
     for (int i = 0; i < 4; ++i) out->src[i] = op.srcs[i];
     out->head_direct = op.head_direct; out->head_nsrc = op.head_nsrc; out->head_nfold = op.head_nfold;
     for (int i = 0; i < 5; ++i) out->head_src[i] = i < HEAD_MAX_SRC ? op.head_src[i] : -1;
-    for (int i = 0; i < 2; ++i) out->head_fold[i] = i < HEAD_MAX_FOLD ? op.head_fold[i] : -1;
+    for (int i = 0; i < 3; ++i) out->head_fold[i] = i < HEADX4_FOLD ? op.head_fold[i] : -1;
     out->relu = op.relu ? 1 : 0; out->out_coff = op.out_coff; out->out_f32 = op.out_f32 ? 1 : 0;
     if (op.conv >= 0) {
         const ConvLayer& L = net->layers[op.conv];

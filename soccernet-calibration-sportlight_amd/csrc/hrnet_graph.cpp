@@ -307,14 +307,17 @@ struct Builder {
             Op hop; hop.type = OP_HEAD; hop.group = GRP_FUSED; hop.out = logits;
             int col = 0;
             std::vector<int> gathered;
-            if (d.upscale > 1) { hop.head_direct = t_stem; net.head_direct_coff = 0; net.head_direct_c = d.stem_width; col = d.stem_width; gathered = ys; }
+            // upscale 4 (headx4.hip): the head is four times branch 0's size and no tensor sits there; the stem leads the folded sources
+            if (d.upscale > 2) { hop.head_direct = -1; net.head_direct_coff = 0; net.head_direct_c = 0; gathered = ys; gathered.insert(gathered.begin(), t_stem); }
+            else if (d.upscale > 1) { hop.head_direct = t_stem; net.head_direct_coff = 0; net.head_direct_c = d.stem_width; col = d.stem_width; gathered = ys; }
             else { hop.head_direct = ys[0]; net.head_direct_coff = 0; net.head_direct_c = net.tensors[ys[0]].C; col = net.head_direct_c; gathered.assign(ys.begin() + 1, ys.end()); }
             // narrow branches are upsampled inside the head kernel and appended to the stage-1 K dimension (their
             // columns of last_layer.0 follow the direct tensor's in concat order); the wide ones go through
             // t_i = W0_i . b_i at native resolution and are gathered
             net.head_k = net.head_direct_c;
             size_t first = 0;
-            while (first < gathered.size() && hop.head_nfold < HEAD_MAX_FOLD && gathered.size() - first > 2 &&
+            const int max_fold = hop.head_direct < 0 ? HEADX4_FOLD : HEAD_MAX_FOLD;
+            while (first < gathered.size() && hop.head_nfold < max_fold && gathered.size() - first > 2 &&
                    net.head_k + net.tensors[gathered[first]].C <= 224 && net.tensors[gathered[first]].C % 8 == 0 && net.head_k % 8 == 0) {
                 hop.head_fold[hop.head_nfold++] = gathered[first];
                 net.head_k += net.tensors[gathered[first]].C;
@@ -341,7 +344,7 @@ struct Builder {
             const int direct = d.upscale > 1 ? t_stem : ys[0];
             std::vector<int> rest;
             if (d.upscale > 1) rest = ys; else rest.assign(ys.begin() + 1, ys.end());
-            if (rest.size() <= 4) {
+            if (d.upscale <= 2 && rest.size() <= 4) {      // (upscale 4: five interpolated sources and no base -- the reference formulation serves it)
                 int col = 0;
                 const ConvLayer& H0 = net.layers[net.l_head0];
                 const int ld = add_layer("headx.d", "", net.tensors[direct].C, H0.cout, 1, 1, false);

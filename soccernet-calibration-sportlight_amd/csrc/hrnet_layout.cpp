@@ -12,10 +12,10 @@ void sncal::drop_layout(sncal_hrnet& net) {
     net.lay_sb = -1;
 }
 
-int sncal::layout(sncal_hrnet& net, int sb, int H, int W) {
-    if (net.lay_sb == sb && net.lay_h == H && net.lay_w == W) return SNCAL_OK;
-    drop_layout(net);
-    std::vector<Tensor>& T = net.tensors;
+namespace {
+
+// which head formulation serves frames of HxW (net.use_fused / net.use_split; the same for every sub-batch size)
+void choose_head(sncal_hrnet& net, int H, int W) {
     {   // does the fused head apply?  (bf16 path; the direct tensor must already sit at head resolution)
         auto half = [](int v) { return (v + 2 - 3) / 2 + 1; };
         const int sh = half(H), sw = half(W), bh = half(sh), bw = half(sw);
@@ -32,8 +32,52 @@ int sncal::layout(sncal_hrnet& net, int sb, int H, int W) {
             const int w2 = half(half(bw)), w3 = half(w2);
             net.use_fused = nsrc == 2 && head_boxes_fit(align_corners_ratio(w2, sw)) && head_boxes_fit(align_corners_ratio(w3, sw));
         }
+        if (net.x3 && net.fused_enabled && net.desc.upscale == 4 && net.head_packed[HPK_W0_32_LO].p && net.head_ks16 == 13 && net.head_m2 == 4) {
+            // fp16x3 at upscale 4: the fused head without a direct tensor (headx4.hip) when the stem and branches 0 and 1 are its three
+            // blended sources, branches 2 and 3 its two gathered ones, and their boxes fit -- against a head of 4 x branch 0's size
+            // (the scales headx4_params will hand headx4_applies); otherwise the reference formulation serves the head
+            const Op* hop = nullptr;
+            for (const Op& op : net.ops) if (op.type == OP_HEAD) hop = &op;
+            if (hop && hop->head_direct < 0 && hop->head_nfold == HEADX4_FOLD && hop->head_nsrc == 2) {
+                const int hh = bh * 4, hw = bw * 4, h1 = half(bh), w1 = half(bw), w2 = half(w1), w3 = half(w2);
+                const int fh[HEADX4_FOLD] = {sh, bh, h1}, fw[HEADX4_FOLD] = {sw, bw, w1};
+                int fc[HEADX4_FOLD];
+                float fsy[HEADX4_FOLD], fsx[HEADX4_FOLD];
+                for (int f = 0; f < HEADX4_FOLD; ++f) {
+                    fc[f] = net.tensors[hop->head_fold[f]].C;
+                    fsy[f] = align_corners_ratio(fh[f], hh); fsx[f] = align_corners_ratio(fw[f], hw);
+                }
+                const float gsx[2] = {align_corners_ratio(w2, hw), align_corners_ratio(w3, hw)};
+                net.use_fused = headx4_fits(fc, fsy, fsx, gsx);
+            }
+        }
         net.use_split = !net.use_fused && net.has_split && net.dtype == SNCAL_F32 && dims_ok;
     }
+}
+
+// At upscale 4 the reference formulation holds a concat and a hidden tensor of the head's full width at FOUR times branch 0's size
+// (784 channels x 540 x 960 for a 960x540 frame: 1.6 GB each in fp32), so the engines it serves run that many frames at a time that
+// the two stay within this budget.  The fused head (headx4.hip) materialises neither and keeps the caller's sub-batch.
+constexpr size_t X4_HEAD_BUDGET = (size_t)4 << 30;
+
+}  // namespace
+
+int sncal::sub_batch(sncal_hrnet& net, int B, int H, int W) {
+    int sb = std::max(1, std::min(B, net.subbatch));
+    if (net.desc.upscale != 4) return sb;
+    choose_head(net, H, W);
+    if (net.use_fused) return sb;
+    auto half = [](int v) { return (v + 2 - 3) / 2 + 1; };
+    const size_t px = (size_t)half(half(H)) * 4 * half(half(W)) * 4;
+    const size_t per_frame = 2 * px * net.layers[net.l_head0].cout * net.esize;
+    return (int)std::max<size_t>(1, std::min<size_t>(sb, X4_HEAD_BUDGET / per_frame));
+}
+
+int sncal::layout(sncal_hrnet& net, int sb, int H, int W) {
+    if (net.lay_sb == sb && net.lay_h == H && net.lay_w == W) return SNCAL_OK;
+    drop_layout(net);
+    std::vector<Tensor>& T = net.tensors;
+    choose_head(net, H, W);
     for (const Op& op : net.ops) {
         if (!op_active(net, op)) continue;
         switch (op.type) {
@@ -50,7 +94,10 @@ int sncal::layout(sncal_hrnet& net, int sb, int H, int W) {
                 else { T[op.out].H = T[op.dims_from].H * op.dims_mul; T[op.out].W = T[op.dims_from].W * op.dims_mul; }
                 break;
             case OP_SOFTMAX: T[op.out].H = T[op.in].H; T[op.out].W = T[op.in].W; break;
-            case OP_HEAD: T[op.out].H = T[op.head_direct].H; T[op.out].W = T[op.head_direct].W; break;
+            case OP_HEAD:
+                if (op.head_direct >= 0) { T[op.out].H = T[op.head_direct].H; T[op.out].W = T[op.head_direct].W; }
+                else { T[op.out].H = T[net.t_branch0].H * net.desc.upscale; T[op.out].W = T[net.t_branch0].W * net.desc.upscale; }
+                break;
             case OP_DECODE: break;
         }
     }

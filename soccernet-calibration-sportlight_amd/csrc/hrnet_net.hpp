@@ -83,7 +83,8 @@ struct Op {
     int launch_group = -1;                // >= 0: independent convs that may share one grouped launch (consecutive ops)
     bool shared_in = false;               // ... and all members read the SAME input tensor with stride 2 (conv_shared_s2_kernel)
     int head_direct = -1, head_src[HEAD_MAX_SRC] = {-1, -1, -1, -1, -1}, head_nsrc = 0;   // OP_HEAD
-    int head_fold[HEAD_MAX_FOLD] = {-1, -1}, head_nfold = 0;                              // OP_HEAD: branches folded into stage-1 K
+    int head_fold[HEADX4_FOLD] = {-1, -1, -1}, head_nfold = 0;                            // OP_HEAD: sources folded into stage-1 K
+                                                                                          // (head_direct < 0, upscale 4: the stem leads them)
 };
 
 struct Tensor {
@@ -113,7 +114,7 @@ enum LaunchKind {
     LK_BBLOCKX3,     // 48-channel BasicBlock in split arithmetic (bblockx3.hip)
     LK_BBLOCK48,     // 48-channel BasicBlock, bf16 (bblock.hip)
     LK_UPADD,        // upsample + add (ops.hip)
-    LK_HEAD,         // fused head (head.hip / head32.hip / headx3.hip)
+    LK_HEAD,         // fused head (head.hip / head32.hip / headx3.hip / headx4.hip)
     LK_TAIL,         // softmax, or the part of the keypoint decode fused with it
     LK_DECODE,       // keypoint decode (decode.hip)
 };
@@ -259,10 +260,12 @@ int pack_weights(sncal_hrnet& net);
 void release_weights(sncal_hrnet& net);
 // hrnet_layout.cpp: head variant, shapes, lifetimes, workspace offsets (per sub-batch, H, W)
 int layout(sncal_hrnet& net, int sb, int H, int W);
+int sub_batch(sncal_hrnet& net, int B, int H, int W);      // frames per sub-batch of a call of B frames
 void drop_layout(sncal_hrnet& net);
 // hrnet_schedule.cpp: which kernel runs which ops (per layout and sub-batch size), and the predicates layout and launches share
 bool tt_eligible(const sncal_hrnet& net, const Op& op, int sb);
 void head_params(const sncal_hrnet& net, const Op& op, int sb, HeadParams& hp);
+void headx4_params(const sncal_hrnet& net, const Op& op, int sb, HeadX4Params& hp);      // ... of a head without a direct tensor (upscale 4)
 int schedule_for(sncal_hrnet& net, int sb, Schedule** out);
 
 }  // namespace sncal

@@ -330,12 +330,11 @@ void profile_launch(const sncal_hrnet& net, const Schedule& s, Launch& e) {
             break;
         }
         case LK_HEAD: {
-            const Tensor& td = net.tensors[op.head_direct];
             const Tensor& to = net.tensors[op.out];
             const double px = (double)sb * to.H * to.W;
-            r.kernel = net.x3 ? "headx3_fused" : "head_fused";
+            r.kernel = !net.x3 ? "head_fused" : op.head_direct < 0 ? "headx4_fused" : "headx3_fused";
             r.flops = 2.0 * px * net.head_hp * (net.head_k + net.head_m2 * 16);
-            r.bytes = px * (td.C * 2 + to.C * 4);
+            r.bytes = px * ((op.head_direct >= 0 ? net.tensors[op.head_direct].C * 2 : 0) + to.C * 4);
             for (int s2 = 0; s2 < op.head_nsrc; ++s2) { const Tensor& ts = net.tensors[op.head_src[s2]]; r.bytes += (double)sb * ts.H * ts.W * ts.C * 2; }
             for (int s2 = 0; s2 < op.head_nfold; ++s2) { const Tensor& tf = net.tensors[op.head_fold[s2]]; r.bytes += (double)sb * tf.H * tf.W * tf.C * 2; }
             break;
@@ -364,8 +363,11 @@ DecodeAt decode_at(const sncal_hrnet& net, const Schedule& s) {
         if (e.kind == LK_HEAD) {
             const Tensor& to = net.tensors[op.out];
             HeadParams hp;
-            head_params(net, op, sb, hp);
-            if (C > 32 && C <= 64 && (net.x3 ? headx3_applies(hp) : head32_applies(hp)) &&
+            HeadX4Params hp4;
+            bool serves;
+            if (op.head_direct < 0) { headx4_params(net, op, sb, hp4); serves = net.x3 && headx4_applies(hp4); }
+            else { head_params(net, op, sb, hp); serves = net.x3 ? headx3_applies(hp) : head32_applies(hp); }
+            if (C > 32 && C <= 64 && serves &&
                 head32_decode_scratch(sb, C, to.H, to.W) <= to.bytes && th.H == to.H && th.W == to.W) return DEC_HEAD;
         }
         if (e.kind == LK_TAIL) {
@@ -431,11 +433,10 @@ int build_schedule(const sncal_hrnet& net, int sb, Schedule& s) {
 
 // the fused head's parameters that do not point into the workspace
 void sncal::head_params(const sncal_hrnet& net, const Op& op, int sb, HeadParams& hp) {
-    const Tensor& td = net.tensors[op.head_direct];
     const Tensor& to = net.tensors[op.out];
     memset(&hp, 0, sizeof(hp));
     hp.range = net.d_range;
-    hp.Cd = td.C;
+    hp.Cd = op.head_direct >= 0 ? net.tensors[op.head_direct].C : 0;
     hp.w0 = net.head_packed[HPK_W0].p; hp.bias0 = net.d_hb0; hp.w1 = net.head_packed[HPK_W1].p; hp.bias1 = net.d_hb1;
     hp.w0_32 = net.head_packed[HPK_W0_32].p; hp.w1_32 = net.head_packed[HPK_W1_32].p; hp.ks16 = net.head_ks16;
     hp.w0_32_lo = net.head_packed[HPK_W0_32_LO].p; hp.w1_32_lo = net.head_packed[HPK_W1_32_LO].p;
@@ -446,14 +447,28 @@ void sncal::head_params(const sncal_hrnet& net, const Op& op, int sb, HeadParams
         hp.sy[s2] = align_corners_ratio(ts.H, to.H);
         hp.sx[s2] = align_corners_ratio(ts.W, to.W);
     }
-    hp.nfold = op.head_nfold; hp.ks1 = net.head_ks1;
-    for (int s2 = 0; s2 < op.head_nfold; ++s2) {
+    hp.nfold = op.head_direct >= 0 ? op.head_nfold : 0;      // (a head without a direct tensor carries its folds in HeadX4Params)
+    hp.ks1 = net.head_ks1;
+    for (int s2 = 0; s2 < hp.nfold; ++s2) {
         const Tensor& tf = net.tensors[op.head_fold[s2]];
         hp.Cf[s2] = tf.C; hp.Hf[s2] = tf.H; hp.Wf[s2] = tf.W;
         hp.fsy[s2] = align_corners_ratio(tf.H, to.H);
         hp.fsx[s2] = align_corners_ratio(tf.W, to.W);
     }
     hp.N = sb; hp.H = to.H; hp.W = to.W; hp.HP = net.head_hp; hp.NQ = net.head_hp / 32; hp.LC = to.C;
+}
+
+void sncal::headx4_params(const sncal_hrnet& net, const Op& op, int sb, HeadX4Params& hp) {
+    const Tensor& to = net.tensors[op.out];
+    head_params(net, op, sb, hp.h);
+    for (int f = 0; f < HEADX4_FOLD; ++f) {
+        hp.fold[f] = nullptr; hp.Cf[f] = hp.Hf[f] = hp.Wf[f] = 0; hp.fsy[f] = hp.fsx[f] = 0.f;
+        if (f >= op.head_nfold) continue;
+        const Tensor& tf = net.tensors[op.head_fold[f]];
+        hp.Cf[f] = tf.C; hp.Hf[f] = tf.H; hp.Wf[f] = tf.W;
+        hp.fsy[f] = align_corners_ratio(tf.H, to.H);
+        hp.fsx[f] = align_corners_ratio(tf.W, to.W);
+    }
 }
 
 // the schedule of sub-batch size sb at the current layout, built on first use
