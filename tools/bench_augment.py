@@ -8,15 +8,13 @@
 Shapes (16 and 64, 540, 960, 3), all three stages on for every frame.  A/B at the same commit, same device, same process,
 alternating, warmed, device events around the call: ONE fused call (uint8 out, and fp32 CHW out) against
   * the composed path on the device: the same arithmetic in torch ops -- fp64 colour with the fp64 mean, torch.randn noise, flip,
-    permute and div -- with the peak temporary bytes of each (tools/bench_validate.py's helpers);
+    permute and div -- with the peak temporary bytes of each (tools/benchlib.py's helpers);
   * the numpy per-frame restatement (tests/augment_ref.py) on the host, frames/s of ONE process: what a loader worker of the
     reference pays per frame.
 From a kernel trace (a run of its own) the apply kernel's algorithmic bytes over its time against 6.3 TB/s: 3n read + 3n written
 for uint8 out, 3n + 12n for fp32 CHW out; the sums pass (3n read) is listed separately.
 """
 import argparse
-import csv
-import glob
 import json
 import os
 import sys
@@ -24,14 +22,11 @@ import time
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-sys.path.insert(0, ROOT)
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib  # noqa: E402
+sys.path.insert(0, os.path.join(benchlib.ROOT, 'tests'))
 
 H, W = 540, 960
-HBM_ACHIEVABLE = 6.3e12          # bytes/s, the achievable HBM rate of the MI355X
 ALL = 7
 
 
@@ -71,7 +66,6 @@ def cpu_frames_per_s(rng, frames=3):
 
 def cells(dev, reps):
     import torch
-    import bench_validate as bv
     import sncal_amd
     rng = np.random.Generator(np.random.PCG64(3))
     out = []
@@ -90,12 +84,12 @@ def cells(dev, reps):
             for _ in range(3):
                 fused(), comp()
             torch.cuda.synchronize()
-            t_f, t_c = bv.timed(fused, reps, comp)
-            sf, sc = bv.stats(t_f), bv.stats(t_c)
+            t_f, t_c = benchlib.timed(fused, reps, comp)
+            sf, sc = benchlib.stats(t_f), benchlib.stats(t_c)
             c = {'shape': [B, H, W, 3], 'output': 'fp32 CHW' if chw else 'uint8', 'status': 'measured', 'fused': sf, 'composed': sc,
                  'speedup_median': round(sc['median_ms'] / sf['median_ms'], 2),
                  'fused_frames_per_s': round(B / (sf['median_ms'] * 1e-3)), 'composed_frames_per_s': round(B / (sc['median_ms'] * 1e-3)),
-                 'fused_peak_temp_bytes': bv.peak_temp(fused), 'composed_peak_temp_bytes': bv.peak_temp(comp)}
+                 'fused_peak_temp_bytes': benchlib.peak_temp(fused), 'composed_peak_temp_bytes': benchlib.peak_temp(comp)}
             print(json.dumps(c), flush=True)
             out.append(c)
         del img
@@ -120,29 +114,20 @@ def kernel_only(dev):
 def read_trace(trace_dir):
     """Medians of the two kernels per batch size and output from rocprofv3's kernel trace.  The grid's y is the batch; a sums
     dispatch is followed by its apply dispatch; calls alternate uint8 (first six of a batch size) and fp32 CHW (last six)."""
-    rows = []
-    for path in glob.glob(os.path.join(trace_dir, '**', '*kernel_trace.csv'), recursive=True):
-        with open(path) as f:
-            rows += [r for r in csv.DictReader(f) if 'augment_' in r.get('Kernel_Name', '')]
-    rows.sort(key=lambda r: int(r['Start_Timestamp']))
     groups = {}
-    for r in rows:
+    for r in benchlib.trace_rows(trace_dir, 'augment_'):
         kind = 'sums' if 'augment_sums' in r['Kernel_Name'] else 'apply'
-        B = int(r['Grid_Size_Y']) // max(int(r.get('Workgroup_Size_Y', 1) or 1), 1)
-        groups.setdefault((kind, B), []).append((int(r['End_Timestamp']) - int(r['Start_Timestamp'])) * 1e-6)
+        groups.setdefault((kind, benchlib.workgroups(r, 'Y')), []).append(benchlib.duration_ms(r))
     res = {}
     for (kind, B), v in groups.items():
         n = B * H * W * 3
         halves = {'': v} if kind == 'sums' else {' uint8': v[:len(v) // 2], ' fp32 CHW': v[len(v) // 2:]}
         for tag, t in halves.items():
-            t = t[1:] if len(t) > 1 else t                  # drop the first (cold) call
             if not t:
                 continue
             nbytes = 3 * n if kind == 'sums' else (6 * n if tag == ' uint8' else 15 * n)
-            med = float(np.median(t))
-            res[f'{kind}{tag} B={B}'] = {'median_ms': round(med, 4), 'min_ms': round(float(min(t)), 4), 'max_ms': round(float(max(t)), 4),
-                                         'calls': len(t), 'algorithmic_bytes': nbytes,
-                                         'share_of_hbm_roof': round(nbytes / (med * 1e-3) / HBM_ACHIEVABLE, 3)}
+            res[f'{kind}{tag} B={B}'] = {**benchlib.call_stats(t), 'algorithmic_bytes': nbytes,
+                                         'share_of_hbm_roof': benchlib.roof_share(nbytes, float(np.median(benchlib.warm(t))))}
     return res
 
 
@@ -182,18 +167,12 @@ def write_md(rep, path):
               'were collected).']
     else:
         L.append(rep.get('kernel_trace_note') or 'not measured')
-    L.append('')
-    with open(path, 'w') as f:
-        f.write('\n'.join(L))
+    benchlib.write_lines(L, path)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--kernel-only', action='store_true')
-    ap.add_argument('--trace-dir', default=None)
-    ap.add_argument('--reps', type=int, default=16)
-    ap.add_argument('--build', default='unlabelled', help='label of the build the figures come from (written into the report)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles'))
+    benchlib.add_common_args(ap, reps=16, trace_dir=True, kernel_only=True)
     a = ap.parse_args()
     import torch
     dev = torch.device('cuda:0')
@@ -202,16 +181,8 @@ def main():
         return
     rep = {'device': torch.cuda.get_device_name(0), 'build': a.build, 'cells': cells(dev, a.reps),
            'cpu_frames_per_s': round(cpu_frames_per_s(np.random.Generator(np.random.PCG64(4))), 2)}
-    if a.trace_dir:
-        try:
-            rep['kernel_trace'] = read_trace(a.trace_dir) or None
-        except (KeyError, ValueError, OSError) as e:          # a trace in another layout: say so, keep the rest of the report
-            rep['kernel_trace'], rep['kernel_trace_note'] = None, f'not measured: the kernel trace could not be read ({e!r})'
-    os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, 'augment.json'), 'w') as f:
-        json.dump(rep, f, indent=1)
-    write_md(rep, os.path.join(a.out, 'augment.md'))
-    print('wrote', os.path.join(a.out, 'augment.json'))
+    benchlib.add_trace(rep, a.trace_dir, read_trace)
+    benchlib.write_report(rep, a.out, 'augment', write_md)
 
 
 if __name__ == '__main__':

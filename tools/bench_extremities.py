@@ -7,14 +7,13 @@
 2. The host restatement (extremities.host_counts: two evaluate_detection_prediction calls per frame and threshold) against ONE device
    call for the batch (extremity_counts: packing, one upload, the launch) at B = 16 and 64, thresholds 5 / 10 / 20, frames of set A
    repeated.  The device call is timed as the host sees it (wall clock, synchronised) and by device events around the launch.
-3. validate_line(folder) frames/s with and without extremities=, on the synthetic split tools/bench_validate_line.py builds, runs
+3. validate_line(folder) frames/s with and without extremities=, on the synthetic split tools/bench_validate_line.py scores, runs
    alternating; --parent-lib PATH adds the same runs of validate_line() in a fresh process that loads the PARENT commit's library
    (SNCAL_LIB_PATH): the parent's own number on the same split.
 """
 import argparse
 import json
 import os
-import shutil
 import subprocess
 import sys
 import tempfile
@@ -22,26 +21,17 @@ import time
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib  # noqa: E402
+sys.path.insert(0, os.path.join(benchlib.ROOT, 'tests'))
+
 TS = (5.0, 10.0, 20.0)
 
 
-def _imports():
-    """The modules that need the library and a device: not loaded for write_md (tests/test_bench_extremities_tool.py)."""
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, HERE)
-    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+def max_ulp(dev):
     import torch
-    import bench_validate as bv
-    import bench_validate_line as bvl
     import extremities_cases as xc
     import sncal_amd
-    return torch, bv, bvl, xc, sncal_amd
-
-
-def max_ulp(dev):
-    torch, _, _, xc, sncal_amd = _imports()
     g = xc.load()
     rows = []
     for key in ('A', 'B'):
@@ -64,7 +54,9 @@ def max_ulp(dev):
 
 
 def host_vs_device(dev, reps):
-    torch, bv, _, xc, sncal_amd = _imports()
+    import torch
+    import extremities_cases as xc
+    import sncal_amd
     ex = sncal_amd.extremities
     c = xc.case(xc.load(), 'A')
     W, H = c['size']
@@ -85,19 +77,14 @@ def host_vs_device(dev, reps):
         for _ in range(3):
             device()
         torch.cuda.synchronize()
-        wall, host = [], []
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            device()
-            torch.cuda.synchronize()
-            wall.append((time.perf_counter() - t0) * 1e3)
+        wall, host = [benchlib.wall(device)[0] * 1e3 for _ in range(reps)], []
         for _ in range(max(3, reps // 8)):
             t0 = time.perf_counter()
             ex.host_counts(preds_px, gts_px, TS)
             host.append((time.perf_counter() - t0) * 1e3)
-        ev, _ = bv.timed(device_packed, reps)
-        cells.append({'B': B, 'thresholds': list(TS), 'status': 'measured', 'host': bv.stats(host), 'device_wall': bv.stats(wall),
-                      'device_events_packed': bv.stats(ev), 'host_ms_per_frame': round(float(np.median(host)) / B, 4),
+        ev, _ = benchlib.timed(device_packed, reps)
+        cells.append({'B': B, 'thresholds': list(TS), 'status': 'measured', 'host': benchlib.stats(host), 'device_wall': benchlib.stats(wall),
+                      'device_events_packed': benchlib.stats(ev), 'host_ms_per_frame': round(float(np.median(host)) / B, 4),
                       'host_over_device_wall': round(float(np.median(host)) / float(np.median(wall)), 1)})
         print(json.dumps(cells[-1]), flush=True)
     return cells
@@ -105,22 +92,11 @@ def host_vs_device(dev, reps):
 
 def validate_rates(dev, runs, with_metric=True, n_frames=512):
     """validate_line(folder) over the synthetic split of tools/bench_validate_line.py: `runs` timed runs per setting, alternating."""
-    torch, bv, bvl, _, sncal_amd = _imports()
-    import bench
-    tmp = tempfile.mkdtemp(prefix='sncal_extremities_')
-    try:
+    import sncal_amd
+    with tempfile.TemporaryDirectory(prefix='sncal_extremities_', ignore_cleanup_errors=True) as tmp:
         folder = os.path.join(tmp, 'valid')
-        source = bv.jpeg_folder(folder, n_frames)
-        cfg = sncal_amd.load_config('line_hrnet_w48')
-        bare = {k: v for k, v in cfg.items() if k not in ('head', 'upscale')}
-        ck = {'model_name': 'EHMMetaModel',
-              'params': {'nn_module': {'hrnet_config': bare, 'num_refinement_stages': 0, 'num_heatmaps': bvl.C},
-                         'loss': {'num_refinement_stages': 0, 'gmse_w': 1.0, 'awing_w': 1.0, 'sigma': 4},
-                         'prediction_transform': {'scale': 4, 'sigma': 3}, 'device': 'cuda:0'},
-              'nn_state_dict': sncal_amd.synth.line_deep_state_dict(bench.seeded_weights('line_hrnet_w48', seed=2))}
-        path = os.path.join(tmp, 'line.pth')
-        torch.save(ck, path)
-        model = sncal_amd.load_model(path, device='cuda:0')
+        source = benchlib.jpeg_folder(folder, n_frames)
+        model = benchlib.line_model(tmp)
         settings = [('off', {})] + ([('on', {'extremities': (5, 10, 20)})] if with_metric else [])
         rows = []
         for bs in (8, 64):
@@ -130,11 +106,8 @@ def validate_rates(dev, runs, with_metric=True, n_frames=512):
                 sncal_amd.validate.validate_line(model, folder, batch_size=bs, **kw)          # warm: workspaces, decoder, allocator
             for _ in range(runs):
                 for name, kw in settings:
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    last[name] = sncal_amd.validate.validate_line(model, folder, batch_size=bs, **kw)
-                    torch.cuda.synchronize()
-                    secs[name].append(time.perf_counter() - t0)
+                    dt, last[name] = benchlib.wall(lambda: sncal_amd.validate.validate_line(model, folder, batch_size=bs, **kw))
+                    secs[name].append(dt)
             for name, _ in settings:
                 res = last[name]
                 rows.append({'batch_size': bs, 'extremities': name, 'frames': res.frames, 'status': 'measured', 'seconds': [round(t, 4) for t in secs[name]],
@@ -143,8 +116,6 @@ def validate_rates(dev, runs, with_metric=True, n_frames=512):
                 print(json.dumps(rows[-1]), flush=True)
         return {'engine': model.nn_module.dtype_name, 'network': 'line_hrnet_w48, random-init weights with the designed signal path',
                 'frames_source': source, 'files': n_frames, 'runs': runs, 'rows': rows}
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
 
 
 def parent_rates(lib, runs):
@@ -205,22 +176,18 @@ def write_md(rep, path):
                   'pinned memory that does not wait for the stream, and one launch.']
     else:
         L.append('not measured')
-    L.append('')
-    with open(path, 'w') as f:
-        f.write('\n'.join(L))
+    benchlib.write_lines(L, path)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--reps', type=int, default=24)
+    benchlib.add_common_args(ap, reps=24)
     ap.add_argument('--runs', type=int, default=3, help='timed validate_line() runs per setting')
     ap.add_argument('--skip-validate', action='store_true')
     ap.add_argument('--parent-lib', default=None, help="the parent commit's libsncal.so: its validate_line() rates are measured beside this build's")
     ap.add_argument('--rates-child', action='store_true', help=argparse.SUPPRESS)
-    ap.add_argument('--build', default='unlabelled', help='label of the build the figures come from (written into the report)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles'))
     a = ap.parse_args()
-    torch = _imports()[0]
+    import torch
     dev = torch.device('cuda:0')
     if a.rates_child:
         print(json.dumps(validate_rates(dev, a.runs, with_metric=False)))
@@ -228,11 +195,7 @@ def main():
     rep = {'device': torch.cuda.get_device_name(0), 'build': a.build, 'ulp': max_ulp(dev), 'host_vs_device': host_vs_device(dev, a.reps)}
     rep['validate'] = None if a.skip_validate else validate_rates(dev, a.runs)
     rep['parent'] = parent_rates(a.parent_lib, a.runs) if a.parent_lib and not a.skip_validate else None
-    os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, 'extremities.json'), 'w') as f:
-        json.dump(rep, f, indent=1)
-    write_md(rep, os.path.join(a.out, 'extremities.md'))
-    print('wrote', os.path.join(a.out, 'extremities.json'))
+    benchlib.write_report(rep, a.out, 'extremities', write_md)
 
 
 if __name__ == '__main__':

@@ -15,8 +15,6 @@ real footage's (fewer non-zero coefficients per block).  Same commit, same proce
   2. JPEG bytes -> cameras, HRNet-W48 fp16x3: reduce=2 into the 540p network against reduce=1 into the 1080p network, frames/s.
 """
 import argparse
-import csv
-import glob
 import json
 import os
 import re
@@ -26,10 +24,9 @@ import time
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-sys.path.insert(0, ROOT)
-sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib  # noqa: E402
+from benchlib import ROOT  # noqa: E402
 
 H, W = 1080, 1920
 KERNELS = ('jpeg_idct_kernel', 'jpeg_idct_scaled_kernel', 'jpeg_colour_kernel')
@@ -37,17 +34,13 @@ KERNELS = ('jpeg_idct_kernel', 'jpeg_idct_scaled_kernel', 'jpeg_colour_kernel')
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument('--kernel-only', action='store_true')
+    benchlib.add_common_args(ap, reps=8, trace_dir=True, kernel_only=True)
     ap.add_argument('--resources', action='store_true')
-    ap.add_argument('--trace-dir', default=None)
-    ap.add_argument('--reps', type=int, default=8)
     ap.add_argument('--batch', type=int, default=64)
     ap.add_argument('--threads', type=int, default=16)
     ap.add_argument('--net-batch', type=int, default=16, help='batch of the bytes-to-cameras legs (the 1080p network is the C5 shape)')
     ap.add_argument('--net-steps', type=int, default=4)
     ap.add_argument('--no-net', action='store_true', help='leave out the bytes-to-cameras legs')
-    ap.add_argument('--build', default='unlabelled', help='label of the build the figures come from (written into the report)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles'))
     a = ap.parse_args(argv)
     if a.reps < 1 or a.batch < 1 or a.threads < 0 or a.net_batch < 1 or a.net_steps < 1:
         ap.error('--reps, --batch, --net-batch and --net-steps are positive, --threads is not negative')
@@ -70,11 +63,6 @@ def frame_bytes(info: dict, layout: dict) -> dict:
     oh, ow = layout['out_hw']
     return {'coefficients_uploaded': coef, 'planes_written': planes, 'frame_written': oh * ow * 3,
             'device_total': 2 * coef + 2 * planes + oh * ow * 3}         # coefficients written by the copy and read once, planes written and read
-
-
-def stats(ms):
-    a = np.sort(np.asarray(ms, dtype=np.float64))
-    return {'median_ms': round(float(np.median(a)), 4), 'min_ms': round(float(a[0]), 4), 'max_ms': round(float(a[-1]), 4), 'reps': len(a)}
 
 
 def decode_cells(dev, a, blob):
@@ -104,23 +92,15 @@ def decode_cells(dev, a, blob):
     nbytes = sum(info['blocks']) * 128 * a.batch
     src = torch.empty(nbytes, dtype=torch.uint8).pin_memory()
     dst = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    copy = []
-    for k in range(a.reps + 2):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        dst.copy_(src, non_blocking=True)
-        e1.record()
-        e1.synchronize()
-        if k >= 2:
-            copy.append(e0.elapsed_time(e1))
+    copy = benchlib.timed(lambda: dst.copy_(src, non_blocking=True), a.reps + 2)[0][2:]          # the first two are warm-up
     cells = []
     for r in (1, 2):
         lay = sncal_amd.jpeg.scaled_layout(info, r)
-        h, t = stats(host[r]), stats(total[r])
+        h, t = benchlib.stats(host[r], percentiles=None), benchlib.stats(total[r], percentiles=None)
         cells.append({'reduce': r, 'batch': a.batch, 'host_threads': a.threads, 'out_hw': list(lay['out_hw']), 'status': 'measured',
                       'host_share': h, 'drained_call': t, 'frames_per_s_drained': round(a.batch / (t['median_ms'] * 1e-3)),
                       'bytes_per_frame': frame_bytes(info, lay)})
-    return cells, {'bytes': nbytes, 'status': 'measured', **stats(copy), 'GB_per_s': round(nbytes / (float(np.median(copy)) * 1e-3) / 1e9, 1)}
+    return cells, {'bytes': nbytes, 'status': 'measured', **benchlib.stats(copy, percentiles=None), 'GB_per_s': round(nbytes / (float(np.median(copy)) * 1e-3) / 1e9, 1)}
 
 
 def net_cells(dev, a, blob):
@@ -157,7 +137,7 @@ def net_cells(dev, a, blob):
             t[r].append((time.perf_counter() - t0) / a.net_steps * 1e3)
     for r in (1, 2):
         decs[r].close()
-        s = stats(t[r])
+        s = benchlib.stats(t[r], percentiles=None)
         res[r] = {'reduce': r, 'network_input': [decs[r].out_height, decs[r].out_width], 'batch': B, 'steps': a.net_steps, 'status': 'measured',
                   'step': s, 'frames_per_s': round(B / (s['median_ms'] * 1e-3), 1)}
     return [res[1], res[2]]
@@ -179,24 +159,13 @@ def kernel_only(dev, a, blob):
 
 def read_trace(trace_dir):
     """Per kernel and scale the median time of rocprofv3's kernel trace, the first (cold) call of each dropped."""
-    rows = []
-    for path in glob.glob(os.path.join(trace_dir, '**', '*kernel_trace.csv'), recursive=True):
-        with open(path) as f:
-            rows += [r for r in csv.DictReader(f) if 'jpeg_' in r.get('Kernel_Name', '')]
-    rows.sort(key=lambda r: int(r['Start_Timestamp']))
     groups, reduce = {}, 1
-    for r in rows:
-        name = next((k for k in KERNELS if k in r['Kernel_Name']), None)
-        if name is None:
-            continue
+    for r in benchlib.trace_rows(trace_dir, *KERNELS):
+        name = next(k for k in KERNELS if k in r['Kernel_Name'])
         if name != 'jpeg_colour_kernel':
             reduce = 2 if name == 'jpeg_idct_scaled_kernel' else 1       # a colour dispatch follows the IDCT of its call
-        groups.setdefault(f'{name} reduce={reduce}', []).append((int(r['End_Timestamp']) - int(r['Start_Timestamp'])) * 1e-6)
-    res = {}
-    for k, v in groups.items():
-        v = v[1:] if len(v) > 1 else v
-        res[k] = {'median_ms': round(float(np.median(v)), 4), 'min_ms': round(float(min(v)), 4), 'max_ms': round(float(max(v)), 4), 'calls': len(v)}
-    return res
+        groups.setdefault(f'{name} reduce={reduce}', []).append(benchlib.duration_ms(r))
+    return {k: benchlib.call_stats(v) for k, v in groups.items()}
 
 
 def resources():
@@ -276,9 +245,7 @@ def write_md(rep, path):
         L += ['', 'jpeg_idct_scaled_kernel holds the 8 / 4 / 2 / 1 instantiations (the block size is the component\'s, chosen inside the one launch).']
     else:
         L.append('not measured')
-    L.append('')
-    with open(path, 'w') as f:
-        f.write('\n'.join(L))
+    benchlib.write_lines(L, path)
 
 
 def main(argv=None):
@@ -302,16 +269,8 @@ def main(argv=None):
             net = None if a.no_net else net_cells(dev, a, blob)
         rep = {'device': torch.cuda.get_device_name(0), 'build': a.build, 'jpeg_bytes_per_frame': len(blob), 'decode': cells, 'copy': copy,
                'net': net, 'resources': old.get('resources')}
-        if a.trace_dir:
-            try:
-                rep['kernel_trace'] = read_trace(a.trace_dir) or None
-            except (KeyError, ValueError, OSError) as e:          # a trace in another layout: say so, keep the rest of the report
-                rep['kernel_trace'], rep['kernel_trace_note'] = None, f'not measured: the kernel trace could not be read ({e!r})'
-    os.makedirs(a.out, exist_ok=True)
-    with open(jpath, 'w') as f:
-        json.dump(rep, f, indent=1)
-    write_md(rep, os.path.join(a.out, 'jpeg_reduced.md'))
-    print('wrote', jpath)
+        benchlib.add_trace(rep, a.trace_dir, read_trace)
+    benchlib.write_report(rep, a.out, 'jpeg_reduced', write_md)
 
 
 if __name__ == '__main__':

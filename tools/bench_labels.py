@@ -13,18 +13,15 @@
 import argparse
 import json
 import os
-import shutil
 import sys
 import tempfile
 import time
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-sys.path.insert(0, ROOT)
-sys.path.insert(0, HERE)
-sys.path.insert(0, os.path.join(ROOT, 'tests'))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib  # noqa: E402
+sys.path.insert(0, os.path.join(benchlib.ROOT, 'tests'))
 
 
 def frames_64():
@@ -46,7 +43,6 @@ def host_ms_per_frame(annots):
 
 def label_cells(dev, reps):
     import torch
-    import bench_validate as bv
     from sncal_amd import annotations as an
     annots = frames_64()
     per = host_ms_per_frame(annots)
@@ -71,45 +67,28 @@ def label_cells(dev, reps):
         for _ in range(3):
             call()
         torch.cuda.synchronize()
-        wall = []
-        for _ in range(reps):
-            t0 = time.perf_counter()
-            call()
-            torch.cuda.synchronize()
-            wall.append((time.perf_counter() - t0) * 1e3)
+        wall = [benchlib.wall(call)[0] * 1e3 for _ in range(reps)]
         points, offsets, pres = an.pack_annotations(batch)
         t0 = time.perf_counter()
         for _ in range(reps):
             an.pack_annotations(batch)
         pack_ms = (time.perf_counter() - t0) * 1e3 / reps
-        ev, _ = bv.timed(call, reps)                        # device events: the upload and the launch, queued behind the host's packing
+        ev, _ = benchlib.timed(call, reps)                        # device events: the upload and the launch, queued behind the host's packing
         host_ms = float(np.sum(per[:B]))
-        c = {'frames': B, 'points': int(len(points)), 'status': 'measured', 'host_ms': round(host_ms, 2), 'device_call_wall': bv.stats(wall),
-             'device_events': bv.stats(ev), 'pack_ms': round(pack_ms, 3),
-             'speedup_wall_median': round(host_ms / bv.stats(wall)['median_ms'], 1)}
+        c = {'frames': B, 'points': int(len(points)), 'status': 'measured', 'host_ms': round(host_ms, 2), 'device_call_wall': benchlib.stats(wall),
+             'device_events': benchlib.stats(ev), 'pack_ms': round(pack_ms, 3),
+             'speedup_wall_median': round(host_ms / benchlib.stats(wall)['median_ms'], 1)}
         print(json.dumps(c), flush=True)
         cells.append(c)
     return host, cells, {'max_label_distance_px': worst, 'presence_identical': bool(same), 'frames': len(annots)}
 
 
 def pipeline_rates(dev, n_frames):
-    import torch
-    import bench
-    import bench_validate as bv
     import sncal_amd
-    tmp = tempfile.mkdtemp(prefix='sncal_labels_')
-    try:
+    with tempfile.TemporaryDirectory(prefix='sncal_labels_', ignore_cleanup_errors=True) as tmp:
         folder = os.path.join(tmp, 'valid')
-        source = bv.jpeg_folder(folder, n_frames)
-        cfg = sncal_amd.load_config('hrnet_w48')
-        ck = {'model_name': 'HRNetMetaModel',
-              'params': {'nn_module': {'hrnet_config': cfg, 'num_refinement_stages': 0, 'num_heatmaps': 58},
-                         'loss': {'num_refinement_stages': 0, 'stride': bv.STRIDE, 'sigma': bv.SIGMA, 'pred_size': [bv.H, bv.W], 'num_keypoints': bv.N},
-                         'prediction_transform': {'size': [540, 960]}, 'device': 'cuda:0'},
-              'nn_state_dict': sncal_amd.synth.peaked_state_dict(bench.seeded_weights('hrnet_w48', seed=1), deep=True)}
-        path = os.path.join(tmp, 'model.pth')
-        torch.save(ck, path)
-        model = sncal_amd.load_model(path, device='cuda:0')
+        source = benchlib.jpeg_folder(folder, n_frames)
+        model = benchlib.keypoint_model(tmp)
         cal = sncal_amd.submit.default_calibrator()
         A, V = sncal_amd.augment, sncal_amd.validate
 
@@ -133,19 +112,13 @@ def pipeline_rates(dev, n_frames):
                 run()                                                      # warm: workspaces, decoder, allocator, sample tables
             for _ in range(3):                                             # alternating
                 for k, run in runs.items():
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    run()
-                    torch.cuda.synchronize()
-                    times[k].append(time.perf_counter() - t0)
+                    times[k].append(benchlib.wall(run)[0])
             for k, t in times.items():
                 row[k + '_frames_per_s'] = round(n_frames / float(np.median(t)), 1)
                 row[k + '_s'] = [round(x, 4) for x in t]
             rows.append(row)
             print(json.dumps(row), flush=True)
         return {'engine': model.nn_module.dtype_name, 'frames_source': source, 'rows': rows}
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
 
 
 def write_md(rep, path):
@@ -181,18 +154,14 @@ def write_md(rep, path):
               'path, the kernel\'s flag on the device path); train_batches runs train_transform() and only delivers the batches (no network).']
     else:
         L.append(rep.get('pipeline_note') or 'not measured')
-    L.append('')
-    with open(path, 'w') as f:
-        f.write('\n'.join(L))
+    benchlib.write_lines(L, path)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--reps', type=int, default=16)
+    benchlib.add_common_args(ap, reps=16)
     ap.add_argument('--frames', type=int, default=256)
     ap.add_argument('--skip-pipeline', action='store_true')
-    ap.add_argument('--build', default='unlabelled', help='label of the build the figures come from (written into the report)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles'))
     a = ap.parse_args()
     import torch
     dev = torch.device('cuda:0')
@@ -202,11 +171,7 @@ def main():
         rep['pipeline'], rep['pipeline_note'] = None, 'not measured (--skip-pipeline)'
     else:
         rep['pipeline'] = pipeline_rates(dev, a.frames)
-    os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, 'labels.json'), 'w') as f:
-        json.dump(rep, f, indent=1)
-    write_md(rep, os.path.join(a.out, 'labels.md'))
-    print('wrote', os.path.join(a.out, 'labels.json'))
+    benchlib.write_report(rep, a.out, 'labels', write_md)
 
 
 if __name__ == '__main__':

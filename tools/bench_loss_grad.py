@@ -10,28 +10,23 @@ the gradient left in .grad): the fused classes (HRNetLoss / EHMLoss on a predict
 torch autograd (create_target or sncal_line_target + the torch ops of the reference's forward, fp32).  Shapes (16 / 64, 58, 270,
 480) and (8 / 64, 23, 135, 240), with and without the wing term.  Peak temporaries are torch.cuda.max_memory_allocated over the
 step minus what was allocated before it (the inputs and the previous step's gradient, released at the start of the step).  The
-timing helpers and the composed forwards are those of tools/bench_validate.py and tools/bench_validate_line.py.
+timing helpers are tools/benchlib.py's; the inputs and the composed forwards are those of tools/bench_validate.py and
+tools/bench_validate_line.py.
 """
 import argparse
-import csv
-import glob
 import json
 import os
-import re
 import sys
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-sys.path.insert(0, ROOT)
-sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib  # noqa: E402
 import bench_validate as bv  # noqa: E402
 import bench_validate_line as bl  # noqa: E402
 import sncal_amd  # noqa: E402
 
-HBM_ACHIEVABLE = bv.HBM_ACHIEVABLE
 KP_ROWS = (('default (l2 1, kldiv 1)', (1.0, 1.0, 0.0)), ('with awing_w 0.5', (1.0, 1.0, 0.5)))
 LINE_ROWS = (('default (gmse 1, awing 1)', (1.0, 1.0)), ('gmse only (no wing term)', (1.0, 0.0)))
 
@@ -51,15 +46,15 @@ def cell(shape, label, fused, composed, grad_only, reps):
     for _ in range(3):
         fused(), composed(), grad_only()
     torch.cuda.synchronize()
-    t_f, t_c = bv.timed(fused, reps, composed)
-    t_g, _ = bv.timed(grad_only, reps)
-    sf, sc, sg = bv.stats(t_f), bv.stats(t_c), bv.stats(t_g)
+    t_f, t_c = benchlib.timed(fused, reps, composed)
+    t_g, _ = benchlib.timed(grad_only, reps)
+    sf, sc, sg = benchlib.stats(t_f), benchlib.stats(t_c), benchlib.stats(t_g)
     n = int(np.prod(shape))
     out = {'shape': list(shape), 'weights': label, 'status': 'measured', 'fused': sf, 'composed': sc, 'fused_grad_call': sg,
            'speedup_median': round(sc['median_ms'] / sf['median_ms'], 2), 'fused_value': a, 'composed_value': b,
-           'fused_peak_temp_bytes': bv.peak_temp(fused), 'composed_peak_temp_bytes': bv.peak_temp(composed),
+           'fused_peak_temp_bytes': benchlib.peak_temp(fused), 'composed_peak_temp_bytes': benchlib.peak_temp(composed),
            'grad_algorithmic_bytes': 8 * n,
-           'grad_call_share_of_hbm_roof': round(8 * n / (sg['median_ms'] * 1e-3) / HBM_ACHIEVABLE, 3)}
+           'grad_call_share_of_hbm_roof': benchlib.roof_share(8 * n, sg['median_ms'])}
     print(json.dumps(out), flush=True)
     return out
 
@@ -128,45 +123,25 @@ def kernel_only(dev):
 
 
 def variant(kernel_name):
-    """loss_grad_kernel<V, MSE, KL, AW> / line_grad_kernel<REBUILD, V, GMSE, AW> -> 'keypoint mse+kl' ...; the trace holds the name
-    demangled or mangled, depending on the profiler's settings."""
-    m = re.search(r'loss_grad_kernel<\s*\d+,\s*(true|false),\s*(true|false),\s*(true|false)\s*>', kernel_name)
-    flags = [f == 'true' for f in m.groups()] if m else None
-    if flags is None:
-        m = re.search(r'loss_grad_kernelILi\d+ELb([01])ELb([01])ELb([01])E', kernel_name)
-        flags = [f == '1' for f in m.groups()] if m else None
-    if flags is not None:
-        return 'keypoint ' + '+'.join(n for n, f in zip(('mse', 'kl', 'awing'), flags) if f)
-    m = re.search(r'line_grad_kernel<\s*(?:true|false),\s*\d+,\s*(true|false),\s*(true|false)\s*>', kernel_name)
-    flags = [f == 'true' for f in m.groups()] if m else None
-    if flags is None:
-        m = re.search(r'line_grad_kernelILb[01]ELi\d+ELb([01])ELb([01])E', kernel_name)
-        flags = [f == '1' for f in m.groups()] if m else None
-    if flags is not None:
-        return 'line ' + '+'.join(n for n, f in zip(('gmse', 'awing'), flags) if f)
+    """loss_grad_kernel<V, MSE, KL, AW> / line_grad_kernel<REBUILD, V, GMSE, AW> -> 'keypoint mse+kl' ..."""
+    for model, base, terms in (('keypoint', 'loss_grad_kernel', ('mse', 'kl', 'awing')), ('line', 'line_grad_kernel', (None, 'gmse', 'awing'))):
+        flags = benchlib.template_flags(base, kernel_name)
+        if flags:
+            return model + ' ' + '+'.join(n for n, f in zip(terms, flags) if f and n)
     return kernel_name
 
 
 def read_trace(trace_dir):
     """Per-variant medians of the gradient kernels from rocprofv3's kernel trace (start / end timestamps per dispatch; the grid's z
     tells the batch sizes apart)."""
-    rows = []
-    for path in glob.glob(os.path.join(trace_dir, '**', '*kernel_trace.csv'), recursive=True):
-        with open(path) as f:
-            rows += [r for r in csv.DictReader(f) if '_grad_kernel' in r.get('Kernel_Name', '')]
     out = {}
-    for r in rows:
-        v = variant(r['Kernel_Name'])
-        frames = int(r['Grid_Size_Z']) // max(int(r.get('Workgroup_Size_Z', 1) or 1), 1)
-        out.setdefault(f'{v} B={frames}', []).append((int(r['End_Timestamp']) - int(r['Start_Timestamp'])) * 1e-6)
+    for r in benchlib.trace_rows(trace_dir, '_grad_kernel'):
+        out.setdefault((variant(r['Kernel_Name']), benchlib.workgroups(r, 'Z')), []).append(benchlib.duration_ms(r))
     res = {}
-    for k, v in out.items():
-        v = v[1:] if len(v) > 1 else v                      # dispatches are in time order: drop the first (cold) call
-        B = int(k.rsplit('B=', 1)[1])
-        per_frame = (bv.N + 1) * bv.H * bv.W if k.startswith('keypoint') else bl.C * bl.H * bl.W
-        med = float(np.median(v))
-        res[k] = {'median_ms': round(med, 4), 'min_ms': round(float(min(v)), 4), 'max_ms': round(float(max(v)), 4), 'calls': len(v),
-                  'algorithmic_bytes': 8 * B * per_frame, 'share_of_hbm_roof': round(8 * B * per_frame / (med * 1e-3) / HBM_ACHIEVABLE, 3)}
+    for (v, B), ms in out.items():
+        nbytes = 8 * B * ((bv.N + 1) * bv.H * bv.W if v.startswith('keypoint') else bl.C * bl.H * bl.W)
+        res[f'{v} B={B}'] = {**benchlib.call_stats(ms), 'algorithmic_bytes': nbytes,
+                             'share_of_hbm_roof': benchlib.roof_share(nbytes, float(np.median(benchlib.warm(ms))))}
     return res
 
 
@@ -197,34 +172,20 @@ def write_md(rep, path):
               'say by what (no counters were collected).']
     else:
         L.append(rep.get('kernel_trace_note') or 'not measured')
-    L.append('')
-    with open(path, 'w') as f:
-        f.write('\n'.join(L))
+    benchlib.write_lines(L, path)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--kernel-only', action='store_true')
-    ap.add_argument('--trace-dir', default=None)
-    ap.add_argument('--reps', type=int, default=16)
-    ap.add_argument('--build', default='unlabelled', help='label of the build the figures come from (written into the report)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles'))
+    benchlib.add_common_args(ap, reps=16, trace_dir=True, kernel_only=True)
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     if a.kernel_only:
         kernel_only(dev)
         return
     rep = {'device': torch.cuda.get_device_name(0), 'build': a.build, 'cells': keypoint_cells(dev, a.reps) + line_cells(dev, a.reps)}
-    if a.trace_dir:
-        try:
-            rep['kernel_trace'] = read_trace(a.trace_dir) or None
-        except (KeyError, ValueError, OSError) as e:          # a trace in another layout: say so, keep the rest of the report
-            rep['kernel_trace'], rep['kernel_trace_note'] = None, f'not measured: the kernel trace could not be read ({e!r})'
-    os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, 'loss_grad.json'), 'w') as f:
-        json.dump(rep, f, indent=1)
-    write_md(rep, os.path.join(a.out, 'loss_grad.md'))
-    print('wrote', os.path.join(a.out, 'loss_grad.json'))
+    benchlib.add_trace(rep, a.trace_dir, read_trace)
+    benchlib.write_report(rep, a.out, 'loss_grad', write_md)
 
 
 if __name__ == '__main__':

@@ -5,28 +5,21 @@
                                                      #   rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/bench_sweep.py --stages-only
     python tools/bench_sweep.py --trace-dir DIR [--bench-json FILE]      # the A/B, then DIR's kernel trace as the three stage times
 
-Both forms score the same synthetic split (tools/bench_validate.py's jpeg_folder) with the same network in the same process,
+Both forms score the same synthetic split (tools/benchlib.py's jpeg_folder) with the same network in the same process,
 alternated, after one warm pass each.  The list form is the baseline; this change does not alter it.  No speed is asserted anywhere.
 --bench-json: a file of `python bench.py` result lines labelled by build ({"build": ..., "result": {...}}), written into the report.
 """
 import argparse
-import csv
-import glob
 import json
 import os
-import shutil
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-import bench  # noqa: E402
-import bench_validate as bv  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib  # noqa: E402
 import sncal_amd  # noqa: E402
 from sncal_amd.prediction import parse_range  # noqa: E402
 
@@ -34,19 +27,6 @@ GRID = {'max_rmse': parse_range('10:70:4'), 'max_rmse_rel': parse_range('4:16:2'
 STAGES = {'solve': ('first_pass_task_kernel', 'first_pass_combine_kernel', 'voter_task_kernel', 'sweep_mark_pending_kernel'),
           'outcome evaluation': ('evaluate_outcomes_kernel',),
           'select + fold': ('sweep_outcomes_kernel', 'sweep_select_kernel', 'sweep_fold_kernel')}
-
-
-def setup(tmp, n_frames):
-    source = bv.jpeg_folder(os.path.join(tmp, 'valid'), n_frames)
-    cfg = sncal_amd.load_config('hrnet_w48')
-    ck = {'model_name': 'HRNetMetaModel',
-          'params': {'nn_module': {'hrnet_config': cfg, 'num_refinement_stages': 0, 'num_heatmaps': 58},
-                     'loss': {'num_refinement_stages': 0, 'stride': bv.STRIDE, 'sigma': bv.SIGMA, 'pred_size': [bv.H, bv.W], 'num_keypoints': bv.N},
-                     'prediction_transform': {'size': [540, 960]}, 'device': 'cuda:0'},
-          'nn_state_dict': sncal_amd.synth.peaked_state_dict(bench.seeded_weights('hrnet_w48', seed=1), deep=True)}
-    path = os.path.join(tmp, 'model.pth')
-    torch.save(ck, path)
-    return sncal_amd.load_model(path, device='cuda:0'), os.path.join(tmp, 'valid'), source
 
 
 def calibrators():
@@ -58,14 +38,6 @@ def calibrators():
             c.max_rmse, c.max_rmse_rel = float(a), float(r)
             cams.append(c)
     return base, cams
-
-
-def wall(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    res = fn()
-    torch.cuda.synchronize()
-    return time.perf_counter() - t0, res
 
 
 def ab(model, folder, n_frames, reps):
@@ -85,7 +57,7 @@ def ab(model, folder, n_frames, reps):
         t = {'list': [], 'sweep': [], 'single': []}
         for _ in range(reps):
             for name, f in (('list', run_list), ('sweep', run_sweep), ('single', run_single)):
-                dt, res = wall(f)
+                dt, res = benchlib.wall(f)
                 t[name].append(dt)
                 if name == 'list':
                     want = res
@@ -107,14 +79,11 @@ def ab(model, folder, n_frames, reps):
 
 def read_trace(trace_dir, passes_frames):
     """Kernel time of the three stages, summed over the traced passes -> ms per pass and per frame."""
-    rows = []
-    for path in glob.glob(os.path.join(trace_dir, '**', '*kernel_trace.csv'), recursive=True):
-        with open(path) as f:
-            rows += list(csv.DictReader(f))
+    rows = benchlib.trace_rows(trace_dir, *(n for names in STAGES.values() for n in names))
     out = {}
     for stage, names in STAGES.items():
-        sel = [r for r in rows if any(n in r.get('Kernel_Name', '') for n in names)]
-        ms = sum((int(r['End_Timestamp']) - int(r['Start_Timestamp'])) * 1e-6 for r in sel)
+        sel = [r for r in rows if any(n in r['Kernel_Name'] for n in names)]
+        ms = sum(benchlib.duration_ms(r) for r in sel)
         out[stage] = {'kernels': list(names), 'dispatches': len(sel), 'total_ms': round(ms, 3),
                       'ms_per_frame': round(ms / passes_frames, 5) if passes_frames else None}
     return out
@@ -157,25 +126,21 @@ def write_md(rep, path):
             L.append(f"| {b['build']} | {r['value']} | {r['ms_per_step']} | {r['steps']} / {r['warmup']} | {r['cameras_found']} |")
     else:
         L.append('not measured')
-    L.append('')
-    with open(path, 'w') as f:
-        f.write('\n'.join(L))
+    benchlib.write_lines(L, path)
 
 
 def main():
     ap = argparse.ArgumentParser()
+    benchlib.add_common_args(ap, reps=3, trace_dir=True)
     ap.add_argument('--stages-only', action='store_true')
-    ap.add_argument('--trace-dir', default=None)
     ap.add_argument('--bench-json', default=None)
     ap.add_argument('--frames', type=int, default=128)
-    ap.add_argument('--reps', type=int, default=3)
-    ap.add_argument('--build', default='unlabelled', help='label of the build the figures come from (written into the report)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles'))
     a = ap.parse_args()
     stage_passes, stage_batch = 2, 16
-    tmp = tempfile.mkdtemp(prefix='sncal_sweep_')
-    try:
-        model, folder, source = setup(tmp, a.frames)
+    with tempfile.TemporaryDirectory(prefix='sncal_sweep_', ignore_cleanup_errors=True) as tmp:
+        folder = os.path.join(tmp, 'valid')
+        source = benchlib.jpeg_folder(folder, a.frames)
+        model = benchlib.keypoint_model(tmp)
         if a.stages_only:
             base, _ = calibrators()
             for _ in range(stage_passes):
@@ -185,26 +150,17 @@ def main():
         rep = {'device': torch.cuda.get_device_name(0), 'build': a.build, 'frames_source': source, 'engine': model.nn_module.dtype_name,
                'network': 'hrnet_w48, random-init weights with the designed signal path (synth.peaked_state_dict(..., deep=True))',
                'ab': ab(model, folder, a.frames, a.reps)}
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-    if a.trace_dir:
-        try:
-            rep['stages'] = read_trace(a.trace_dir, stage_passes * a.frames)
-            rep['stage_passes'], rep['stage_frames'], rep['stage_batch'] = stage_passes, a.frames, stage_batch
-            if not any(v['dispatches'] for v in rep['stages'].values()):
-                rep['stages'], rep['stages_note'] = None, 'not measured: the kernel trace holds none of the stage kernels'
-        except (KeyError, ValueError, OSError) as e:
-            rep['stages'], rep['stages_note'] = None, f'not measured: the kernel trace could not be read ({e!r})'
+    benchlib.add_trace(rep, a.trace_dir, lambda d: read_trace(d, stage_passes * a.frames), key='stages')
+    if rep.get('stages'):
+        rep['stage_passes'], rep['stage_frames'], rep['stage_batch'] = stage_passes, a.frames, stage_batch
+        if not any(v['dispatches'] for v in rep['stages'].values()):
+            rep['stages'], rep['stages_note'] = None, 'not measured: the kernel trace holds none of the stage kernels'
     if a.bench_json and os.path.exists(a.bench_json):
         with open(a.bench_json) as f:
             lines = [json.loads(ln) for ln in f if ln.strip().startswith('{')]
         rep['bench'] = [{'build': b['build'], 'result': {**{k: b['result'][k] for k in ('metric', 'value', 'ms_per_step', 'steps', 'warmup', 'dtype')},
                                                            'cameras_found': b['result']['config']['cameras_found']}} for b in lines]
-    os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, 'sweep.json'), 'w') as f:
-        json.dump(rep, f, indent=1)
-    write_md(rep, os.path.join(a.out, 'sweep.md'))
-    print('wrote', os.path.join(a.out, 'sweep.json'))
+    benchlib.write_report(rep, a.out, 'sweep', write_md)
 
 
 if __name__ == '__main__':

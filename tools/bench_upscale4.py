@@ -15,10 +15,9 @@ import json
 import os
 import sys
 
-import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib  # noqa: E402
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 H, W = 540, 960
 SPREAD = 0.02          # README: box-to-box spread of bench.py's value
 
@@ -29,14 +28,7 @@ def head_macs_per_frame(h, w, hidden=800, k1=208, classes=64):
     return h * w * hidden * (k1 + 2 * 16 + classes)
 
 
-def stats(ms):
-    ms = np.asarray(ms, dtype=np.float64)
-    return {'median_ms': round(float(np.median(ms)), 3), 'p10_ms': round(float(np.percentile(ms, 10)), 3),
-            'p90_ms': round(float(np.percentile(ms, 90)), 3), 'reps': int(ms.size)}
-
-
 def measure(batch, reps):
-    sys.path.insert(0, ROOT)
     import torch
     import sncal_amd
     from bench import seeded_weights
@@ -55,12 +47,7 @@ def measure(batch, reps):
     torch.cuda.synchronize()
     for _ in range(reps):
         for name, _, net in variants:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            net.forward(x, want_heat=False, decode_size=(H, W))
-            e1.record()
-            e1.synchronize()
-            times[name].append(e0.elapsed_time(e1))
+            times[name] += benchlib.timed(lambda: net.forward(x, want_heat=False, decode_size=(H, W)), 1)[0]
     rows = []
     for name, cfg, net in variants:
         net.set_profiling(1)
@@ -68,7 +55,7 @@ def measure(batch, reps):
         prof = net.get_profile()
         net.set_profiling(0)
         head = [p for p in prof if p['kernel'] in ('headx4_fused', 'headx3_fused')]
-        st = stats(times[name])
+        st = benchlib.stats(times[name], digits=3, minmax=False, percentiles='linear')
         rows.append({'variant': name, 'config': cfg, 'batch': batch, 'status': 'measured', 'forward_ms': st,
                      'frames_per_s': round(batch / st['median_ms'] * 1e3, 1), 'workspace_bytes': int(net.workspace_bytes(batch, H, W)),
                      'sub_batch': net.plan_tensor(0)['sub_batch'],
@@ -109,28 +96,20 @@ def write_md(rep, path):
         d = (t - p) / p
         L += ['| build | frames/s |', '|---|---|', f'| parent commit | {p} |', f'| this commit | {t} |', '',
               f"Difference {d * 100:+.2f} %: {'inside' if abs(d) <= SPREAD else 'OUTSIDE'} the +-{SPREAD * 100:.0f} % box-to-box spread the README states."]
-    L.append('')
-    with open(path, 'w') as f:
-        f.write('\n'.join(L))
+    benchlib.write_lines(L, path)
 
 
 def main():
     ap = argparse.ArgumentParser()
+    benchlib.add_common_args(ap, reps=5)
     ap.add_argument('--batch', type=int, default=16)
-    ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--bench-parent', default=None, help="file with the parent commit's bench.py output")
     ap.add_argument('--bench-this', default=None, help="file with this commit's bench.py output")
-    ap.add_argument('--build', default='unlabelled', help='label of the build the figures come from (written into the report)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles'))
     a = ap.parse_args()
     rep = measure(a.batch, a.reps)
     rep['build'] = a.build
     rep['bench'] = {'parent': _bench_line(a.bench_parent), 'this': _bench_line(a.bench_this)} if a.bench_parent and a.bench_this else None
-    os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, 'upscale4.json'), 'w') as f:
-        json.dump(rep, f, indent=1)
-    write_md(rep, os.path.join(a.out, 'upscale4.md'))
-    print('wrote', os.path.join(a.out, 'upscale4.json'))
+    benchlib.write_report(rep, a.out, 'upscale4', write_md)
 
 
 if __name__ == '__main__':

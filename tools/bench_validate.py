@@ -9,24 +9,18 @@ A/B: fused kernel (sncal_heatmap_loss) vs the composed path (sncal_create_target
 device, same process), alternating, warmed, device events.  The baseline is always the composed path.
 """
 import argparse
-import glob
-import csv
 import json
 import os
-import shutil
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import bench  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib  # noqa: E402
 import sncal_amd  # noqa: E402
 
-HBM_ACHIEVABLE = 6.3e12          # bytes/s, the achievable HBM rate of the MI355X
 N, H, W, SIGMA, STRIDE = 57, 270, 480, 2.0, 2
 
 
@@ -64,39 +58,6 @@ def inputs(B, dev, seed=0):
     return pred, kp.to(dev), mask.to(dev)
 
 
-def timed(fn, reps, other=None):
-    """reps timings of fn in ms (device events), alternating with `other` when given -> (ms list, ms list of other)."""
-    out, out2 = [], []
-    for _ in range(reps):
-        for f, acc in ((fn, out), (other, out2)):
-            if f is None:
-                continue
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            f()
-            b.record()
-            b.synchronize()
-            acc.append(a.elapsed_time(b))
-    return out, out2
-
-
-def peak_temp(fn):
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    base = torch.cuda.memory_allocated()
-    torch.cuda.reset_peak_memory_stats()
-    r = fn()
-    torch.cuda.synchronize()
-    del r
-    return torch.cuda.max_memory_allocated() - base
-
-
-def stats(ms):
-    a = np.sort(np.asarray(ms))
-    return {'median_ms': round(float(np.median(a)), 4), 'min_ms': round(float(a[0]), 4), 'max_ms': round(float(a[-1]), 4),
-            'p10_ms': round(float(a[len(a) // 10]), 4), 'p90_ms': round(float(a[(9 * len(a)) // 10]), 4), 'reps': len(a)}
-
-
 def ab_cells(dev, reps):
     cells = []
     for B in (16, 64):
@@ -113,15 +74,15 @@ def ab_cells(dev, reps):
             for _ in range(3):
                 fused(), composed()
             torch.cuda.synchronize()
-            t_f, t_c = timed(fused, reps, composed)
-            sf, sc = stats(t_f), stats(t_c)
+            t_f, t_c = benchlib.timed(fused, reps, composed)
+            sf, sc = benchlib.stats(t_f), benchlib.stats(t_c)
             bytes_alg = B * (N + 1) * H * W * 4
             cells.append({'shape': [B, N + 1, H, W], 'weights': label, 'status': 'measured', 'fused': sf, 'composed': sc,
                           'speedup_median': round(sc['median_ms'] / sf['median_ms'], 2),
                           'fused_value': a, 'composed_value': b,
-                          'fused_peak_temp_bytes': peak_temp(fused), 'composed_peak_temp_bytes': peak_temp(composed),
+                          'fused_peak_temp_bytes': benchlib.peak_temp(fused), 'composed_peak_temp_bytes': benchlib.peak_temp(composed),
                           'algorithmic_bytes': bytes_alg,
-                          'fused_call_share_of_hbm_roof': round(bytes_alg / (sf['median_ms'] * 1e-3) / HBM_ACHIEVABLE, 3),
+                          'fused_call_share_of_hbm_roof': benchlib.roof_share(bytes_alg, sf['median_ms']),
                           'transcendentals_per_element': '1 exp' if wts[2] == 0 else '1 exp + 2 exp2 + 1 pow + 2 log1p (one of them behind the branch)'})
             print(json.dumps(cells[-1]), flush=True)
         del pred, kp, mask
@@ -140,83 +101,24 @@ def kernel_only(dev):
 
 
 def _variant(kernel_name):
-    """loss_kernel<V, MSE, KL, AW> -> 'mse+kl' ...; the trace holds the name demangled or mangled, depending on the profiler's settings."""
-    import re
-    m = re.search(r'loss_kernel<\s*\d+,\s*(true|false),\s*(true|false),\s*(true|false)\s*>', kernel_name)
-    flags = [f == 'true' for f in m.groups()] if m else None
-    if flags is None:
-        m = re.search(r'loss_kernelILi\d+ELb([01])ELb([01])ELb([01])E', kernel_name)
-        flags = [f == '1' for f in m.groups()] if m else None
-    if flags is None:
-        return kernel_name
-    return '+'.join(n for n, f in zip(('mse', 'kl', 'awing'), flags) if f)
+    """loss_kernel<V, MSE, KL, AW> -> 'mse+kl' ..."""
+    flags = benchlib.template_flags('loss_kernel', kernel_name)
+    return '+'.join(n for n, f in zip(('mse', 'kl', 'awing'), flags) if f) if flags else kernel_name
 
 
 def read_trace(trace_dir):
-    """Per-kernel average of the loss kernels from rocprofv3's kernel trace (start / end timestamps per dispatch, grid size to tell
-    the batch sizes apart)."""
-    rows = []
-    for path in glob.glob(os.path.join(trace_dir, '**', '*kernel_trace.csv'), recursive=True):
-        with open(path) as f:
-            rows += [r for r in csv.DictReader(f) if 'loss_kernel' in r.get('Kernel_Name', '')]
+    """Per-variant medians of the loss kernels from rocprofv3's kernel trace; the grid's z, one frame each, tells the batch sizes apart."""
     out = {}
-    for r in rows:
-        name = r['Kernel_Name']
-        variant = _variant(name)
-        frames = int(r['Grid_Size_Z']) // max(int(r.get('Workgroup_Size_Z', 1) or 1), 1)      # the trace gives work-items; one frame per grid z
-        key = f"{variant} B={frames}"
-        out.setdefault(key, []).append((int(r['End_Timestamp']) - int(r['Start_Timestamp'])) * 1e-6)
-    res = {}
-    for k, v in out.items():
-        v = v[1:] if len(v) > 1 else v                      # dispatches are in time order: drop the first (cold) call
-        B = int(k.rsplit('B=', 1)[1])
-        med = float(np.median(v))
-        res[k] = {'median_ms': round(med, 4), 'min_ms': round(float(min(v)), 4), 'max_ms': round(float(max(v)), 4), 'calls': len(v),
-                  'share_of_hbm_roof': round(B * (N + 1) * H * W * 4 / (med * 1e-3) / HBM_ACHIEVABLE, 3)}
-    return res
-
-
-def jpeg_folder(path, n):
-    """n frames + annotations.  Stamped synthetic frames encoded with Pillow when it is installed (baseline, 4:4:4, quality 98);
-    otherwise the golden 960x540 JPEG, whose pixels mean nothing to the network (no keypoints, trivial solves)."""
-    os.makedirs(path, exist_ok=True)
-    try:
-        from PIL import Image
-        import io
-        frames, _ = sncal_amd.synth.stamped_frames(32, seed=7)
-        blobs = []
-        for f in frames:
-            rgb = np.ascontiguousarray((f[::-1].transpose(1, 2, 0) * 255.0 + 0.5).astype(np.uint8))      # BGR planes -> RGB image
-            buf = io.BytesIO()
-            Image.fromarray(rgb).save(buf, format='JPEG', quality=98, subsampling=0)
-            blobs.append(buf.getvalue())
-        source = 'synth.stamped_frames, 32 distinct frames, Pillow baseline JPEG 4:4:4 q98'
-    except ImportError:
-        g = np.load(os.path.join(ROOT, 'tests', 'golden', 'jpeg_cases.npz'))
-        blobs = [g['jpg.full'].tobytes()]
-        source = 'tests/golden/jpeg_cases.npz jpg.full (no JPEG encoder installed)'
-    for i in range(n):
-        annot, _ = sncal_amd.synth.synthetic_annotation(seed=i % 32)
-        with open(os.path.join(path, f'{i:05d}.json'), 'w') as f:
-            json.dump({c: [{'x': x, 'y': y} for x, y in pts] for c, pts in annot.items()}, f)
-        with open(os.path.join(path, f'{i:05d}.jpg'), 'wb') as f:
-            f.write(blobs[i % len(blobs)])
-    return source
+    for r in benchlib.trace_rows(trace_dir, 'loss_kernel'):
+        out.setdefault((_variant(r['Kernel_Name']), benchlib.workgroups(r, 'Z')), []).append(benchlib.duration_ms(r))
+    return {f'{v} B={B}': {**benchlib.call_stats(ms), 'share_of_hbm_roof': benchlib.roof_share(B * (N + 1) * H * W * 4, float(np.median(benchlib.warm(ms))))}
+            for (v, B), ms in out.items()}
 
 
 def validate_rates(dev, n_frames=256):
-    tmp = tempfile.mkdtemp(prefix='sncal_validate_')
-    try:
-        source = jpeg_folder(os.path.join(tmp, 'valid'), n_frames)
-        cfg = sncal_amd.load_config('hrnet_w48')
-        ck = {'model_name': 'HRNetMetaModel',
-              'params': {'nn_module': {'hrnet_config': cfg, 'num_refinement_stages': 0, 'num_heatmaps': 58},
-                         'loss': {'num_refinement_stages': 0, 'stride': STRIDE, 'sigma': SIGMA, 'pred_size': [H, W], 'num_keypoints': N},
-                         'prediction_transform': {'size': [540, 960]}, 'device': 'cuda:0'},
-              'nn_state_dict': sncal_amd.synth.peaked_state_dict(bench.seeded_weights('hrnet_w48', seed=1), deep=True)}
-        path = os.path.join(tmp, 'model.pth')
-        torch.save(ck, path)
-        model = sncal_amd.load_model(path, device='cuda:0')
+    with tempfile.TemporaryDirectory(prefix='sncal_validate_', ignore_cleanup_errors=True) as tmp:
+        source = benchlib.jpeg_folder(os.path.join(tmp, 'valid'), n_frames)
+        model = benchlib.keypoint_model(tmp)
         cal = sncal_amd.submit.default_calibrator()
         rows = []
         for bs in (16, 64):
@@ -227,11 +129,8 @@ def validate_rates(dev, n_frames=256):
                 run()                                                      # warm: workspaces, decoder, allocator
                 best = []
                 for _ in range(3):
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    res = run()
-                    torch.cuda.synchronize()
-                    best.append(time.perf_counter() - t0)
+                    dt, res = benchlib.wall(run)
+                    best.append(dt)
                 row[name + '_frames_per_s'] = round(n_frames / float(np.median(best)), 1)
                 row[name + '_s'] = [round(t, 4) for t in best]
                 row[name + '_completeness'] = round(float(res['val_completeness'] if name == 'validate' else res['completeness']), 3)
@@ -240,8 +139,6 @@ def validate_rates(dev, n_frames=256):
             print(json.dumps(row), flush=True)
         return {'engine': model.nn_module.dtype_name, 'network': 'hrnet_w48, random-init weights with the designed signal path (synth.peaked_state_dict(..., deep=True))', 'frames_source': source,
                 'rows': rows}
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
 
 
 def write_md(rep, path):
@@ -274,36 +171,22 @@ def write_md(rep, path):
                      f"{r['validate_completeness']} / {r['make_submit_completeness']} |")
     else:
         L.append('not measured')
-    L.append('')
-    with open(path, 'w') as f:
-        f.write('\n'.join(L))
+    benchlib.write_lines(L, path)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--kernel-only', action='store_true')
-    ap.add_argument('--trace-dir', default=None)
-    ap.add_argument('--reps', type=int, default=24)
+    benchlib.add_common_args(ap, reps=24, trace_dir=True, kernel_only=True)
     ap.add_argument('--skip-validate', action='store_true')
-    ap.add_argument('--build', default='unlabelled', help='label of the build the figures come from (written into the report)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles'))
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     if a.kernel_only:
         kernel_only(dev)
         return
     rep = {'device': torch.cuda.get_device_name(0), 'build': a.build, 'ab': ab_cells(dev, a.reps)}
-    if a.trace_dir:
-        try:
-            rep['kernel_trace'] = read_trace(a.trace_dir) or None
-        except (KeyError, ValueError, OSError) as e:          # a trace in another layout: say so, keep the rest of the report
-            rep['kernel_trace'], rep['kernel_trace_note'] = None, f'not measured: the kernel trace could not be read ({e!r})'
+    benchlib.add_trace(rep, a.trace_dir, read_trace)
     rep['validate'] = None if a.skip_validate else validate_rates(dev)
-    os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, 'validate_loss.json'), 'w') as f:
-        json.dump(rep, f, indent=1)
-    write_md(rep, os.path.join(a.out, 'validate_loss.md'))
-    print('wrote', os.path.join(a.out, 'validate_loss.json'))
+    benchlib.write_report(rep, a.out, 'validate_loss', write_md)
 
 
 if __name__ == '__main__':

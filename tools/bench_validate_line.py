@@ -5,25 +5,19 @@
 A/B: the fused loss in its rebuild form (sncal_line_loss from the endpoints: no target written) vs the composed path
 (sncal_line_target + the torch ops of EHMLoss.forward, fp32, same device, same process) at (8,23,135,240) and (64,23,135,240),
 alternating, warmed, device events around the whole call, spread reported.  The maps form (target read from memory) is timed beside
-them.  Then validate_line() frames/s over a synthetic split folder.  The timing helpers are tools/bench_validate.py's.
+them.  Then validate_line() frames/s over a synthetic split folder.  The timing helpers are tools/benchlib.py's.
 """
 import argparse
 import json
 import os
-import shutil
 import sys
 import tempfile
-import time
 
 import numpy as np
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-sys.path.insert(0, ROOT)
-sys.path.insert(0, HERE)
-import bench  # noqa: E402
-import bench_validate as bv  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import benchlib  # noqa: E402
 import sncal_amd  # noqa: E402
 
 C, H, W, TARGET_SIGMA, STRIDE, GMSE_SIGMA = 23, 135, 240, 1.0, 4, 4.0
@@ -79,32 +73,22 @@ def ab_cells(dev, reps):
             for _ in range(3):
                 fused(), composed(), from_maps()
             torch.cuda.synchronize()
-            t_f, t_c = bv.timed(fused, reps, composed)
-            t_m, _ = bv.timed(from_maps, reps)
-            sf, sc, sm = bv.stats(t_f), bv.stats(t_c), bv.stats(t_m)
+            t_f, t_c = benchlib.timed(fused, reps, composed)
+            t_m, _ = benchlib.timed(from_maps, reps)
+            sf, sc, sm = benchlib.stats(t_f), benchlib.stats(t_c), benchlib.stats(t_m)
             cells.append({'shape': [B, C, H, W], 'weights': label, 'status': 'measured', 'fused': sf, 'composed': sc, 'fused_from_maps': sm,
                           'speedup_median': round(sc['median_ms'] / sf['median_ms'], 2), 'fused_value': a, 'composed_value': b,
-                          'fused_peak_temp_bytes': bv.peak_temp(fused), 'composed_peak_temp_bytes': bv.peak_temp(composed),
+                          'fused_peak_temp_bytes': benchlib.peak_temp(fused), 'composed_peak_temp_bytes': benchlib.peak_temp(composed),
                           'algorithmic_bytes': B * C * H * W * 4})
             print(json.dumps(cells[-1]), flush=True)
     return cells
 
 
 def validate_rates(dev, n_frames=512):
-    tmp = tempfile.mkdtemp(prefix='sncal_validate_line_')
-    try:
+    with tempfile.TemporaryDirectory(prefix='sncal_validate_line_', ignore_cleanup_errors=True) as tmp:
         folder = os.path.join(tmp, 'valid')
-        source = bv.jpeg_folder(folder, n_frames)
-        cfg = sncal_amd.load_config('line_hrnet_w48')
-        bare = {k: v for k, v in cfg.items() if k not in ('head', 'upscale')}
-        ck = {'model_name': 'EHMMetaModel',
-              'params': {'nn_module': {'hrnet_config': bare, 'num_refinement_stages': 0, 'num_heatmaps': C},
-                         'loss': {'num_refinement_stages': 0, 'gmse_w': 1.0, 'awing_w': 1.0, 'sigma': 4},
-                         'prediction_transform': {'scale': 4, 'sigma': 3}, 'device': 'cuda:0'},
-              'nn_state_dict': sncal_amd.synth.line_deep_state_dict(bench.seeded_weights('line_hrnet_w48', seed=2))}
-        path = os.path.join(tmp, 'line.pth')
-        torch.save(ck, path)
-        model = sncal_amd.load_model(path, device='cuda:0')
+        source = benchlib.jpeg_folder(folder, n_frames)
+        model = benchlib.line_model(tmp)
         usable = len(sncal_amd.validate.list_line_split(folder)[0])
         rows = []
         for bs in (8, 64):
@@ -113,19 +97,14 @@ def validate_rates(dev, n_frames=512):
             run()                                                          # warm: workspaces, decoder, allocator
             secs = []
             for _ in range(3):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                res = run()
-                torch.cuda.synchronize()
-                secs.append(time.perf_counter() - t0)
+                dt, res = benchlib.wall(run)
+                secs.append(dt)
             rows.append({'batch_size': bs, 'frames': res.frames, 'skipped': len(res.skipped), 'status': 'measured',
                          'frames_per_s': round(res.frames / float(np.median(secs)), 1), 'seconds': [round(t, 4) for t in secs],
                          'val_loss': res['val_loss'], 'val_acc': res['val_acc']})
             print(json.dumps(rows[-1]), flush=True)
         return {'engine': model.nn_module.dtype_name, 'network': 'line_hrnet_w48, random-init weights with the designed signal path (synth.line_deep_state_dict)',
                 'frames_source': source, 'files': n_frames, 'usable_annotations': usable, 'rows': rows}
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
 
 
 def write_md(rep, path):
@@ -152,26 +131,18 @@ def write_md(rep, path):
             L.append(f"| {r['batch_size']} | {r['frames']} | {r['frames_per_s']} | {r['seconds']} | {r['val_loss']:.6g} | {r['val_acc']:.4g} |")
     else:
         L.append('not measured')
-    L.append('')
-    with open(path, 'w') as f:
-        f.write('\n'.join(L))
+    benchlib.write_lines(L, path)
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--reps', type=int, default=24)
+    benchlib.add_common_args(ap, reps=24)
     ap.add_argument('--skip-validate', action='store_true')
-    ap.add_argument('--build', default='unlabelled', help='label of the build the figures come from (written into the report)')
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles'))
     a = ap.parse_args()
     dev = torch.device('cuda:0')
     rep = {'device': torch.cuda.get_device_name(0), 'build': a.build, 'ab': ab_cells(dev, a.reps)}
     rep['validate'] = None if a.skip_validate else validate_rates(dev)
-    os.makedirs(a.out, exist_ok=True)
-    with open(os.path.join(a.out, 'validate_line.json'), 'w') as f:
-        json.dump(rep, f, indent=1)
-    write_md(rep, os.path.join(a.out, 'validate_line.md'))
-    print('wrote', os.path.join(a.out, 'validate_line.json'))
+    benchlib.write_report(rep, a.out, 'validate_line', write_md)
 
 
 if __name__ == '__main__':
