@@ -712,6 +712,51 @@ int sncal_extremity_counts(const double* d_gt_points, int total_points, const in
                            int B, int n_classes, int img_w, int img_h, const double* ts, int n_t, int* d_frame, int* d_class,
                            double* d_err, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Cameras from line extremities: the dev-kit's baseline of the calibration task, per frame, a batch in one launch
+ * replaces the per-frame body of __main__                                baseline/baseline_cameras.py:174-246
+ *          normalization_transform                                       baseline/baseline_cameras.py:13-41
+ *          estimate_homography_from_line_correspondences                 baseline/baseline_cameras.py:44-106
+ *          Camera.from_homography, project_point, refine_camera          baseline/camera.py:121-154, 249-268, 105-119
+ * (named after the reference's file: tests/test_validate_line_host.py and tests/test_extremities_host.py pin the sets of line-model and
+ *  extremity-metric entry points)
+ *   the prediction, exactly one of two forms (those of sncal_extremity_counts):
+ *     d_peaks  (B, C, 2, 3) fp32 rows [x, y, p], channel k = class 3 + k (LINE_CLS order), C <= 23.  A class is kept when BOTH slots
+ *              have p >= p_threshold.  A pixel is float32(x * scale), widened, divided by (img_w - 1, img_h - 1) -- the value an
+ *              extremities_<id>.json of this package holds -- and multiplied by (img_w, img_h) as the baseline reads such a file: the
+ *              same bits as the route through the files.
+ *     d_pred_points, pred_total, d_pred_offsets   (pred_total, 2) fp64 normalised points and (B, n_classes + 1) int32 offsets,
+ *              n_classes = 28 in sncal_keypoint_labels' class order.  A class contributes its first two points, times (img_w, img_h)
+ *              (:188-189: the size, not the size - 1); with fewer than two points, or a range that leaves [0, pred_total], it is
+ *              skipped (the reference raises IndexError there).
+ *   Classes are walked in class order; 'Circle central' and the two 'unknown' classes are skipped.  A kept class appends its two image
+ *   points to the candidates of its two 3-D end points (end points shared between lines merge) and to the image cloud; its line
+ *   p1 x p2 joins the line matches when its coefficients sum to a finite number and the class lies on the lawn (no post, no crossbar,
+ *   no circle).  Fewer than 4 line matches: no camera.  Else: both clouds normalised (the running mean of :22-29), the 2L x 9 system
+ *   of :53-84, its SVD (one-sided Jacobi on the wave; A^T A is never formed) and the right singular vector at index min(2L, 9) - 1
+ *   of the singular values sorted descending, walking up past exact zeros (:87-97) -- with exactly four lines that is the vector of
+ *   the smallest of EIGHT values, not the null vector: the reference's behaviour, kept.  H = inv(T2) V T1 / H[2][2]; focal length
+ *   from the image of the absolute conic, the nearest rotation of [r0 r1 r0 x r1], the position; every 3-D end point that projects
+ *   strictly inside the image takes its nearest candidate (the first of equal ones) when closer than 100 px; with more than 3 such
+ *   matches and refine = 1 the pose is refined by the LM of sncal_pnp_refine_lm (same schedule, cap and stop; SNCAL_SOLVE_SCHEDULE
+ *   applies as there).  refine = 0 stops after from_homography.
+ *   d_cameras (B) the camera, n_points = matches, rmse = mean L2 over the matches (0 without any), status as d_status;
+ *   d_status (B) int32 SNCAL_LINECAM_*;  d_H (B, 9) fp64 the homography, zeros when none was estimated or it is not finite;
+ *   d_n_lines (B) int32 line matches;  d_slots (B, n_slots = 34) int32: per 3-D end point (the distinct end points of the lines,
+ *   sorted by keypoint id) the chosen candidate as class * 2 + end, or -1.
+ * A frame without a camera has a zeroed record: no output holds a NaN.  One wavefront per frame, plain stores, no atomics: a frame's
+ * record depends on neither the batch size nor its position.  B == 0 returns SNCAL_OK without touching a pointer.  Asynchronous on
+ * `stream`; the library allocates nothing and needs no workspace.
+ * ---------------------------------------------------------------------------------------------- */
+enum {
+    SNCAL_LINECAM_NONE = 0,        /* fewer than 4 line matches, no singular vector, or from_homography failed          */
+    SNCAL_LINECAM_HOMOGRAPHY = 1,  /* Camera.from_homography's camera, not refined (refine = 0, or at most 3 matches)    */
+    SNCAL_LINECAM_REFINED = 2      /* refined on its matches                                                             */
+};
+int sncal_baseline_cameras(const float* d_peaks, int C, float scale, float p_threshold, const double* d_pred_points, int pred_total,
+                       const int* d_pred_offsets, int B, int n_classes, int img_w, int img_h, int refine, sncal_camera* d_cameras,
+                       int32_t* d_status, double* d_H, int32_t* d_n_lines, int32_t* d_slots, int n_slots, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

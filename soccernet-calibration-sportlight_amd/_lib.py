@@ -166,6 +166,8 @@ SIGNATURES = {
     'sncal_extremity_counts': (ctypes.c_int, [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_float, ctypes.c_float, vp, ctypes.c_int, vp,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, vp, vp, vp,
                                               vp]),
+    'sncal_baseline_cameras': (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_float, ctypes.c_float, vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int, vp]),
     'sncal_calibrate': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.POINTER(VoterCfg), vp, vp]),
     'sncal_calibrate_workspace': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(VoterCfg), ctypes.POINTER(ctypes.c_size_t)]),
     'sncal_calibrate_ws': (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.POINTER(VoterCfg), vp, vp, ctypes.c_size_t, vp]),

@@ -1,4 +1,4 @@
-// Part of the camera solve: included by solve.hip alone (one translation unit), after solve_homography.hpp.
+// Part of the camera solve: included by solve.hip and by linecam.hip (one translation unit each), after solve_homography.hpp.
 // Camera pose from point matches, K fixed: the pose of a plane homography, residual and Jacobian rows, the four minimisers
 // (refine_pose_lm, lm_solver_pose, cvlevmarq_pose, polish4) and the RANSAC PnP built from them.
 #pragma once
