@@ -757,6 +757,33 @@ int sncal_baseline_cameras(const float* d_peaks, int C, float scale, float p_thr
                        const int* d_pred_offsets, int B, int n_classes, int img_w, int img_h, int refine, sncal_camera* d_cameras,
                        int32_t* d_status, double* d_H, int32_t* d_n_lines, int32_t* d_slots, int n_slots, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Frames of any size: cv2.resize's bilinear (INTER_LINEAR) on uint8 BGR frames, a batch in one launch
+ * replaces cv2.resize(img, (W, H))    src/models/line/dataset.py:73
+ *          the dev-kit's copies       baseline/dataloader.py:62, baseline/detect_extremities.py:237
+ * The arithmetic is OpenCV 4.7's 8-bit path (modules/imgproc/src/resize.cpp, the C / SIMD code), restated:
+ *   taps of one axis, destination index d:  scale = 1.0 / ((double)n_dst / n_src);  f = (float)((d + 0.5) * scale - 0.5) in double
+ *     without contraction;  s = floor(f);  f -= s in float;  c0 = rint((1.f - f) * 2048.f), c1 = rint(f * 2048.f) in float, half to
+ *     even, int16 (they need not sum to 2048).
+ *     x axis (zero_edges = 1): s < 0 -> s = 0, f = 0;  s >= n_src - 1 -> s = n_src - 1, f = 0;  the second column is min(s + 1, w - 1).
+ *     y axis (zero_edges = 0): f is kept and the rows s, s + 1 are clipped to [0, n_src - 1] each, so a first row with s = -1 reads
+ *     row 0 twice with both weights.
+ *   pixel, int32:  h0 = S[y0][x0] * a0 + S[y0][x1] * a1, h1 the same on row y1;
+ *                  out = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2              (0..255 without a clamp)
+ *   w == 2 W and h == 2 H exactly: cv::resize takes its fast area path instead, (a + b + c + d + 2) >> 2 over the 2x2 block; a ratio
+ *   of 2 along one axis only takes the general path.  h == H and w == W is a copy.
+ * sncal_resize_tables is HOST ONLY (no GPU): ofs[n_dst] = s (after the x rule; unclipped under the y rule) and coef[n_dst][2] =
+ * (c0, c1) of one axis, from the same function the kernel forms its taps with on the device.
+ * sncal_resize_u8: d_src (B,h,w,3) uint8 -> d_dst (B,H,W,3) uint8, one pass, no intermediate tensor, no workspace.  B == 0 returns
+ * SNCAL_OK without touching a pointer.  SNCAL_ERR_ARG: a dimension < 1, h*w*3 or H*W*3 >= 2^31, B > 65535, overlapping ranges.
+ * A 16-byte aligned d_dst with H * W % 16 == 0 takes 16-byte stores; anything else takes a byte path that writes the same bits.
+ * Asynchronous on `stream`; the library allocates nothing; vector stores, no atomics: two runs give the same bits.
+ * Pinned to a numpy restatement of the formulas above and to float64 bilinear within < 1 level; OpenCV's own bytes are pinned only
+ * once tests/test_resize_cv2_optional.py has run with a cv2.
+ * ---------------------------------------------------------------------------------------------- */
+int sncal_resize_tables(int n_src, int n_dst, int zero_edges, int32_t* ofs, int16_t* coef);
+int sncal_resize_u8(const unsigned char* d_src, int B, int h, int w, unsigned char* d_dst, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

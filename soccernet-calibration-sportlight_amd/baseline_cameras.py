@@ -261,15 +261,17 @@ def baseline_cameras(soccernet_dir: str, prediction_dir: str, split: str = 'vali
 
 
 def line_model_cameras(img_dir: str, model, save_dir: str, batch_size: int = 64, conf_threshold: float = 0.2, decoder_threads: int = 0,
-                       reduce: int = 1, collect: Optional[list] = None) -> int:
+                       reduce: int = 1, collect: Optional[list] = None, resize=None) -> int:
     """One pass over the .jpg files of img_dir: JPEG decode -> line network -> two-peak decode -> sncal_baseline_cameras on the decoded
     peaks where they lie (no host round trip between the decode and the cameras) -> camera_<id>.json in save_dir -> files written.
-    collect: a list that receives (names, peaks, records, status) per batch, on the device."""
+    collect: a list that receives (names, peaks, records, status) per batch, on the device.
+    resize=(W, H): every frame is brought to W x H after the decode (resize.resize_u8: the cv2.resize of baseline/dataloader.py:62 and
+    detect_extremities.py:237), frames of any size, mixed sizes included (validate.decoded_batches); the cameras are in its pixels."""
     from .interop import save_cameras
     from .validate import decoded_batches
     names = sorted(f for f in os.listdir(img_dir) if f.endswith('.jpg'))
     skipped: List[str] = []
-    frames = decoded_batches(img_dir, names, batch_size, model.device, decoder_threads, skipped, reduce=reduce)
+    frames = decoded_batches(img_dir, names, batch_size, model.device, decoder_threads, skipped, reduce=reduce, resize=resize)
     written = 0
     try:
         for keep, image in frames:
@@ -285,7 +287,8 @@ def line_model_cameras(img_dir: str, model, save_dir: str, batch_size: int = 64,
     return written
 
 
-def main(argv=None):
+def parser():
+    from .validate import add_resize_argument
     ap = argparse.ArgumentParser(description='Baseline for camera parameters extraction (baseline_cameras.py counterpart)')
     ap.add_argument('-s', '--soccernet', default='./annotations', type=str, help='Path to the SoccerNet-V3 dataset folder')
     ap.add_argument('-p', '--prediction', default='./results_bis', required=False, type=str, help='Path to the prediction folder')
@@ -296,12 +299,20 @@ def main(argv=None):
     ap.add_argument('--img-dir', type=str, default=None, help='folder of .jpg frames for the one-pass form')
     ap.add_argument('--save-dir', type=str, default=None, help='where the one-pass form writes camera_<id>.json')
     ap.add_argument('--reduce', type=int, default=1, help='decode the frames at 1/N of their size (1, 2, 4, 8)')
+    add_resize_argument(ap)
+    return ap
+
+
+def main(argv=None):
+    from .validate import parsed_resize
+    ap = parser()
     a = ap.parse_args(argv)
+    resize = parsed_resize(a)
     if a.line_model is not None:
         if not (a.img_dir and a.save_dir):
             ap.error('--line-model needs --img-dir and --save-dir')
         from .metamodel import load_model
-        n = line_model_cameras(a.img_dir, load_model(a.line_model), a.save_dir, reduce=a.reduce)
+        n = line_model_cameras(a.img_dir, load_model(a.line_model), a.save_dir, reduce=a.reduce, resize=resize)
     else:
         n = baseline_cameras(a.soccernet, a.prediction, split=a.split, resolution=(a.resolution_width, a.resolution_height))
     print(f'{n} cameras written')

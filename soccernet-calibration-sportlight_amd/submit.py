@@ -7,10 +7,12 @@
     16-process pool, CameraCreator per row :65-69          one batched solve on a side stream (overlaps the next batch)
     json.dump(cam.to_json_parameters())   :36-37          interop.save_cameras, written while the next batch runs
 
-    python -m sncal_amd.submit --img-dir DIR --model model.pth --save-dir OUT [--lines-file lines.pkl] [--reduce 2]
+    python -m sncal_amd.submit --img-dir DIR --model model.pth --save-dir OUT [--lines-file lines.pkl] [--reduce 2] [--resize 960 540]
 
 --reduce 2 / 4 / 8 (make_submit(..., reduce=)) is the loop whose imread carries cv2.IMREAD_REDUCED_COLOR_2 / _4 / _8: libjpeg's
 scaled decode, so that 1920x1080 footage reaches a network trained at 960x540 at the size it was trained for.
+--resize W H (make_submit(..., resize=(W, H))) is the loop with a cv2.resize(img, (W, H)) behind its imread, on the device
+(resize.resize_u8): 1280x720 footage, or any other size, into that network.  It composes with --reduce.
 """
 import argparse
 import warnings
@@ -28,6 +30,7 @@ from .metamodel import load_model
 from .pipeline import CalibrationPipeline
 from .pitch import PITCH_POINTS
 from .prediction import CameraCreator, camera_from_record
+from .resize import check_size, resize_u8
 
 
 def default_calibrator(lines_file: Optional[str] = None) -> CameraCreator:
@@ -57,7 +60,8 @@ def run_frame_size(img_dir: str, img_names: List[str], sample: int = 32):
 
 
 def make_submit(img_dir: str, model, calibrator: CameraCreator, save_dir: str, batch_size: int = 64,
-                decoder_threads: int = 0, img_names: Optional[List[str]] = None, max_skip_fraction: float = 0.5, reduce: int = 1) -> dict:
+                decoder_threads: int = 0, img_names: Optional[List[str]] = None, max_skip_fraction: float = 0.5, reduce: int = 1,
+                resize=None) -> dict:
     """The directory loop on a non-blocking stream of its own (JPEG decode, network, result copies), never on the legacy null
     stream: the condition for the pipeline's CU-masked solve streams (pipeline.py).  See _make_submit for the loop itself.
 
@@ -65,18 +69,25 @@ def make_submit(img_dir: str, model, calibrator: CameraCreator, save_dir: str, b
     computes when its imread carries cv2.IMREAD_REDUCED_COLOR_2 / _4 / _8 -- not cv2.resize).  The run's size vote and the
     per-file size check stay on the SOURCE size; the network, the pipeline and the calibrator see the reduced frames, and the
     cameras written are in the pixels of the DECODED frame, exactly as in that reference loop.  A caller who wants them in
-    source pixels rescales them with Camera.scale_resolution."""
+    source pixels rescales them with Camera.scale_resolution.
+
+    resize=(W, H): every decoded frame (at 1 / reduce when given) is brought to W x H by resize.resize_u8, cv2.resize's INTER_LINEAR,
+    one more launch per batch between the decoder and the network; the cameras are in the pixels of the RESIZED frame.  The size
+    vote and the double-buffered loop stay on one source size: frames of another size are skipped as without it."""
     check_reduce(reduce)                                                            # refuses a bad denominator before anything runs
+    if resize is not None:
+        resize = check_size(resize)
     own = torch.cuda.Stream(device=model.nn_module.device)
     with torch.cuda.stream(own):
-        res = _make_submit(img_dir, model, calibrator, save_dir, batch_size, decoder_threads, img_names, max_skip_fraction, reduce)
+        res = _make_submit(img_dir, model, calibrator, save_dir, batch_size, decoder_threads, img_names, max_skip_fraction, reduce,
+                           resize)
     own.synchronize()
     return res
 
 
 def _make_submit(img_dir: str, model, calibrator: CameraCreator, save_dir: str, batch_size: int = 64,
                  decoder_threads: int = 0, img_names: Optional[List[str]] = None, max_skip_fraction: float = 0.5,
-                 reduce: int = 1) -> dict:
+                 reduce: int = 1, resize=None) -> dict:
     """Returns {'frames', 'written', 'completeness', 'skipped'} (make_submit.py:72 prints the completeness).  Files the device
     decoder cannot take are skipped with a warning; when more than `max_skip_fraction` of the run was skipped the function
     raises instead of returning a near-empty result that looks like a bad model."""
@@ -92,6 +103,9 @@ def _make_submit(img_dir: str, model, calibrator: CameraCreator, save_dir: str, 
     pipe = CalibrationPipeline(net, calibrator, decode_size=(pt.H, pt.W))
     dec = JpegDecoder(H, W, max_batch=batch_size, threads=decoder_threads, device=net.device, reduce=reduce)     # H, W: the source size
     frames = [torch.empty((batch_size, dec.out_height, dec.out_width, 3), dtype=torch.uint8, device=net.device) for _ in range(2)]
+    # resize: the decoder's frames are resized into buffers of their own, two again (batch k + 1 is resized while batch k's solve reads)
+    sized = None if resize is None else [torch.empty((batch_size, resize[1], resize[0], 3), dtype=torch.uint8, device=net.device)
+                                         for _ in range(2)]
     pending = []                                                                    # (names, records, event)
     written = 0
     skipped = []                                                                    # frames the device decoder cannot take
@@ -139,6 +153,8 @@ def _make_submit(img_dir: str, model, calibrator: CameraCreator, save_dir: str, 
                 continue
             names, blobs = [n for n, _ in keep], [b for _, b in keep]
             x = dec.decode(blobs, frames[k & 1][:len(blobs)])
+        if sized is not None:
+            x = resize_u8(x, resize, out=sized[k & 1][:len(blobs)])
         out = pipe.submit(x, names=names)
         pending.append((names, out[1], pipe.last_done))
         drain(1)                                                                    # write batch k-1 while batch k runs
@@ -152,7 +168,8 @@ def _make_submit(img_dir: str, model, calibrator: CameraCreator, save_dir: str, 
     return {'frames': total, 'written': written, 'completeness': written / total, 'skipped': skipped}
 
 
-def main(argv=None):
+def parser():
+    from .validate import add_resize_argument
     ap = argparse.ArgumentParser(description='Camera calibration of a directory of frames (make_submit.py counterpart)')
     ap.add_argument('--img-dir', required=True)
     ap.add_argument('--model', required=True, help='argus checkpoint of the keypoint model (model_name/params/nn_state_dict)')
@@ -162,16 +179,24 @@ def main(argv=None):
     ap.add_argument('--reduce', type=int, default=1, choices=[1, 2, 4, 8],
                     help="decode the frames at 1/N of their size (libjpeg's scaled decode = cv2.IMREAD_REDUCED_COLOR_N): 2 takes "
                          '1920x1080 footage into a 960x540 network; the cameras are in the pixels of the decoded frame')
+    add_resize_argument(ap)
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--dtype', default=None, choices=['fp16x3', 'bf16x3', 'fp32', 'bf16', 'fp8'],
                     help='default: the fp32-class engine of the build (fp16x3: split-fp16 products, fp32 accumulation -- the exact engine\'s '
                          'keypoint indices on every measured frame); fp32: the reference\'s own arithmetic on the fp32 MFMA, 2.8x slower; '
                          'bf16 / fp8: throughput modes, keypoints may move by one cell on near-ties')
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    from .validate import parsed_resize
+    a = parser().parse_args(argv)
+    resize = parsed_resize(a)
     if not torch.cuda.is_available():
         raise _lib.SncalError('no GPU visible: this package has no CPU path')
     model = load_model(a.model, loss=None, optimizer=None, device=a.device, dtype=a.dtype)
-    res = make_submit(a.img_dir, model, default_calibrator(a.lines_file), a.save_dir, batch_size=a.batch_size, reduce=a.reduce)
+    res = make_submit(a.img_dir, model, default_calibrator(a.lines_file), a.save_dir, batch_size=a.batch_size, reduce=a.reduce,
+                      resize=resize)
     print(f"Completeness: {res['completeness']:.2f}")
     return res
 

@@ -19,6 +19,8 @@ The line model (line/train_config.yaml: val_loss and the monitored val_acc) is s
 
 --reduce 2 / 4 / 8 decodes the split's frames at that fraction (libjpeg's scaled decode = cv2.imread's IMREAD_REDUCED_COLOR flags, not
 cv2.resize): a 1920x1080 split scored by a 960x540 checkpoint.
+--resize W H brings every frame to W x H after the decode with cv2.resize's bilinear shrink on the device (resize.resize_u8: the
+cv2.resize of line/dataset.py:73): a 1280x720 split, or one of mixed sizes, scored by a 960x540 checkpoint.  It composes with --reduce.
 """
 import argparse
 import json
@@ -36,6 +38,7 @@ from .jpeg import JpegDecoder, check_reduce, probe, reduced_size
 from .lines import LINE_CLS
 from .metrics import AccMetric, EvalAImetric, EvalAISweep, ExtremityMetric, L2metric
 from .prediction import CameraCreator, parse_range
+from .resize import check_size, resize_u8
 
 
 class _State:
@@ -88,15 +91,100 @@ def list_split(folder: str):
     return names, annots
 
 
+MAX_SOURCE_SIZES = 4        # decoders a run with resize= keeps, one per distinct source size
+
+
+def resize_plan(height: int, width: int, reduce: int = 1, resize=None):
+    """Size bookkeeping of one height x width file (host only) -> ((h, w) it is decoded at, (H, W) of the frame yielded): decoded at
+    1 / reduce (libjpeg rounds up), then brought to resize=(W, H) -- cv2.imread(path, IMREAD_REDUCED_COLOR_n) followed by
+    cv2.resize(img, (W, H)).  resize=None: yielded as decoded."""
+    dec = reduced_size(height, width, reduce)
+    if resize is None:
+        return dec, dec
+    W, H = check_size(resize)
+    return dec, (H, W)
+
+
+def _resized_batches(folder, names, batch_size, device, decoder_threads, skipped, frame_size, reduce, resize):
+    """decoded_batches with resize=(W, H): any source size is taken, one JpegDecoder per distinct size (MAX_SOURCE_SIZES at most)."""
+    W, H = check_size(resize)
+    if frame_size is not None and tuple(frame_size) != (H, W):
+        raise _lib.SncalError(f'resize={W}x{H} where frame_size asks for frames of {frame_size[1]}x{frame_size[0]}')
+    decs = {}                                           # source (height, width) -> its decoder, in order of first appearance
+
+    def skip(name, why):
+        warnings.warn(f'{name}: skipped ({why})')
+        skipped.append(name)
+
+    try:
+        for i in range(0, len(names), batch_size):
+            groups = {}                                 # source size -> [(index into names, blob)], file order inside a group
+            for j in range(i, min(i + batch_size, len(names))):
+                try:
+                    with open(os.path.join(folder, names[j]), 'rb') as f:
+                        blob = f.read()
+                    fi = probe(blob)
+                    key = (fi['height'], fi['width'])
+                    if key not in decs:
+                        if len(decs) >= MAX_SOURCE_SIZES:
+                            raise _lib.SncalError(f"{fi['width']}x{fi['height']}: source size number {MAX_SOURCE_SIZES + 1} of a run that keeps a "
+                                                  f'decoder for {MAX_SOURCE_SIZES} (' + ', '.join(f'{w}x{h}' for h, w in decs) + ')')
+                        decs[key] = JpegDecoder(key[0], key[1], max_batch=batch_size, threads=decoder_threads, device=device, reduce=reduce)
+                except (_lib.SncalError, OSError) as e:
+                    skip(names[j], e)
+                    continue
+                groups.setdefault(key, []).append((j, blob))
+            decoded = []                                # (indices, frames at the decoded size) per size group
+            for key, files in groups.items():
+                dec = decs[key]
+                try:
+                    image = dec.decode([b for _, b in files])
+                except _lib.SncalError:                 # a stream damaged behind its headers: find it, drop it, decode the rest
+                    good = []
+                    for j, blob in files:
+                        try:
+                            dec.decode([blob])
+                            good.append((j, blob))
+                        except _lib.SncalError as e:
+                            skip(names[j], e)
+                    if not good:
+                        continue
+                    files = good
+                    image = dec.decode([b for _, b in files])
+                decoded.append(([j for j, _ in files], image))
+            keep = sorted(j for js, _ in decoded for j in js)
+            if not keep:
+                continue
+            row = {j: r for r, j in enumerate(keep)}
+            out = torch.empty((len(keep), H, W, 3), dtype=torch.uint8, device=device)
+            for js, image in decoded:
+                r0 = row[js[0]]
+                if [row[j] for j in js] == list(range(r0, r0 + len(js))):      # a run of rows: resized where it belongs
+                    resize_u8(image, (W, H), out=out[r0:r0 + len(js)])
+                else:
+                    out[torch.tensor([row[j] for j in js], device=out.device)] = resize_u8(image, (W, H))
+            yield keep, out
+    finally:
+        for dec in decs.values():
+            dec.close()
+
+
 def decoded_batches(folder: str, names: Sequence[str], batch_size: int, device, decoder_threads: int, skipped: List[str],
-                    frame_size=None, reduce: int = 1) -> Iterator[tuple]:
+                    frame_size=None, reduce: int = 1, resize=None) -> Iterator[tuple]:
     """(indices into `names`, (n,H,W,3) uint8 BGR frames on the device) per batch of the JPEG files `names` of `folder`.  A file
     the decoder cannot take, or whose size is not the run's (frame_size (H, W), or the first frame's when None), is left out of
     its batch and named in `skipped`; a batch left empty is not yielded.
     reduce=2 / 4 / 8: the files are decoded at that fraction (JpegDecoder(reduce=): libjpeg's scaled decode, cv2.imread's
-    IMREAD_REDUCED_COLOR flags).  frame_size stays the size of the frames YIELDED: a file is taken when its reduced size equals it."""
-    dec, size = None, frame_size
+    IMREAD_REDUCED_COLOR flags).  frame_size stays the size of the frames YIELDED: a file is taken when its reduced size equals it.
+    resize=(W, H): every decoded frame is brought to W x H by resize.resize_u8 (cv2.resize's INTER_LINEAR; after the reduced decode
+    when reduce is given too), so files of ANY size are taken, mixed sizes included: one decoder per distinct source size, at most
+    MAX_SOURCE_SIZES in a run -- a file of a further size is skipped and named like any other refusal.  A batch's files are decoded
+    per size group and resized into their rows of the one batch yielded, in file order.  frame_size, when given, must be (H, W)."""
     check_reduce(reduce)
+    if resize is not None:
+        yield from _resized_batches(folder, names, batch_size, device, decoder_threads, skipped, frame_size, reduce, resize)
+        return
+    dec, size = None, frame_size
 
     def skip(name, why):
         warnings.warn(f'{name}: skipped ({why})')
@@ -159,9 +247,9 @@ def _label_mode(labels: str, transform):
 
 
 def folder_batches(folder: str, batch_size: int, device, num_keypoints: int, margin: float, img_size, decoder_threads: int,
-                   skipped: List[str], transform=None, labels: str = 'host', reduce: int = 1) -> Iterator[dict]:
-    """The batch dicts of a split folder, frames decoded on the device as uint8 BGR (at 1 / reduce: see decoded_batches; the labels
-    are normalised coordinates and do not change).  A file the decoder cannot take is left out
+                   skipped: List[str], transform=None, labels: str = 'host', reduce: int = 1, resize=None) -> Iterator[dict]:
+    """The batch dicts of a split folder, frames decoded on the device as uint8 BGR (at 1 / reduce, then brought to resize=(W, H):
+    see decoded_batches; the labels are normalised coordinates and do not change).  A file the decoder cannot take is left out
     of its batch and named in `skipped`.  transform: None, or the label transform of the reference's validation loader
     (augment.test_transform(): FixLRAmbiguous), applied to each annotation before scale_points and annot_to_keypoints as
     HRNetDataset.__getitem__ does (dataset.py:60-64).  labels: see labelled_batch."""
@@ -169,7 +257,7 @@ def folder_batches(folder: str, batch_size: int, device, num_keypoints: int, mar
     transform, fix_lr = _label_mode(labels, transform)
     if transform is not None:
         annots = [transform.labels(a) for a in annots]
-    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped, reduce=reduce)
+    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped, reduce=reduce, resize=resize)
     try:
         for keep, image in frames:
             yield labelled_batch(image, [annots[j] for j in keep], [names[j] for j in keep], num_keypoints, margin, img_size,
@@ -209,7 +297,7 @@ def labelled_batch(image, annots: Sequence[dict], names: Sequence[str], num_keyp
 
 def train_batches(folder: str, batch_size: int, transform, shuffle: bool = True, seed=None, device='cuda:0', num_keypoints: int = 57,
                   margin: float = 0.0, img_size=(960, 540), decoder_threads: int = 0, skipped: List[str] = None,
-                  labels: str = 'host', reduce: int = 1) -> Iterator[dict]:
+                  labels: str = 'host', reduce: int = 1, resize=None) -> Iterator[dict]:
     """One epoch of the reference's TRAINING batches (train.py:31-33: HRNetDataset with train_transform under a shuffling loader)
     of a split folder: {'image', 'keypoints', 'mask', 'raw_annot', 'img_name'}.  Frames are decoded and augmented on the device
     (augment.train_transform: 'image' is fp32 (B,3,H,W) with ToTensor in the list, uint8 (B,H,W,3) without); the labels come from
@@ -217,13 +305,14 @@ def train_batches(folder: str, batch_size: int, transform, shuffle: bool = True,
     the transform's draws from random / numpy.random are those of a run without shuffling.  A file the decoder cannot take is
     left out of its batch and named in `skipped` (when a list is given); the last batch may be short, as the reference's is.
     labels: see labelled_batch; with 'device' the transform's FixLRAmbiguous is carried out by the label kernel (it draws nothing,
-    so the other transforms' draws are those of labels='host').  reduce: the frames are decoded at 1 / reduce (decoded_batches)
-    before the transform sees them."""
+    so the other transforms' draws are those of labels='host').  reduce, resize: the frames are decoded at 1 / reduce and
+    brought to resize=(W, H) (decoded_batches) before the transform sees them."""
     names, annots = list_split(folder)
     order = np.random.RandomState(seed).permutation(len(names)) if shuffle else np.arange(len(names))
     names, annots = [names[j] for j in order], [annots[j] for j in order]
     transform, fix_lr = _label_mode(labels, transform)
-    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped if skipped is not None else [], reduce=reduce)
+    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped if skipped is not None else [], reduce=reduce,
+                             resize=resize)
     try:
         for keep, image in frames:
             out = transform({'image': image, 'annot': [annots[j] for j in keep]})
@@ -256,14 +345,16 @@ def list_line_split(folder: str, input_size=(960, 540), annots: bool = False):
 
 
 def line_folder_batches(folder: str, batch_size: int, device, num_keypoint_pairs: int, input_size, decoder_threads: int,
-                        skipped: List[str], reduce: int = 1, annots: bool = False) -> Iterator[dict]:
+                        skipped: List[str], reduce: int = 1, annots: bool = False, resize=None) -> Iterator[dict]:
     """The line model's batch dicts {'image', 'keypoints', 'line_para', 'img_name'} of a split folder (no 'keypoint_maps': the
     loss rebuilds them); with annots=True also 'annot', the frames' annotations as they are on disk.  A frame is taken when its size
     at 1 / reduce is input_size (W, H): a 1920x1080 split goes into the 960x540 network with reduce=2.  That is libjpeg's scaled decode (cv2.imread's IMREAD_REDUCED_COLOR_2), NOT the cv2.resize of
-    line/dataset.py:73, which is not built -- a declared deviation; a frame of any other size is skipped."""
+    line/dataset.py:73 -- a declared deviation; a frame of any other size is skipped.
+    resize=input_size IS that cv2.resize (resize.resize_u8, after the decode at 1 / reduce): frames of any size are taken, mixed
+    sizes included (decoded_batches)."""
     names, labels, *raw = list_line_split(folder, input_size, annots=annots)
     frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped, frame_size=(input_size[1], input_size[0]),
-                             reduce=reduce)
+                             reduce=reduce, resize=resize)
     try:
         for keep, image in frames:
             pairs = [line_keypoints(labels[j], num_keypoint_pairs) for j in keep]
@@ -280,7 +371,8 @@ def line_folder_batches(folder: str, batch_size: int, device, num_keypoint_pairs
 
 def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreator, Sequence[CameraCreator]], batch_size: int = 16,
              loss=None, decoder_threads: int = 0, conf_threshold: float = 0.5, pckhs_thres: Sequence[float] = (2.0, 5.0, 10.0, 50.0),
-             threshold: int = 5, img_size=(960, 540), transform=None, labels: str = 'host', reduce: int = 1, sweep: Dict[str, Sequence[float]] = None):
+             threshold: int = 5, img_size=(960, 540), transform=None, labels: str = 'host', reduce: int = 1, sweep: Dict[str, Sequence[float]] = None,
+             resize=None):
     """-> {'val_loss', 'val_l2', 'val_precision', 'val_recall', 'val_pcks-2.0', ..., 'val_l2_reprojection', 'val_completeness',
     'val_eval_precision', 'val_eval_recall', 'val_eval_accuracy', 'val_evalai'} as floats (a ValidationResult).
 
@@ -299,6 +391,9 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
     reduce  folder form only.  2 / 4 / 8: the frames are decoded at that fraction of their size (libjpeg's scaled decode, what
             cv2.imread returns with IMREAD_REDUCED_COLOR_2 / _4 / _8; not cv2.resize), so that a 1920x1080 split is scored by a
             network trained at 960x540.  img_size stays the size the metrics work in; the labels are normalised and do not change
+    resize  folder form only.  (W, H): every frame is brought to that size after the decode (at 1 / reduce when given) by
+            resize.resize_u8, cv2.resize's INTER_LINEAR on the device; frames of any size are taken, mixed sizes included
+            (decoded_batches).  img_size is in the resized frame's units
     sweep   {'max_rmse': [...], 'max_rmse_rel': [...]}: the search space of optimize_valid.yaml in ONE pass.  camera then is one
             CameraCreator ('iterative_voter' or 'voter'; its own max_rmse / max_rmse_rel are not read): every batch is solved once
             and each distinct camera evaluated once (metrics.EvalAISweep), and a SweepResults comes back: one ValidationResult per
@@ -316,6 +411,8 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
         raise _lib.SncalError('labels applies to the folder form: batches handed in carry their labels already')
     if reduce != 1 and not isinstance(data, (str, os.PathLike)):
         raise _lib.SncalError('reduce applies to the folder form: batches handed in carry their frames already')
+    if resize is not None and not isinstance(data, (str, os.PathLike)):
+        raise _lib.SncalError('resize applies to the folder form: batches handed in carry their frames already')
     if sweep is not None:
         if isinstance(camera, (list, tuple)):
             raise _lib.SncalError('sweep takes ONE CameraCreator: the grid replaces the list of calibrators')
@@ -337,7 +434,7 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
         skipped: List[str] = []
         if isinstance(data, (str, os.PathLike)):
             batches = folder_batches(os.fspath(data), batch_size, model.device, nk, float(loss_fn.sigma), img_size, decoder_threads, skipped,
-                                     transform=transform, labels=labels, reduce=reduce)
+                                     transform=transform, labels=labels, reduce=reduce, resize=resize)
         loss_sum = torch.zeros((), dtype=torch.float64, device=model.device)
         frames = 0
         for batch in (batches if batches is not None else data):
@@ -379,7 +476,7 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
 
 
 def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, loss=None, conf_threshold: float = 0.2,
-                  decoder_threads: int = 0, input_size=(960, 540), reduce: int = 1, extremities: Sequence[float] = None):
+                  decoder_threads: int = 0, input_size=(960, 540), reduce: int = 1, extremities: Sequence[float] = None, resize=None):
     """Score a line-model checkpoint (EHMMetaModel) -> {'val_loss', 'val_acc'} as floats (a ValidationResult): the two numbers
     line/train_config.yaml logs and monitors.
 
@@ -390,6 +487,8 @@ def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, 
     reduce  folder form only.  A 1920x1080 split is taken with reduce=2: libjpeg's scaled decode (cv2.imread with
             IMREAD_REDUCED_COLOR_2), which is NOT the cv2.resize of line/dataset.py:73 -- a declared deviation.
             The labels are normalised coordinates and do not change; a frame whose reduced size is not input_size is skipped
+    resize  folder form only.  input_size again, as (W, H): every frame is brought to it after the decode (at 1 / reduce when given)
+            by resize.resize_u8 -- the cv2.resize of line/dataset.py:73 -- so frames of any size are scored, mixed sizes included
     extremities  None (default): the two keys above, nothing else runs.  A tuple of pixel thresholds, e.g. (5, 10, 20): the
             dev-kit's extremity metric (baseline/evaluate_extremities.py; metrics.ExtremityMetric, one more launch per batch) on the
             decoded peaks with p >= conf_threshold, against each frame's RAW annotation scaled to input_size: the keys
@@ -404,6 +503,8 @@ def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, 
     left out and named in .skipped.  The host waits for the GPU once, at the end."""
     if reduce != 1 and not isinstance(data, (str, os.PathLike)):
         raise _lib.SncalError('reduce applies to the folder form: batches handed in carry their frames already')
+    if resize is not None and not isinstance(data, (str, os.PathLike)):
+        raise _lib.SncalError('resize applies to the folder form: batches handed in carry their frames already')
     own_loss = model.loss
     if loss is not None:
         model.loss = loss                      # for this call only: restored below
@@ -416,7 +517,7 @@ def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, 
         skipped: List[str] = []
         if isinstance(data, (str, os.PathLike)):
             batches = line_folder_batches(os.fspath(data), batch_size, model.device, acc.num_keypoints, input_size, decoder_threads, skipped,
-                                          reduce=reduce, annots=ext is not None)
+                                          reduce=reduce, annots=ext is not None, resize=resize)
         loss_sum = torch.zeros((), dtype=torch.float64, device=model.device)
         frames = 0
         for batch in (batches if batches is not None else data):
@@ -450,9 +551,19 @@ def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, 
     return res
 
 
-def main(argv=None):
-    from .metamodel import load_model
-    from .submit import default_calibrator
+def add_resize_argument(ap):
+    """--resize W H, shared by the validate, submit and baseline_cameras command lines; parsed_resize() reads it back."""
+    ap.add_argument('--resize', type=int, nargs=2, default=None, metavar=('W', 'H'),
+                    help="bring every frame to W x H after the decode (cv2.resize's bilinear shrink, on the device): frames of any "
+                         'size, mixed sizes included, e.g. --resize 960 540 for a 1280x720 folder; composes with --reduce')
+
+
+def parsed_resize(a):
+    """The resize= keyword of a parsed command line: None, or (W, H)."""
+    return None if a.resize is None else check_size(tuple(a.resize), '--resize')
+
+
+def parser():
     ap = argparse.ArgumentParser(description='Validate a keypoint checkpoint on a SoccerNet split (validate.py counterpart)')
     ap.add_argument('--line', action='store_true', help='the checkpoint is the line model (EHMMetaModel): val_loss and val_acc')
     ap.add_argument('--data', required=True, help='split folder: NNNNN.jpg + NNNNN.json')
@@ -461,6 +572,7 @@ def main(argv=None):
     ap.add_argument('--batch-size', type=int, default=None, help='default 16, with --line 8')
     ap.add_argument('--reduce', type=int, default=1, choices=[1, 2, 4, 8],
                     help="decode the frames at 1/N of their size (libjpeg's scaled decode = cv2.IMREAD_REDUCED_COLOR_N)")
+    add_resize_argument(ap)
     ap.add_argument('--sweep-max-rmse', default=None, metavar='START:STOP:STEP',
                     help="sweep camera.max_rmse over Hydra's range(start, stop, step), stop excluded (optimize_valid.yaml: 10:70:4); one solve per batch")
     ap.add_argument('--sweep-max-rmse-rel', default=None, metavar='START:STOP:STEP', help='the same for camera.max_rmse_rel (optimize_valid.yaml: 4:16:2)')
@@ -468,7 +580,15 @@ def main(argv=None):
                     help="with --line: also the dev-kit's extremity metric at these pixel thresholds, e.g. 5,10,20")
     ap.add_argument('--device', default='cuda:0')
     ap.add_argument('--dtype', default=None, choices=['fp16x3', 'bf16x3', 'fp32', 'bf16', 'fp8'])
+    return ap
+
+
+def main(argv=None):
+    from .metamodel import load_model
+    from .submit import default_calibrator
+    ap = parser()
     a = ap.parse_args(argv)
+    resize = parsed_resize(a)
     sweep = None
     if a.sweep_max_rmse is not None or a.sweep_max_rmse_rel is not None:
         if a.line:
@@ -485,9 +605,10 @@ def main(argv=None):
         raise _lib.SncalError('no GPU visible: this package has no CPU path')
     model = load_model(a.model, device=a.device, dtype=a.dtype)
     if a.line:
-        res = validate_line(model, a.data, batch_size=a.batch_size or 8, reduce=a.reduce, extremities=ext)
+        res = validate_line(model, a.data, batch_size=a.batch_size or 8, reduce=a.reduce, extremities=ext, resize=resize)
     else:
-        res = validate(model, a.data, default_calibrator(a.lines_file), batch_size=a.batch_size or 16, reduce=a.reduce, sweep=sweep)
+        res = validate(model, a.data, default_calibrator(a.lines_file), batch_size=a.batch_size or 16, reduce=a.reduce, sweep=sweep,
+                       resize=resize)
     if sweep is not None:
         print(f"{'max_rmse':>10} {'max_rmse_rel':>12} {'completeness':>12} {'accuracy':>10} {'evalai':>10}")
         for r in res:
