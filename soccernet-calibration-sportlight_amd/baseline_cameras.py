@@ -32,8 +32,10 @@ from . import _lib
 from .annotations import ANNOT_CLASSES, pack_annotations
 from .camera import Camera
 from .evaluate import LINE_EXTREMITIES
+from .frames import decoded_batches
 from .lines import LINE_CLS
 from .pitch import PITCH_POINTS, PITCH_POINTS_TO_INTERSECTON
+from .resize import add_resize_argument, parsed_resize
 
 IGNORED = 'Circle central'
 STATUS_NONE, STATUS_HOMOGRAPHY, STATUS_REFINED = 0, 1, 2       # SNCAL_LINECAM_*
@@ -266,9 +268,8 @@ def line_model_cameras(img_dir: str, model, save_dir: str, batch_size: int = 64,
     peaks where they lie (no host round trip between the decode and the cameras) -> camera_<id>.json in save_dir -> files written.
     collect: a list that receives (names, peaks, records, status) per batch, on the device.
     resize=(W, H): every frame is brought to W x H after the decode (resize.resize_u8: the cv2.resize of baseline/dataloader.py:62 and
-    detect_extremities.py:237), frames of any size, mixed sizes included (validate.decoded_batches); the cameras are in its pixels."""
+    detect_extremities.py:237), frames of any size, mixed sizes included (frames.decoded_batches); the cameras are in its pixels."""
     from .interop import save_cameras
-    from .validate import decoded_batches
     names = sorted(f for f in os.listdir(img_dir) if f.endswith('.jpg'))
     skipped: List[str] = []
     frames = decoded_batches(img_dir, names, batch_size, model.device, decoder_threads, skipped, reduce=reduce, resize=resize)
@@ -288,7 +289,6 @@ def line_model_cameras(img_dir: str, model, save_dir: str, batch_size: int = 64,
 
 
 def parser():
-    from .validate import add_resize_argument
     ap = argparse.ArgumentParser(description='Baseline for camera parameters extraction (baseline_cameras.py counterpart)')
     ap.add_argument('-s', '--soccernet', default='./annotations', type=str, help='Path to the SoccerNet-V3 dataset folder')
     ap.add_argument('-p', '--prediction', default='./results_bis', required=False, type=str, help='Path to the prediction folder')
@@ -304,7 +304,6 @@ def parser():
 
 
 def main(argv=None):
-    from .validate import parsed_resize
     ap = parser()
     a = ap.parse_args(argv)
     resize = parsed_resize(a)

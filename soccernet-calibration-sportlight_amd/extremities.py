@@ -25,6 +25,7 @@ from . import _lib
 from .annotations import ANNOT_CLASSES, pack_annotations
 from .augment import mirror_labels
 from .evaluate import scale_points  # noqa: F401  (the scorer's other half: re-exported beside evaluate_detection_prediction)
+from .frames import decoded_batches
 from .lines import LINE_CLS
 
 IGNORED = 'Circle central'
@@ -272,7 +273,6 @@ def export_extremities(img_dir: str, model, save_dir: str, batch_size: int = 64,
     schema -> files written.  The points are the kept peaks (p >= conf_threshold) as pixels divided by (W - 1, H - 1), so that the
     scorer's scale_points gives the pixels back; the dev-kit's own detector divides by (W, H) (detect_extremities.py:116-117) -- a
     declared choice.  A frame the decoder refuses gets no file: the scorer counts it as missing."""
-    from .validate import decoded_batches
     names = sorted(f for f in os.listdir(img_dir) if f.endswith('.jpg'))
     os.makedirs(save_dir, exist_ok=True)
     skipped: List[str] = []

@@ -30,6 +30,18 @@ def check_size(size, name='resize'):
     return W, H
 
 
+def add_resize_argument(ap):
+    """--resize W H, shared by the validate, submit and baseline_cameras command lines; parsed_resize() reads it back."""
+    ap.add_argument('--resize', type=int, nargs=2, default=None, metavar=('W', 'H'),
+                    help="bring every frame to W x H after the decode (cv2.resize's bilinear shrink, on the device): frames of any "
+                         'size, mixed sizes included, e.g. --resize 960 540 for a 1280x720 folder; composes with --reduce')
+
+
+def parsed_resize(a):
+    """The resize= keyword of a parsed command line: None, or (W, H)."""
+    return None if a.resize is None else check_size(tuple(a.resize), '--resize')
+
+
 def tables(n_src: int, n_dst: int, zero_edges: bool):
     """The taps of one axis (host only, no GPU) -> (ofs (n_dst,) int32, coef (n_dst, 2) int16): the first source index and the two
     weights (of 2048) of every destination index.  zero_edges=True is the x axis rule (an index past either edge is pinned to it

@@ -15,7 +15,6 @@ scaled decode, so that 1920x1080 footage reaches a network trained at 960x540 at
 (resize.resize_u8): 1280x720 footage, or any other size, into that network.  It composes with --reduce.
 """
 import argparse
-import warnings
 import os
 from typing import List, Optional
 
@@ -24,13 +23,14 @@ os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')      # see pipeline.py: streams 
 import torch  # noqa: E402
 
 from . import _lib
+from .frames import decode_dropping, read_probed, skipper
 from .interop import save_cameras
-from .jpeg import JpegDecoder, check_reduce, probe
+from .jpeg import JpegDecoder, check_reduce
 from .metamodel import load_model
 from .pipeline import CalibrationPipeline
 from .pitch import PITCH_POINTS
 from .prediction import CameraCreator, camera_from_record
-from .resize import check_size, resize_u8
+from .resize import add_resize_argument, check_size, parsed_resize, resize_u8
 
 
 def default_calibrator(lines_file: Optional[str] = None) -> CameraCreator:
@@ -47,8 +47,7 @@ def run_frame_size(img_dir: str, img_names: List[str], sample: int = 32):
     sizes = {}
     for n in img_names[:sample]:
         try:
-            with open(os.path.join(img_dir, n), 'rb') as f:
-                info = probe(f.read())
+            info = read_probed(img_dir, n)[1]
         except (_lib.SncalError, OSError):
             continue
         key = (info['height'], info['width'])
@@ -109,6 +108,7 @@ def _make_submit(img_dir: str, model, calibrator: CameraCreator, save_dir: str, 
     pending = []                                                                    # (names, records, event)
     written = 0
     skipped = []                                                                    # frames the device decoder cannot take
+    skip = skipper(skipped)
 
     def drain(keep: int):
         nonlocal written
@@ -119,42 +119,27 @@ def _make_submit(img_dir: str, model, calibrator: CameraCreator, save_dir: str, 
             written += save_cameras(cams, names, save_dir)
 
     for k, i in enumerate(range(0, total, batch_size)):
-        names, blobs = [], []
+        files = []
         for n in img_names[i:i + batch_size]:
-            with open(os.path.join(img_dir, n), 'rb') as f:
-                blob = f.read()
             # a file the device decoder does not handle (progressive, arithmetic-coded, CMYK, another size than the first frame's, damaged)
             # is skipped with a warning and simply gets no camera file -- what the reference's loop does for a frame without a
             # camera -- instead of ending the run (cv2.imread would decode some of these: decode them elsewhere and upload uint8 frames)
-            try:
-                fi = probe(blob)
+            try:                                    # SncalError only: a file that cannot be read (OSError) ends the run
+                blob, fi = read_probed(img_dir, n)
                 if (fi['height'], fi['width']) != (H, W):
                     raise _lib.SncalError(f"{fi['width']}x{fi['height']} where the run's frames are {W}x{H}")
             except _lib.SncalError as e:
-                warnings.warn(f'{n}: skipped ({e})')
-                skipped.append(n)
+                skip(n, e)
                 continue
-            names.append(n)
-            blobs.append(blob)
-        if not blobs:
+            files.append((n, blob))
+        if not files:
             continue
-        try:
-            x = dec.decode(blobs, frames[k & 1][:len(blobs)])
-        except _lib.SncalError:                     # a stream that is damaged behind its headers: find it, drop it, decode the rest
-            keep = []
-            for n, blob in zip(names, blobs):
-                try:
-                    dec.decode([blob], frames[k & 1][:1])
-                    keep.append((n, blob))
-                except _lib.SncalError as e:
-                    warnings.warn(f'{n}: skipped ({e})')
-                    skipped.append(n)
-            if not keep:
-                continue
-            names, blobs = [n for n, _ in keep], [b for _, b in keep]
-            x = dec.decode(blobs, frames[k & 1][:len(blobs)])
+        kept, x = decode_dropping(dec, files, skip, out=frames[k & 1])
+        if not kept:
+            continue
+        names = [files[p][0] for p in kept]
         if sized is not None:
-            x = resize_u8(x, resize, out=sized[k & 1][:len(blobs)])
+            x = resize_u8(x, resize, out=sized[k & 1][:len(names)])
         out = pipe.submit(x, names=names)
         pending.append((names, out[1], pipe.last_done))
         drain(1)                                                                    # write batch k-1 while batch k runs
@@ -169,7 +154,6 @@ def _make_submit(img_dir: str, model, calibrator: CameraCreator, save_dir: str, 
 
 
 def parser():
-    from .validate import add_resize_argument
     ap = argparse.ArgumentParser(description='Camera calibration of a directory of frames (make_submit.py counterpart)')
     ap.add_argument('--img-dir', required=True)
     ap.add_argument('--model', required=True, help='argus checkpoint of the keypoint model (model_name/params/nn_state_dict)')
@@ -189,7 +173,6 @@ def parser():
 
 
 def main(argv=None):
-    from .validate import parsed_resize
     a = parser().parse_args(argv)
     resize = parsed_resize(a)
     if not torch.cuda.is_available():

@@ -23,22 +23,20 @@ cv2.resize): a 1920x1080 split scored by a 960x540 checkpoint.
 cv2.resize of line/dataset.py:73): a 1280x720 split, or one of mixed sizes, scored by a 960x540 checkpoint.  It composes with --reduce.
 """
 import argparse
-import json
+import contextlib
 import os
-import warnings
-from typing import Dict, Iterable, Iterator, List, Sequence, Union
+from typing import Callable, Dict, Iterable, List, Sequence, Union
 
-import numpy as np
 import torch
 
 from . import _lib
-from .annotations import get_extreme_points, get_intersections, keypoint_labels_device, line_keypoints, sort_anno
-from .evaluate import scale_points
-from .jpeg import JpegDecoder, check_reduce, probe, reduced_size
+from .frames import (MAX_SOURCE_SIZES, _label_mode, annot_to_keypoints, decoded_batches, folder_batches,  # noqa: F401
+                     labelled_batch, line_folder_batches, list_line_split, list_split, resize_plan,
+                     train_batches)  # the loaders lived here until frames.py
 from .lines import LINE_CLS
 from .metrics import AccMetric, EvalAImetric, EvalAISweep, ExtremityMetric, L2metric
 from .prediction import CameraCreator, parse_range
-from .resize import check_size, resize_u8
+from .resize import add_resize_argument, parsed_resize
 
 
 class _State:
@@ -60,313 +58,50 @@ class SweepResults(list):
     best = 0
 
 
-def annot_to_keypoints(annot: dict, num_keypoints: int = 57, margin: float = 0.0):
-    """HRNetDataset._annot2keypoints (dataset.py:73-87): SoccerNet annotation {class: [{'x', 'y'}, ...]} (normalised) ->
-    (keypoints (3*num_keypoints,) float32 [x, y, 1] or [-1, -1, 0], mask (num_keypoints + 1,) int64)."""
-    points = {cls: [(p['x'], p['y']) for p in pts] for cls, pts in annot.items()}           # reader.decode_annot
-    kpts, missing = get_intersections(points, margin=margin)
-    keypoints = np.ones(num_keypoints * 3, dtype=np.float32) * -1
-    for i in range(num_keypoints):
-        if kpts[i] is not None:
-            keypoints[i * 3], keypoints[i * 3 + 1], keypoints[i * 3 + 2] = kpts[i][0], kpts[i][1], 1
-        else:
-            keypoints[i * 3 + 2] = 0
-    mask = np.ones(num_keypoints + 1, dtype=np.int64)
-    for i in missing:
-        mask[i] = 0
-    return keypoints, mask
+FOLDER_ONLY = {'transform': (None, 'labels'), 'labels': ('host', 'labels'), 'reduce': (1, 'frames'), 'resize': (None, 'frames')}
 
 
-def list_split(folder: str):
-    """dataset.py:41-50: (image names, annotation dicts) of a SoccerNet split folder, sorted; names containing 'info' skipped."""
-    names, annots = [], []
-    for fname in sorted(os.listdir(folder)):
-        if 'info' in fname or not fname.endswith('.json'):
-            continue
-        img = fname.replace('.json', '.jpg')
-        if os.path.exists(os.path.join(folder, img)):
-            with open(os.path.join(folder, fname), 'r') as f:
-                annots.append(json.load(f))
-            names.append(img)
-    return names, annots
+def _refuse_folder_keywords(data, **given):
+    """The keywords of the folder form (FOLDER_ONLY: name -> (default, what a batch carries already)) are refused, in the order given,
+    when one that is not at its default comes with batches handed in."""
+    for name, value in given.items():
+        default, carried = FOLDER_ONLY[name]
+        if value != default and not isinstance(data, (str, os.PathLike)):
+            raise _lib.SncalError(f'{name} applies to the folder form: batches handed in carry their {carried} already')
 
 
-MAX_SOURCE_SIZES = 4        # decoders a run with resize= keeps, one per distinct source size
-
-
-def resize_plan(height: int, width: int, reduce: int = 1, resize=None):
-    """Size bookkeeping of one height x width file (host only) -> ((h, w) it is decoded at, (H, W) of the frame yielded): decoded at
-    1 / reduce (libjpeg rounds up), then brought to resize=(W, H) -- cv2.imread(path, IMREAD_REDUCED_COLOR_n) followed by
-    cv2.resize(img, (W, H)).  resize=None: yielded as decoded."""
-    dec = reduced_size(height, width, reduce)
-    if resize is None:
-        return dec, dec
-    W, H = check_size(resize)
-    return dec, (H, W)
-
-
-def _resized_batches(folder, names, batch_size, device, decoder_threads, skipped, frame_size, reduce, resize):
-    """decoded_batches with resize=(W, H): any source size is taken, one JpegDecoder per distinct size (MAX_SOURCE_SIZES at most)."""
-    W, H = check_size(resize)
-    if frame_size is not None and tuple(frame_size) != (H, W):
-        raise _lib.SncalError(f'resize={W}x{H} where frame_size asks for frames of {frame_size[1]}x{frame_size[0]}')
-    decs = {}                                           # source (height, width) -> its decoder, in order of first appearance
-
-    def skip(name, why):
-        warnings.warn(f'{name}: skipped ({why})')
-        skipped.append(name)
-
+@contextlib.contextmanager
+def _lent_loss(model, loss):
+    """model.loss is `loss` for the block only (None: the model's own stays, built by the first val_step if need be)."""
+    own_loss = model.loss
+    if loss is not None:
+        model.loss = loss
     try:
-        for i in range(0, len(names), batch_size):
-            groups = {}                                 # source size -> [(index into names, blob)], file order inside a group
-            for j in range(i, min(i + batch_size, len(names))):
-                try:
-                    with open(os.path.join(folder, names[j]), 'rb') as f:
-                        blob = f.read()
-                    fi = probe(blob)
-                    key = (fi['height'], fi['width'])
-                    if key not in decs:
-                        if len(decs) >= MAX_SOURCE_SIZES:
-                            raise _lib.SncalError(f"{fi['width']}x{fi['height']}: source size number {MAX_SOURCE_SIZES + 1} of a run that keeps a "
-                                                  f'decoder for {MAX_SOURCE_SIZES} (' + ', '.join(f'{w}x{h}' for h, w in decs) + ')')
-                        decs[key] = JpegDecoder(key[0], key[1], max_batch=batch_size, threads=decoder_threads, device=device, reduce=reduce)
-                except (_lib.SncalError, OSError) as e:
-                    skip(names[j], e)
-                    continue
-                groups.setdefault(key, []).append((j, blob))
-            decoded = []                                # (indices, frames at the decoded size) per size group
-            for key, files in groups.items():
-                dec = decs[key]
-                try:
-                    image = dec.decode([b for _, b in files])
-                except _lib.SncalError:                 # a stream damaged behind its headers: find it, drop it, decode the rest
-                    good = []
-                    for j, blob in files:
-                        try:
-                            dec.decode([blob])
-                            good.append((j, blob))
-                        except _lib.SncalError as e:
-                            skip(names[j], e)
-                    if not good:
-                        continue
-                    files = good
-                    image = dec.decode([b for _, b in files])
-                decoded.append(([j for j, _ in files], image))
-            keep = sorted(j for js, _ in decoded for j in js)
-            if not keep:
-                continue
-            row = {j: r for r, j in enumerate(keep)}
-            out = torch.empty((len(keep), H, W, 3), dtype=torch.uint8, device=device)
-            for js, image in decoded:
-                r0 = row[js[0]]
-                if [row[j] for j in js] == list(range(r0, r0 + len(js))):      # a run of rows: resized where it belongs
-                    resize_u8(image, (W, H), out=out[r0:r0 + len(js)])
-                else:
-                    out[torch.tensor([row[j] for j in js], device=out.device)] = resize_u8(image, (W, H))
-            yield keep, out
+        yield
     finally:
-        for dec in decs.values():
-            dec.close()
+        if loss is not None:
+            model.loss = own_loss
 
 
-def decoded_batches(folder: str, names: Sequence[str], batch_size: int, device, decoder_threads: int, skipped: List[str],
-                    frame_size=None, reduce: int = 1, resize=None) -> Iterator[tuple]:
-    """(indices into `names`, (n,H,W,3) uint8 BGR frames on the device) per batch of the JPEG files `names` of `folder`.  A file
-    the decoder cannot take, or whose size is not the run's (frame_size (H, W), or the first frame's when None), is left out of
-    its batch and named in `skipped`; a batch left empty is not yielded.
-    reduce=2 / 4 / 8: the files are decoded at that fraction (JpegDecoder(reduce=): libjpeg's scaled decode, cv2.imread's
-    IMREAD_REDUCED_COLOR flags).  frame_size stays the size of the frames YIELDED: a file is taken when its reduced size equals it.
-    resize=(W, H): every decoded frame is brought to W x H by resize.resize_u8 (cv2.resize's INTER_LINEAR; after the reduced decode
-    when reduce is given too), so files of ANY size are taken, mixed sizes included: one decoder per distinct source size, at most
-    MAX_SOURCE_SIZES in a run -- a file of a further size is skipped and named like any other refusal.  A batch's files are decoded
-    per size group and resized into their rows of the one batch yielded, in file order.  frame_size, when given, must be (H, W)."""
-    check_reduce(reduce)
-    if resize is not None:
-        yield from _resized_batches(folder, names, batch_size, device, decoder_threads, skipped, frame_size, reduce, resize)
-        return
-    dec, size = None, frame_size
-
-    def skip(name, why):
-        warnings.warn(f'{name}: skipped ({why})')
-        skipped.append(name)
-
+def _epoch(model, data, open_folder: Callable, step: Callable):
+    """One pass over data -- open_folder(path)'s batch dicts when it is a folder, else the iterable as it is: model.val_step per
+    batch, then step(batch, out) for the metrics -> (val_loss, frames): the mean of the step losses weighted by step size (nan
+    without a frame) and the frames that went through the network.  The host waits for the GPU once, at the end."""
+    batches = open_folder(os.fspath(data)) if isinstance(data, (str, os.PathLike)) else None
+    loss_sum = torch.zeros((), dtype=torch.float64, device=model.device)
+    frames = 0
     try:
-        for i in range(0, len(names), batch_size):
-            keep, blobs = [], []
-            for j in range(i, min(i + batch_size, len(names))):
-                try:
-                    with open(os.path.join(folder, names[j]), 'rb') as f:
-                        blob = f.read()
-                    fi = probe(blob)
-                    got = reduced_size(fi['height'], fi['width'], reduce)
-                    if size is None:
-                        size = got
-                    if got != tuple(size):
-                        raise _lib.SncalError(f"{fi['width']}x{fi['height']}" + (f' (1/{reduce}: {got[1]}x{got[0]})' if reduce != 1 else '') +
-                                              f" where the run's frames are {size[1]}x{size[0]}")
-                    if dec is not None and (fi['height'], fi['width']) != (dec.height, dec.width):      # sizes that round up to the same frame
-                        raise _lib.SncalError(f"{fi['width']}x{fi['height']} where the run's source frames are {dec.width}x{dec.height}")
-                    if dec is None:         # the decoder is built for the SOURCE size of the first frame taken
-                        dec = JpegDecoder(fi['height'], fi['width'], max_batch=batch_size, threads=decoder_threads, device=device, reduce=reduce)
-                except (_lib.SncalError, OSError) as e:
-                    skip(names[j], e)
-                    continue
-                keep.append(j)
-                blobs.append(blob)
-            if not keep:
-                continue
-            try:
-                image = dec.decode(blobs)
-            except _lib.SncalError:                         # a stream damaged behind its headers: find it, drop it, decode the rest
-                good = []
-                for j, blob in zip(keep, blobs):
-                    try:
-                        dec.decode([blob])
-                        good.append((j, blob))
-                    except _lib.SncalError as e:
-                        skip(names[j], e)
-                if not good:
-                    continue
-                keep, blobs = [j for j, _ in good], [b for _, b in good]
-                image = dec.decode(blobs)
-            yield keep, image
-    finally:                                            # also when the consumer stops early or raises: generator.close() lands here
-        if dec is not None:
-            dec.close()
-
-
-def _label_mode(labels: str, transform):
-    """labels='host' | 'device' -> (the transform to run on the host, whether the label kernel takes FixLRAmbiguous' decision)."""
-    if labels not in ('host', 'device'):
-        raise _lib.SncalError(f"labels={labels!r}: 'host' or 'device'")
-    if labels == 'host' or transform is None:
-        return transform, False
-    if not hasattr(transform, 'deferring_fix_lr'):
-        raise _lib.SncalError("labels='device' takes an augment.ComposeTransform (its FixLRAmbiguous moves into the label kernel)")
-    return transform.deferring_fix_lr()
-
-
-def folder_batches(folder: str, batch_size: int, device, num_keypoints: int, margin: float, img_size, decoder_threads: int,
-                   skipped: List[str], transform=None, labels: str = 'host', reduce: int = 1, resize=None) -> Iterator[dict]:
-    """The batch dicts of a split folder, frames decoded on the device as uint8 BGR (at 1 / reduce, then brought to resize=(W, H):
-    see decoded_batches; the labels are normalised coordinates and do not change).  A file the decoder cannot take is left out
-    of its batch and named in `skipped`.  transform: None, or the label transform of the reference's validation loader
-    (augment.test_transform(): FixLRAmbiguous), applied to each annotation before scale_points and annot_to_keypoints as
-    HRNetDataset.__getitem__ does (dataset.py:60-64).  labels: see labelled_batch."""
-    names, annots = list_split(folder)
-    transform, fix_lr = _label_mode(labels, transform)
-    if transform is not None:
-        annots = [transform.labels(a) for a in annots]
-    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped, reduce=reduce, resize=resize)
-    try:
-        for keep, image in frames:
-            yield labelled_batch(image, [annots[j] for j in keep], [names[j] for j in keep], num_keypoints, margin, img_size,
-                                 labels=labels, fix_lr=fix_lr)
+        for batch in (batches if batches is not None else data):
+            out = model.val_step(batch)
+            B = out['prediction'].shape[0]
+            frames += B
+            loss_sum = loss_sum + out['loss'].to(torch.float64) * B
+            step(batch, out)
+        model.check_range()
     finally:
-        frames.close()
-
-
-def labelled_batch(image, annots: Sequence[dict], names: Sequence[str], num_keypoints: int, margin: float, img_size,
-                   labels: str = 'host', fix_lr: bool = False) -> dict:
-    """The reference's batch dict (dataset.py:52-71 + custom_collate) from frames and their (already transformed) annotations.
-    labels='host': annot_to_keypoints per frame, 'keypoints' and 'mask' on the host.  labels='device': one launch of the label kernel
-    for the batch (annotations.keypoint_labels_device), 'keypoints' and 'mask' on the image's device; with fix_lr the kernel also
-    takes FixLRAmbiguous' decision -- the annotations then come in WITHOUT that transform applied (ComposeTransform.deferring_fix_lr)
-    -- and the host renames the swapped frames' annotations for 'raw_annot' from one copy of B bytes."""
-    if labels == 'host':
-        if fix_lr:
-            raise _lib.SncalError("fix_lr is the label kernel's: with labels='host' FixLRAmbiguous runs in the transform")
-        pairs = [annot_to_keypoints(a, num_keypoints, margin) for a in annots]
-        keypoints = torch.from_numpy(np.stack([p[0] for p in pairs]))
-        mask = torch.from_numpy(np.stack([p[1] for p in pairs]))
-    elif labels == 'device':
-        keypoints, mask, swapped = keypoint_labels_device(annots, margin=margin, num_keypoints=num_keypoints, fix_lr=fix_lr,
-                                                          device=image.device)
-        if fix_lr:
-            from .augment import flip_annot_names
-            annots = [flip_annot_names(a, swap_top_bottom=False, swap_posts=False) if s else a
-                      for a, s in zip(annots, swapped.cpu().tolist())]
-    else:
-        raise _lib.SncalError(f"labels={labels!r}: 'host' or 'device'")
-    return {'image': image,
-            'keypoints': keypoints,
-            'mask': mask,
-            'raw_annot': [scale_points(a, img_size[0], img_size[1]) for a in annots],
-            'img_name': list(names)}
-
-
-def train_batches(folder: str, batch_size: int, transform, shuffle: bool = True, seed=None, device='cuda:0', num_keypoints: int = 57,
-                  margin: float = 0.0, img_size=(960, 540), decoder_threads: int = 0, skipped: List[str] = None,
-                  labels: str = 'host', reduce: int = 1, resize=None) -> Iterator[dict]:
-    """One epoch of the reference's TRAINING batches (train.py:31-33: HRNetDataset with train_transform under a shuffling loader)
-    of a split folder: {'image', 'keypoints', 'mask', 'raw_annot', 'img_name'}.  Frames are decoded and augmented on the device
-    (augment.train_transform: 'image' is fp32 (B,3,H,W) with ToTensor in the list, uint8 (B,H,W,3) without); the labels come from
-    the transformed annotations.  shuffle draws the epoch's order from numpy.random.RandomState(seed) -- a generator of its own, so
-    the transform's draws from random / numpy.random are those of a run without shuffling.  A file the decoder cannot take is
-    left out of its batch and named in `skipped` (when a list is given); the last batch may be short, as the reference's is.
-    labels: see labelled_batch; with 'device' the transform's FixLRAmbiguous is carried out by the label kernel (it draws nothing,
-    so the other transforms' draws are those of labels='host').  reduce, resize: the frames are decoded at 1 / reduce and
-    brought to resize=(W, H) (decoded_batches) before the transform sees them."""
-    names, annots = list_split(folder)
-    order = np.random.RandomState(seed).permutation(len(names)) if shuffle else np.arange(len(names))
-    names, annots = [names[j] for j in order], [annots[j] for j in order]
-    transform, fix_lr = _label_mode(labels, transform)
-    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped if skipped is not None else [], reduce=reduce,
-                             resize=resize)
-    try:
-        for keep, image in frames:
-            out = transform({'image': image, 'annot': [annots[j] for j in keep]})
-            yield labelled_batch(out['image'], out['annot'], [names[j] for j in keep], num_keypoints, margin, img_size,
-                                 labels=labels, fix_lr=fix_lr)
-    finally:
-        frames.close()
-
-
-def list_line_split(folder: str, input_size=(960, 540), annots: bool = False):
-    """EHMDataset.__init__ (line/dataset.py:54-67): (image names, labels) of the frames whose annotation sort_anno finds usable;
-    labels are get_extreme_points' dicts.  Sorted by name (the reference takes os.listdir's order).  annots=True: a third list, the
-    kept frames' annotations as they are on disk ({class: [{'x', 'y'}, ...]}, what the extremity metric scores against)."""
-    names, labels, raw = [], [], []
-    for fname in sorted(os.listdir(folder)):
-        if 'info' in fname or not fname.endswith('.json'):
-            continue
-        img = fname.replace('.json', '.jpg')
-        if not os.path.exists(os.path.join(folder, img)):
-            continue
-        with open(os.path.join(folder, fname), 'r') as f:
-            annot = json.load(f)
-        points = {cls: [(p['x'], p['y']) for p in pts] for cls, pts in annot.items()}           # reader.decode_annot
-        res, usable = sort_anno(points, img_size=input_size)
-        if usable:
-            names.append(img)
-            labels.append(get_extreme_points(res, img_size=input_size))
-            raw.append(annot)
-    return (names, labels, raw) if annots else (names, labels)
-
-
-def line_folder_batches(folder: str, batch_size: int, device, num_keypoint_pairs: int, input_size, decoder_threads: int,
-                        skipped: List[str], reduce: int = 1, annots: bool = False, resize=None) -> Iterator[dict]:
-    """The line model's batch dicts {'image', 'keypoints', 'line_para', 'img_name'} of a split folder (no 'keypoint_maps': the
-    loss rebuilds them); with annots=True also 'annot', the frames' annotations as they are on disk.  A frame is taken when its size
-    at 1 / reduce is input_size (W, H): a 1920x1080 split goes into the 960x540 network with reduce=2.  That is libjpeg's scaled decode (cv2.imread's IMREAD_REDUCED_COLOR_2), NOT the cv2.resize of
-    line/dataset.py:73 -- a declared deviation; a frame of any other size is skipped.
-    resize=input_size IS that cv2.resize (resize.resize_u8, after the decode at 1 / reduce): frames of any size are taken, mixed
-    sizes included (decoded_batches)."""
-    names, labels, *raw = list_line_split(folder, input_size, annots=annots)
-    frames = decoded_batches(folder, names, batch_size, device, decoder_threads, skipped, frame_size=(input_size[1], input_size[0]),
-                             reduce=reduce, resize=resize)
-    try:
-        for keep, image in frames:
-            pairs = [line_keypoints(labels[j], num_keypoint_pairs) for j in keep]
-            batch = {'image': image,
-                     'keypoints': torch.from_numpy(np.stack([p[0] for p in pairs])),
-                     'line_para': torch.tensor([p[1] for p in pairs], dtype=torch.float64),
-                     'img_name': [names[j] for j in keep]}
-            if annots:
-                batch['annot'] = [raw[0][j] for j in keep]
-            yield batch
-    finally:
-        frames.close()
+        if batches is not None:
+            batches.close()                    # ends the generator: its finally closes the decoders, also after an exception mid-epoch
+    return (float(loss_sum.item()) / frames if frames else float('nan')), frames
 
 
 def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreator, Sequence[CameraCreator]], batch_size: int = 16,
@@ -405,25 +140,15 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
     it is computed by pytorch-argus' Loss metric there, whose source is not part of the reference tree.
     A frame the decoder refuses (folder form) gets no prediction: it is left out of val_loss and the keypoint metrics and counted
     as a missed frame by the camera metrics, as a frame without a camera is.  The host waits for the GPU once, at the end."""
-    if transform is not None and not isinstance(data, (str, os.PathLike)):
-        raise _lib.SncalError('transform applies to the folder form: batches handed in carry their labels already')
-    if labels != 'host' and not isinstance(data, (str, os.PathLike)):
-        raise _lib.SncalError('labels applies to the folder form: batches handed in carry their labels already')
-    if reduce != 1 and not isinstance(data, (str, os.PathLike)):
-        raise _lib.SncalError('reduce applies to the folder form: batches handed in carry their frames already')
-    if resize is not None and not isinstance(data, (str, os.PathLike)):
-        raise _lib.SncalError('resize applies to the folder form: batches handed in carry their frames already')
+    _refuse_folder_keywords(data, transform=transform, labels=labels, reduce=reduce, resize=resize)
     if sweep is not None:
         if isinstance(camera, (list, tuple)):
             raise _lib.SncalError('sweep takes ONE CameraCreator: the grid replaces the list of calibrators')
         if set(sweep) != {'max_rmse', 'max_rmse_rel'}:
             raise _lib.SncalError(f"sweep={{'max_rmse': [...], 'max_rmse_rel': [...]}}, not keys {sorted(sweep)}")
     cams = list(camera) if isinstance(camera, (list, tuple)) else [camera]
-    own_loss = model.loss
-    if loss is not None:
-        model.loss = loss                      # for this call only: restored below
-    batches = None
-    try:
+    skipped: List[str] = []
+    with _lent_loss(model, loss):
         loss_fn = model._loss()
         nk = loss_fn.num_keypoints
         l2 = L2metric(num_keypoints=nk, conf_threshold=conf_threshold, pckhs_thres=pckhs_thres)
@@ -431,27 +156,16 @@ def validate(model, data: Union[str, Iterable[dict]], camera: Union[CameraCreato
             evals = [EvalAISweep(camera, sweep['max_rmse'], sweep['max_rmse_rel'], threshold=threshold, img_size=img_size)]
         else:
             evals = [EvalAImetric(c, threshold=threshold, img_size=img_size) for c in cams]
-        skipped: List[str] = []
-        if isinstance(data, (str, os.PathLike)):
-            batches = folder_batches(os.fspath(data), batch_size, model.device, nk, float(loss_fn.sigma), img_size, decoder_threads, skipped,
-                                     transform=transform, labels=labels, reduce=reduce, resize=resize)
-        loss_sum = torch.zeros((), dtype=torch.float64, device=model.device)
-        frames = 0
-        for batch in (batches if batches is not None else data):
-            out = model.val_step(batch)
-            B = out['prediction'].shape[0]
-            frames += B
-            loss_sum = loss_sum + out['loss'].to(torch.float64) * B
+
+        def open_folder(folder):
+            return folder_batches(folder, batch_size, model.device, nk, float(loss_fn.sigma), img_size, decoder_threads, skipped,
+                                  transform=transform, labels=labels, reduce=reduce, resize=resize)
+
+        def step(batch, out):
             l2.update(out)
             for ev in evals:
                 ev.update(out)
-        model.check_range()
-    finally:
-        if batches is not None:
-            batches.close()                    # ends the generator: its finally closes the decoder, also after an exception mid-epoch
-        if loss is not None:
-            model.loss = own_loss
-    val_loss = float(loss_sum.item()) / frames if frames else float('nan')
+        val_loss, _ = _epoch(model, data, open_folder, step)
     results = SweepResults() if sweep is not None else []
     for ev in evals:
         ev.add_missed(len(skipped))
@@ -501,44 +215,27 @@ def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, 
     val_loss is the mean of the step losses weighted by step size, as in validate(); val_acc is AccMetric's value (the plain mean
     of the per-batch a@20 * 1.15, so it depends on batch_size, as in the reference).  A frame the decoder refuses (folder form) is
     left out and named in .skipped.  The host waits for the GPU once, at the end."""
-    if reduce != 1 and not isinstance(data, (str, os.PathLike)):
-        raise _lib.SncalError('reduce applies to the folder form: batches handed in carry their frames already')
-    if resize is not None and not isinstance(data, (str, os.PathLike)):
-        raise _lib.SncalError('resize applies to the folder form: batches handed in carry their frames already')
-    own_loss = model.loss
-    if loss is not None:
-        model.loss = loss                      # for this call only: restored below
-    batches = None
-    try:
+    _refuse_folder_keywords(data, reduce=reduce, resize=resize)
+    skipped: List[str] = []
+    state = _State('val')
+    with _lent_loss(model, loss):
         model._loss()
         acc = AccMetric(num_keypoints=len(LINE_CLS), conf_threshold=conf_threshold)
         # the prediction transform has applied its scale: the peaks are pixels already
         ext = None if extremities is None else ExtremityMetric(extremities, conf_threshold=conf_threshold, scale=1, img_size=input_size)
-        skipped: List[str] = []
-        if isinstance(data, (str, os.PathLike)):
-            batches = line_folder_batches(os.fspath(data), batch_size, model.device, acc.num_keypoints, input_size, decoder_threads, skipped,
-                                          reduce=reduce, annots=ext is not None, resize=resize)
-        loss_sum = torch.zeros((), dtype=torch.float64, device=model.device)
-        frames = 0
-        for batch in (batches if batches is not None else data):
+
+        def open_folder(folder):
+            return line_folder_batches(folder, batch_size, model.device, acc.num_keypoints, input_size, decoder_threads, skipped,
+                                       reduce=reduce, annots=ext is not None, resize=resize)
+
+        def step(batch, out):
             if ext is not None and 'annot' not in batch:
                 raise _lib.SncalError("validate_line(extremities=...): every batch dict must carry 'annot', the frames' raw annotations")
-            out = model.val_step(batch)
             acc.num_keypoints = out['prediction'].shape[1]          # the channel count is the network's
-            B = out['prediction'].shape[0]
-            frames += B
-            loss_sum = loss_sum + out['loss'].to(torch.float64) * B
             acc.update(out)
             if ext is not None:
                 ext.update({'prediction': out['prediction'], 'annot': batch['annot']})
-        model.check_range()
-    finally:
-        if batches is not None:
-            batches.close()
-        if loss is not None:
-            model.loss = own_loss
-    state = _State('val')
-    state.metrics['val_loss'] = float(loss_sum.item()) / frames if frames else float('nan')
+        state.metrics['val_loss'], frames = _epoch(model, data, open_folder, step)
     acc.epoch_complete(state)
     detail = None
     if ext is not None:
@@ -549,18 +246,6 @@ def validate_line(model, data: Union[str, Iterable[dict]], batch_size: int = 8, 
         res.extremities = detail
     res.frames, res.skipped = frames + len(skipped), list(skipped)
     return res
-
-
-def add_resize_argument(ap):
-    """--resize W H, shared by the validate, submit and baseline_cameras command lines; parsed_resize() reads it back."""
-    ap.add_argument('--resize', type=int, nargs=2, default=None, metavar=('W', 'H'),
-                    help="bring every frame to W x H after the decode (cv2.resize's bilinear shrink, on the device): frames of any "
-                         'size, mixed sizes included, e.g. --resize 960 540 for a 1280x720 folder; composes with --reduce')
-
-
-def parsed_resize(a):
-    """The resize= keyword of a parsed command line: None, or (W, H)."""
-    return None if a.resize is None else check_size(tuple(a.resize), '--resize')
 
 
 def parser():

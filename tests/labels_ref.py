@@ -1,5 +1,5 @@
 """Frames and the host reference for tests/test_labels_gpu.py (and tools/bench_labels.py): annotations in the SoccerNet form
-{class: [{'x', 'y'}, ...]} (normalised), and what annotations.get_intersections / validate.annot_to_keypoints /
+{class: [{'x', 'y'}, ...]} (normalised), and what annotations.get_intersections / frames.annot_to_keypoints /
 augment.FixLRAmbiguous make of them.  The reference of a set of frames is computed once per process and handed out unchanged."""
 import json
 import os
@@ -127,7 +127,7 @@ def host_reference(annots, margin=0.0, key=None):
     """[(labels {id: (x, y) or None}, mask list, keypoints row, mask vector)] of get_intersections / annot_to_keypoints per
     frame; cached under `key`."""
     from sncal_amd import annotations as an
-    from sncal_amd import validate
+    from sncal_amd import frames
     k = (key, margin)
     if key is not None and k in _CACHE:
         return _CACHE[k]
@@ -137,9 +137,9 @@ def host_reference(annots, margin=0.0, key=None):
         seen.append(an.get_intersections(points, **kw))
         return seen[-1]
     out = []
-    with mock.patch.object(validate, 'get_intersections', spy):
+    with mock.patch.object(frames, 'get_intersections', spy):
         for a in annots:
-            row, vec = validate.annot_to_keypoints(a, 57, margin)
+            row, vec = frames.annot_to_keypoints(a, 57, margin)
             labels, mask = seen[-1]
             out.append((labels, sorted(mask), row, vec))
     if key is not None:

@@ -244,7 +244,7 @@ def test_train_transform_end_to_end_matches_reference(sncal, cuda, gold):
 def test_train_batches_over_a_split_folder(sncal, cuda, gold_dir, gold, tmp_path):
     """The golden 960x540 JPEG beside the fixture's annotations: shapes, order without shuffling, flipped frames carry flipped
     labels, and validate's folder batches with and without the label transform."""
-    V, A = sncal.validate, sncal.augment
+    F, A = sncal.frames, sncal.augment
     full = np.load(os.path.join(gold_dir, 'jpeg_cases.npz'))['jpg.full'].tobytes()
     cases = unjson(gold['labels.cases'])[:5]
     for i, c in enumerate(cases):
@@ -258,7 +258,7 @@ def test_train_batches_over_a_split_folder(sncal, cuda, gold_dir, gold, tmp_path
     want_flip = [random.random() < 0.5 for _ in cases]
     assert any(want_flip) and not all(want_flip)
     random.seed(3)
-    batches = list(V.train_batches(str(tmp_path), 2, flips, shuffle=False, device=cuda, margin=2.0))
+    batches = list(F.train_batches(str(tmp_path), 2, flips, shuffle=False, device=cuda, margin=2.0))
     assert [b['img_name'] for b in batches] == [['00000.jpg', '00001.jpg'], ['00002.jpg', '00003.jpg'], ['00004.jpg']]
     plain = torch_to_tensor(frame, (2, 0, 1)).to(cuda)
     i = 0
@@ -271,20 +271,20 @@ def test_train_batches_over_a_split_folder(sncal, cuda, gold_dir, gold, tmp_path
             if want_flip[i]:
                 a = A.flip_annot(a)
             a = A.test_transform().labels(a)
-            kp, mask = V.annot_to_keypoints(a, 57, 2.0)
+            kp, mask = F.annot_to_keypoints(a, 57, 2.0)
             assert np.array_equal(b['keypoints'][j].numpy(), kp) and np.array_equal(b['mask'][j].numpy(), mask), i
             assert b['raw_annot'][j] == sncal.evaluate.scale_points(a, 960, 540)
             assert torch.equal(b['image'][j], plain.flip(2) if want_flip[i] else plain), i
             i += 1
-    names = [n for b in V.train_batches(str(tmp_path), 2, A.ComposeTransform([]), shuffle=True, seed=4, device=cuda) for n in b['img_name']]
-    again = [n for b in V.train_batches(str(tmp_path), 2, A.ComposeTransform([]), shuffle=True, seed=4, device=cuda) for n in b['img_name']]
+    names = [n for b in F.train_batches(str(tmp_path), 2, A.ComposeTransform([]), shuffle=True, seed=4, device=cuda) for n in b['img_name']]
+    again = [n for b in F.train_batches(str(tmp_path), 2, A.ComposeTransform([]), shuffle=True, seed=4, device=cuda) for n in b['img_name']]
     assert names == again and sorted(names) == [f'{k:05d}.jpg' for k in range(5)] and names != sorted(names)
     # validate's folder batches: transform=None is the labelling of the files as they are, test_transform() changes the swapped frames only
-    none = list(V.folder_batches(str(tmp_path), 5, cuda, 57, 2.0, (960, 540), 0, []))[0]
-    fixed = list(V.folder_batches(str(tmp_path), 5, cuda, 57, 2.0, (960, 540), 0, [], transform=A.test_transform()))[0]
+    none = list(F.folder_batches(str(tmp_path), 5, cuda, 57, 2.0, (960, 540), 0, []))[0]
+    fixed = list(F.folder_batches(str(tmp_path), 5, cuda, 57, 2.0, (960, 540), 0, [], transform=A.test_transform()))[0]
     assert none['image'].dtype == torch.uint8 and torch.equal(none['image'], fixed['image']) and torch.equal(none['image'][0], frame)
     for k, c in enumerate(cases):
-        kp, mask = V.annot_to_keypoints(c['in'], 57, 2.0)
+        kp, mask = F.annot_to_keypoints(c['in'], 57, 2.0)
         assert np.array_equal(none['keypoints'][k].numpy(), kp) and none['raw_annot'][k] == sncal.evaluate.scale_points(c['in'], 960, 540)
         assert torch.equal(none['keypoints'][k], fixed['keypoints'][k]) == (not c['swapped']), k
     assert any(c['swapped'] for c in cases) and not all(c['swapped'] for c in cases)

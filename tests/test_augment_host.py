@@ -148,20 +148,20 @@ def test_validate_labels_with_and_without_the_transform(sncal, gold, tmp_path):
     """A split folder of the fixture's annotations: transform=None labels are what annot_to_keypoints and scale_points give on the
     files as they are (the labelling before this option existed); with test_transform() the frames the reference swaps differ,
     the others do not."""
-    V, A = sncal.validate, sncal.augment
+    V, F, A = sncal.validate, sncal.frames, sncal.augment
     cases = unjson(gold['labels.cases'])[:10]
     for i, c in enumerate(cases):
         (tmp_path / f'{i:05d}.json').write_text(json.dumps(c['in']))
         (tmp_path / f'{i:05d}.jpg').write_bytes(b'\xff\xd8')
-    names, annots = V.list_split(str(tmp_path))
-    plain = V.labelled_batch(None, annots, names, 57, 2.0, (960, 540))
+    names, annots = F.list_split(str(tmp_path))
+    plain = F.labelled_batch(None, annots, names, 57, 2.0, (960, 540))
     for i, a in enumerate(annots):
-        kp, mask = V.annot_to_keypoints(a, 57, 2.0)
+        kp, mask = F.annot_to_keypoints(a, 57, 2.0)
         assert np.array_equal(plain['keypoints'][i].numpy(), kp) and np.array_equal(plain['mask'][i].numpy(), mask)
         assert plain['raw_annot'][i] == sncal.evaluate.scale_points(a, 960, 540)
     assert plain['img_name'] == names and plain['keypoints'].dtype.is_floating_point and tuple(plain['keypoints'].shape) == (len(cases), 171)
     t = A.test_transform()
-    fixed = V.labelled_batch(None, [t.labels(a) for a in annots], names, 57, 2.0, (960, 540))
+    fixed = F.labelled_batch(None, [t.labels(a) for a in annots], names, 57, 2.0, (960, 540))
     swapped = [c['swapped'] for c in cases]
     assert any(swapped) and not all(swapped)
     for i, sw in enumerate(swapped):

@@ -248,8 +248,8 @@ def test_validate_line_folder_form_reads_the_annotations(sncal, cuda, line_model
             json.dump({cls: [{'x': x, 'y': y} for x, y in pts] for cls, pts in case['points'].items()}, f)
         with open(tmp_path / f'{i:05d}.jpg', 'wb') as f:
             f.write(jpg['jpg.full'].tobytes())
-    off = next(iter(sncal.validate.line_folder_batches(str(tmp_path), 2, cuda, 23, (960, 540), 0, [])))
-    on = next(iter(sncal.validate.line_folder_batches(str(tmp_path), 2, cuda, 23, (960, 540), 0, [], annots=True)))
+    off = next(iter(sncal.frames.line_folder_batches(str(tmp_path), 2, cuda, 23, (960, 540), 0, [])))
+    on = next(iter(sncal.frames.line_folder_batches(str(tmp_path), 2, cuda, 23, (960, 540), 0, [], annots=True)))
     assert sorted(off) == ['image', 'img_name', 'keypoints', 'line_para'] and sorted(on) == sorted(list(off) + ['annot'])
     assert on['annot'] == [json.load(open(tmp_path / n.replace('.jpg', '.json'))) for n in on['img_name']]
     plain = sncal.validate.validate_line(model, str(tmp_path), batch_size=2)

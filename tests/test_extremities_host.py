@@ -188,14 +188,14 @@ def test_python_surface_checks():
 
 
 def test_list_line_split_hands_out_the_raw_annotations_on_request(tmp_path):
-    from sncal_amd import validate
+    from sncal_amd import frames
     good = {'Side line top': [{'x': 0.1, 'y': 0.2}, {'x': 0.8, 'y': 0.25}], 'Circle central': [{'x': 0.5, 'y': 0.5}]}
     bad = {'Side line top': [{'x': 0.1, 'y': 0.2}]}                                # one point: sort_anno drops the frame
     for name, annot in (('00000', good), ('00001', bad), ('00002', good)):
         with open(tmp_path / f'{name}.json', 'w') as f:
             json.dump(annot, f)
         (tmp_path / f'{name}.jpg').write_bytes(b'')
-    plain = validate.list_line_split(str(tmp_path))
+    plain = frames.list_line_split(str(tmp_path))
     assert len(plain) == 2 and plain[0] == ['00000.jpg', '00002.jpg']
-    names, labels, raw = validate.list_line_split(str(tmp_path), annots=True)
+    names, labels, raw = frames.list_line_split(str(tmp_path), annots=True)
     assert names == plain[0] and raw == [good, good] and len(labels) == 2

@@ -144,7 +144,7 @@ def test_folder_batches_decode_at_the_reduced_size(sncal, cuda, gold_dir, tmp_pa
     order = group[:3] + [None] + group[3:]
     skipped = []
     with pytest.warns(UserWarning, match='00003.jpg: skipped'):
-        got = list(sncal.validate.decoded_batches(str(tmp_path), files, 4, cuda, 2, skipped, reduce=2))
+        got = list(sncal.frames.decoded_batches(str(tmp_path), files, 4, cuda, 2, skipped, reduce=2))
     assert skipped == ['00003.jpg']
     assert [keep for keep, _ in got] == [[0, 1, 2], [4, 5, 6, 7], [8]]
     for keep, image in got:
@@ -154,7 +154,7 @@ def test_folder_batches_decode_at_the_reduced_size(sncal, cuda, gold_dir, tmp_pa
     # frame_size is the size of the frames yielded: the same folder at another size takes nothing
     skipped = []
     with pytest.warns(UserWarning, match='skipped'):
-        assert list(sncal.validate.decoded_batches(str(tmp_path), files[:2], 4, cuda, 2, skipped, frame_size=(37, 100), reduce=2)) == []
+        assert list(sncal.frames.decoded_batches(str(tmp_path), files[:2], 4, cuda, 2, skipped, frame_size=(37, 100), reduce=2)) == []
     assert skipped == files[:2]
 
 

@@ -1,5 +1,5 @@
 """GPU: sncal_keypoint_labels (csrc/labels.hip) against the host path it restates -- annotations.get_intersections,
-validate.annot_to_keypoints, augment.FixLRAmbiguous -- run here on the same frames (tests/labels_ref.py).
+frames.annot_to_keypoints, augment.FixLRAmbiguous -- run here on the same frames (tests/labels_ref.py).
 
 Bounds, for every frame of every set, none left out:
   presence of each of the 57 labels, the mask vector and `swapped`: IDENTICAL to the host's;
@@ -134,7 +134,7 @@ def test_margin_and_outside_labels(sncal, cuda, frames):
 
 
 def test_fix_lr(sncal, cuda, frames):
-    A, V = sncal.augment, sncal.validate
+    A, F = sncal.augment, sncal.frames
     annots = lr.behind_goal_frames() + frames['plain'][:8]
     fx = A.FixLRAmbiguous()
     verdicts = [fx.decide(a) for a in annots]
@@ -149,7 +149,7 @@ def test_fix_lr(sncal, cuda, frames):
 def test_folder_and_train_batches(sncal, cuda, gold_dir, frames, tmp_path):
     """labels='device' against labels='host' over a folder of 8 small frames, with test_transform() and train_transform()."""
     import os
-    A, V = sncal.augment, sncal.validate
+    A, F = sncal.augment, sncal.frames
     small = np.load(os.path.join(gold_dir, 'jpeg_cases.npz'))['jpg.48x64_420_q95_r0'].tobytes()
     annots = lr.behind_goal_frames()[:4] + frames['plain'][:4]
     for i, a in enumerate(annots):
@@ -166,12 +166,12 @@ def test_folder_and_train_batches(sncal, cuda, gold_dir, frames, tmp_path):
             assert torch.equal(d['image'], h['image'])
 
     def folder(labels):
-        return list(V.folder_batches(str(tmp_path), 3, cuda, 57, 2.0, (960, 540), 0, [], transform=A.test_transform(), labels=labels))
+        return list(F.folder_batches(str(tmp_path), 3, cuda, 57, 2.0, (960, 540), 0, [], transform=A.test_transform(), labels=labels))
 
     def train(labels):
         random.seed(5)
         np.random.seed(5)
-        return list(V.train_batches(str(tmp_path), 3, A.train_transform(), shuffle=True, seed=2, device=cuda, margin=2.0, labels=labels))
+        return list(F.train_batches(str(tmp_path), 3, A.train_transform(), shuffle=True, seed=2, device=cuda, margin=2.0, labels=labels))
     same(folder('host'), folder('device'))
     same(train('host'), train('device'))
     assert any(fx_swapped for fx_swapped, _ in (A.FixLRAmbiguous().decide(a) for a in annots))        # the deferred decision mattered

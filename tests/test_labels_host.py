@@ -10,7 +10,7 @@ import torch
 
 import sncal_amd
 from sncal_amd import annotations as an
-from sncal_amd import augment, validate
+from sncal_amd import augment, frames
 
 import labels_ref as lr
 
@@ -103,18 +103,18 @@ def test_labels_host_is_todays_labelled_batch():
     annots = lr.synthetic_frames(3) + [{}]
     names = [f'{i:05d}.jpg' for i in range(4)]
     image = torch.zeros((4, 2, 2, 3), dtype=torch.uint8)
-    got = validate.labelled_batch(image, annots, names, 57, 3.0, (960, 540), labels='host')
-    plain = validate.labelled_batch(image, annots, names, 57, 3.0, (960, 540))
-    pairs = [validate.annot_to_keypoints(a, 57, 3.0) for a in annots]
+    got = frames.labelled_batch(image, annots, names, 57, 3.0, (960, 540), labels='host')
+    plain = frames.labelled_batch(image, annots, names, 57, 3.0, (960, 540))
+    pairs = [frames.annot_to_keypoints(a, 57, 3.0) for a in annots]
     for out in (got, plain):
         assert out['keypoints'].dtype == torch.float32 and out['mask'].dtype == torch.int64 and not out['keypoints'].is_cuda
         assert out['keypoints'].numpy().tobytes() == np.stack([p[0] for p in pairs]).tobytes()
         assert np.array_equal(out['mask'].numpy(), np.stack([p[1] for p in pairs]))
         assert out['raw_annot'] == [sncal_amd.evaluate.scale_points(a, 960, 540) for a in annots] and out['img_name'] == names
     with pytest.raises(sncal_amd._lib.SncalError):
-        validate.labelled_batch(image, annots, names, 57, 3.0, (960, 540), labels='gpu')
+        frames.labelled_batch(image, annots, names, 57, 3.0, (960, 540), labels='gpu')
     with pytest.raises(sncal_amd._lib.SncalError):
-        validate.labelled_batch(image, annots, names, 57, 3.0, (960, 540), labels='host', fix_lr=True)
+        frames.labelled_batch(image, annots, names, 57, 3.0, (960, 540), labels='host', fix_lr=True)
 
 
 def test_entry_point_validates_before_the_device():

@@ -60,7 +60,7 @@ def test_restatement_takes_the_area_path_at_exactly_half_both_ways_only():
 
 
 def test_reduce_then_resize_size_bookkeeping(sncal):
-    plan = sncal.validate.resize_plan
+    plan = sncal.frames.resize_plan
     assert plan(1080, 1920, 1, None) == ((1080, 1920), (1080, 1920))
     assert plan(1080, 1920, 2, None) == ((540, 960), (540, 960))
     assert plan(720, 1280, 1, (960, 540)) == ((720, 1280), (540, 960))           # resize is (W, H), sizes are (H, W)
@@ -71,10 +71,10 @@ def test_reduce_then_resize_size_bookkeeping(sncal):
             plan(720, 1280, 1, bad)
     with pytest.raises(sncal._lib.SncalError):
         plan(720, 1280, 3, (960, 540))
-    assert sncal.validate.MAX_SOURCE_SIZES == 4
+    assert sncal.frames.MAX_SOURCE_SIZES == 4
     # frame_size stays the size of the frames yielded: one that contradicts resize is refused before a file is opened
     with pytest.raises(sncal._lib.SncalError, match='frame_size'):
-        next(sncal.validate.decoded_batches('/nonexistent', ['a.jpg'], 1, 'cpu', 0, [], frame_size=(540, 960), resize=(72, 54)))
+        next(sncal.frames.decoded_batches('/nonexistent', ['a.jpg'], 1, 'cpu', 0, [], frame_size=(540, 960), resize=(72, 54)))
 
 
 def test_resize_argument_of_the_three_command_lines(sncal):
@@ -83,14 +83,28 @@ def test_resize_argument_of_the_three_command_lines(sncal):
              (b, ['--line-model', 'm', '--img-dir', 'd', '--save-dir', 'o'])]
     for mod, argv in lines:
         a = mod.parser().parse_args(argv)
-        assert a.resize is None and v.parsed_resize(a) is None and a.reduce == 1
+        assert a.resize is None and sncal.resize.parsed_resize(a) is None and a.reduce == 1
         a = mod.parser().parse_args(argv + ['--resize', '960', '540', '--reduce', '2'])
-        assert v.parsed_resize(a) == (960, 540) and a.reduce == 2
+        assert sncal.resize.parsed_resize(a) == (960, 540) and a.reduce == 2
         for bad in (['--resize', '960'], ['--resize', '960', 'x'], ['--resize', '960', '540', '3']):
             with pytest.raises(SystemExit):
                 mod.parser().parse_args(argv + bad)
         with pytest.raises(sncal._lib.SncalError):
-            v.parsed_resize(mod.parser().parse_args(argv + ['--resize', '960', '0']))
+            sncal.resize.parsed_resize(mod.parser().parse_args(argv + ['--resize', '960', '0']))
+
+
+MOVED_TO_FRAMES = ['list_split', 'list_line_split', 'annot_to_keypoints', 'resize_plan', 'MAX_SOURCE_SIZES', 'decoded_batches', '_label_mode',
+                   'labelled_batch', 'folder_batches', 'train_batches', 'line_folder_batches']
+
+
+def test_the_old_addresses_in_validate_are_the_same_objects(sncal):
+    """The loaders lived in validate.py until frames.py: README, DESIGN, INTEGRATION and code outside this tree still say
+    validate.train_batches.  The old address is the object itself, not a wrapper."""
+    for n in MOVED_TO_FRAMES:
+        assert getattr(sncal.validate, n) is getattr(sncal.frames, n), n
+    for n in ('add_resize_argument', 'parsed_resize'):
+        assert getattr(sncal.validate, n) is getattr(sncal.resize, n), n
+    assert not hasattr(sncal.validate, '_resized_batches') and not hasattr(sncal.frames, '_resized_batches')
 
 
 def test_resize_u8_refuses_what_is_not_on_the_gpu(sncal):

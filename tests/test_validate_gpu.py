@@ -110,7 +110,7 @@ def _dataset(sncal, n=11):
 def _batches(sncal, images, annots, names, size):
     out = []
     for i in range(0, len(images), size):
-        pairs = [sncal.validate.annot_to_keypoints(a, 57, margin=LOSS['sigma']) for a in annots[i:i + size]]
+        pairs = [sncal.frames.annot_to_keypoints(a, 57, margin=LOSS['sigma']) for a in annots[i:i + size]]
         out.append({'image': torch.from_numpy(images[i:i + size]), 'keypoints': torch.from_numpy(np.stack([p[0] for p in pairs])),
                     'mask': torch.from_numpy(np.stack([p[1] for p in pairs])),
                     'raw_annot': [sncal.evaluate.scale_points(a, 960, 540) for a in annots[i:i + size]], 'img_name': names[i:i + size]})
@@ -230,7 +230,7 @@ def test_validate_over_a_split_folder(sncal, cuda, gold_dir, tmp_path):
     batches = []
     for lo, hi in ((0, 2), (2, 3), (3, 5)):                                 # the folder's batches of two, frame 2 left out of its batch
         idx = keep[lo:hi]
-        pairs = [sncal.validate.annot_to_keypoints(annots[i], 57, margin=LOSS['sigma']) for i in idx]
+        pairs = [sncal.frames.annot_to_keypoints(annots[i], 57, margin=LOSS['sigma']) for i in idx]
         batches.append({'image': frames[lo:hi], 'keypoints': torch.from_numpy(np.stack([p[0] for p in pairs])),
                         'mask': torch.from_numpy(np.stack([p[1] for p in pairs])),
                         'raw_annot': [sncal.evaluate.scale_points(annots[i], 960, 540) for i in idx],

@@ -205,7 +205,7 @@ def test_annotation_to_keypoints_is_the_dataset_rule():
     import sncal_amd
     annot, _ = sncal_amd.synth.synthetic_annotation(seed=3)
     as_dicts = {c: [{'x': x, 'y': y} for x, y in pts] for c, pts in annot.items()}
-    kp, mask = sncal_amd.validate.annot_to_keypoints(as_dicts, 57, margin=2.0)
+    kp, mask = sncal_amd.frames.annot_to_keypoints(as_dicts, 57, margin=2.0)
     labels, missing = sncal_amd.annotations.get_intersections(annot, margin=2.0)
     assert kp.dtype == np.float32 and kp.shape == (171,) and mask.shape == (58,) and mask.dtype == np.int64
     kp = kp.reshape(57, 3)

@@ -142,7 +142,7 @@ def test_validate_line_over_a_split_folder(sncal, cuda, line_model, gold_dir, tm
             json.dump({cls: [{'x': x, 'y': y} for x, y in pts] for cls, pts in case['points'].items()}, f)
         with open(tmp_path / f'{name}.jpg', 'wb') as f:
             f.write(jpg[key].tobytes())
-    names, labs = sncal.validate.list_line_split(str(tmp_path))
+    names, labs = sncal.frames.list_line_split(str(tmp_path))
     assert names == ['00000.jpg', '00002.jpg', '00003.jpg', '00004.jpg', '00005.jpg'] and len(labs) == 5
     with pytest.warns(UserWarning, match='skipped'):
         res = sncal.validate.validate_line(model, str(tmp_path), batch_size=2)
@@ -151,7 +151,7 @@ def test_validate_line_over_a_split_folder(sncal, cuda, line_model, gold_dir, tm
     acc = sncal.AccMetric(num_keypoints=23, conf_threshold=0.2)
     total, frames, seen = 0.0, 0, []
     with pytest.warns(UserWarning, match='skipped'):
-        for b in sncal.validate.line_folder_batches(str(tmp_path), 2, cuda, 23, (960, 540), 0, skipped):
+        for b in sncal.frames.line_folder_batches(str(tmp_path), 2, cuda, 23, (960, 540), 0, skipped):
             assert b['image'].dtype == torch.uint8 and b['image'].shape[1:] == (540, 960, 3) and b['keypoints'].shape[1:] == (138,)
             out = model.val_step(b)
             acc.update(out)
@@ -161,5 +161,5 @@ def test_validate_line_over_a_split_folder(sncal, cuda, line_model, gold_dir, tm
     assert seen == ['00000.jpg', '00002.jpg', '00005.jpg'] and skipped == res.skipped
     assert res['val_acc'] == acc.compute() and abs(res['val_loss'] - total / frames) <= 1e-12 * res['val_loss']
     kp0, _ = sncal.annotations.line_keypoints(labs[0])
-    first = next(iter(sncal.validate.line_folder_batches(str(tmp_path), 1, cuda, 23, (960, 540), 0, [])))
+    first = next(iter(sncal.frames.line_folder_batches(str(tmp_path), 1, cuda, 23, (960, 540), 0, [])))
     assert np.array_equal(first['keypoints'][0].numpy(), kp0) and first['line_para'].shape == (1, 23, 2)

@@ -189,7 +189,7 @@ def test_argument_checks_need_no_device():
 def test_list_line_split_lists_what_the_dataset_lists(gold, tmp_path):
     """EHMDataset.__init__: json + jpg pairs, names without 'info', annotations sort_anno finds usable (here sorted by name)."""
     import json
-    from sncal_amd import validate
+    from sncal_amd import frames
     cases = vr.label_cases(gold)
     files = {'00002': cases[0], '00000': cases[1], '00001': cases[-4], 'x_info': cases[2], '00003': cases[3], '00004': cases[-2]}
     for name, c in files.items():
@@ -198,7 +198,7 @@ def test_list_line_split_lists_what_the_dataset_lists(gold, tmp_path):
         if name != '00003':
             (tmp_path / f'{name}.jpg').write_bytes(b'')
     (tmp_path / 'notes.txt').write_text('x')
-    names, labels = validate.list_line_split(str(tmp_path))
+    names, labels = frames.list_line_split(str(tmp_path))
     assert names == ['00000.jpg', '00002.jpg', '00004.jpg']                 # 00001: horizontal line; 00003: no image; x_info: ignored
     _same_labels(labels[0], cases[1]['labels'])
     _same_labels(labels[1], cases[0]['labels'])

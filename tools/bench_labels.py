@@ -90,14 +90,14 @@ def pipeline_rates(dev, n_frames):
         source = benchlib.jpeg_folder(folder, n_frames)
         model = benchlib.keypoint_model(tmp)
         cal = sncal_amd.submit.default_calibrator()
-        A, V = sncal_amd.augment, sncal_amd.validate
+        A, V, F = sncal_amd.augment, sncal_amd.validate, sncal_amd.frames
 
         def epoch(labels, bs):
             import random
             random.seed(1)
             np.random.seed(1)
             n = 0
-            for b in V.train_batches(folder, bs, A.train_transform(), shuffle=True, seed=0, device=dev, margin=3.0, labels=labels):
+            for b in F.train_batches(folder, bs, A.train_transform(), shuffle=True, seed=0, device=dev, margin=3.0, labels=labels):
                 n += len(b['img_name'])
             return n
         rows = []

@@ -89,7 +89,7 @@ def validate_rates(dev, n_frames=512):
         folder = os.path.join(tmp, 'valid')
         source = benchlib.jpeg_folder(folder, n_frames)
         model = benchlib.line_model(tmp)
-        usable = len(sncal_amd.validate.list_line_split(folder)[0])
+        usable = len(sncal_amd.frames.list_line_split(folder)[0])
         rows = []
         for bs in (8, 64):
             def run():
