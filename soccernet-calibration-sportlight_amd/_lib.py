@@ -232,6 +232,63 @@ def current_stream_ptr():
     return int(torch.cuda.current_stream().cuda_stream)
 
 
+def call(name, *args, device=None):
+    """check(lib().<name>(*args), name).  A tensor (anything with data_ptr) goes as its address -- NULL for an empty one -- and None
+    and everything else as they are.  device: make it current around a host call that needs it (the launches use launch())."""
+    fn = getattr(lib(), name)
+    args = [a.data_ptr() if hasattr(a, 'data_ptr') else a for a in args]
+    if device is None:
+        return check(fn(*args), name)
+    import torch
+    with torch.cuda.device(device):
+        check(fn(*args), name)
+
+
+def launch(name, device, *args):
+    """call() with `device` current and torch's current stream on it as the last argument: where include/sncal.h puts every
+    `void* stream` (tests/test_lib_call_host.py holds the header to that)."""
+    import torch
+    with torch.cuda.device(device):
+        call(name, *args, current_stream_ptr())
+
+
+def workspace_bytes(query_name, *dims):
+    """The size_t a sncal_*_workspace query writes through its last argument."""
+    n = ctypes.c_size_t()
+    call(query_name, *dims, ctypes.byref(n))
+    return n.value
+
+
+def workspace(query_name, *dims, device):
+    """uint8 scratch of the size the query names, at least 16 bytes so that an empty batch still has an address."""
+    import torch
+    return torch.empty(max(workspace_bytes(query_name, *dims), 16), dtype=torch.uint8, device=device)
+
+
+def pack_parts(parts):
+    """Host arrays -> (flat uint8 array holding them one after the other, their byte offsets).  Every part starts at a multiple
+    of 8 bytes, in whatever order they come, so each can be read on the device as the type it has."""
+    import numpy as np
+    offsets = [0]
+    for p in parts:
+        offsets.append(offsets[-1] + -(-p.nbytes // 8) * 8)
+    flat = np.zeros(offsets.pop(), np.uint8)
+    for at, p in zip(offsets, parts):
+        flat[at:at + p.nbytes] = np.ascontiguousarray(p).reshape(-1).view(np.uint8)
+    return flat, offsets
+
+
+def upload(parts, device, pinned=False):
+    """pack_parts in one copy to the device -> (the device tensor, which the caller keeps alive until the launch is queued, [device
+    address of each part]).  pinned: from page-locked memory and without waiting; a copy from pageable memory holds the host
+    until the stream has drained."""
+    import torch
+    flat, offsets = pack_parts(parts)
+    host = torch.from_numpy(flat)
+    d = host.pin_memory().to(device, non_blocking=True) if pinned else host.to(device)
+    return d, [d.data_ptr() + at for at in offsets]
+
+
 def require_device(t, dtype, name):
     import torch
     if not isinstance(t, torch.Tensor) or not t.is_cuda:

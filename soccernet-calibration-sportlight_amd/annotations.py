@@ -489,33 +489,23 @@ def keypoint_labels_device(annots, img_size=(960, 540), within_image: bool = Tru
     (sncal_keypoint_labels) -> (keypoints (B, 3*num_keypoints) float32, mask (B, num_keypoints + 1) int64, swapped (B,) uint8), on
     the device; with return_labels also (labels (B,57,2) float64, present (B,57) uint8): the fp64 labels before the float32 rows.
     swapped[b] = 1: the labels are those of flip_annot_names(annot, False, False), as FixLRAmbiguous would have renamed it."""
-    import ctypes
     import torch
     from . import _lib
     dev = torch.device(device)
     points, offsets, present = pack_annotations(annots)
     B, N = len(annots), int(num_keypoints)
-    n = ctypes.c_size_t()
-    _lib.check(_lib.lib().sncal_keypoint_labels_workspace(B, len(points), ctypes.byref(n)), 'sncal_keypoint_labels_workspace')
-    with torch.cuda.device(dev):
-        key = (dev.type, torch.cuda.current_device())
-        if key not in _SAMPLES:
-            _SAMPLES[key] = torch.from_numpy(sample_tables()).to(dev)
-        keypoints = torch.empty((B, 3 * N), dtype=torch.float32, device=dev)
-        mask = torch.empty((B, N + 1), dtype=torch.int64, device=dev)
-        swapped = torch.zeros(B, dtype=torch.uint8, device=dev)
-        labels = torch.empty((B, 57, 2), dtype=torch.float64, device=dev) if return_labels else None
-        lpres = torch.empty((B, 57), dtype=torch.uint8, device=dev) if return_labels else None
-        if B:
-            flat = np.concatenate([points.reshape(-1).view(np.uint8), offsets.reshape(-1).view(np.uint8), present.view(np.uint8)])
-            d_in = torch.from_numpy(flat).to(dev)                             # one upload: points | offsets | present (8-byte multiples first)
-            p_pts = d_in.data_ptr()
-            p_off = p_pts + points.nbytes
-            ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=dev)
-            _lib.check(_lib.lib().sncal_keypoint_labels(
-                p_pts, len(points), p_off, p_off + offsets.nbytes, B, len(ANNOT_CLASSES), int(img_size[0]), int(img_size[1]),
-                int(bool(within_image)), float(margin), N, LABELS_FIX_LR if fix_lr else 0, _SAMPLES[key].data_ptr(),
-                keypoints.data_ptr(), mask.data_ptr(), labels.data_ptr() if return_labels else None,
-                lpres.data_ptr() if return_labels else None, swapped.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
-                'sncal_keypoint_labels')
+    ws = _lib.workspace('sncal_keypoint_labels_workspace', B, len(points), device=dev)
+    key = (dev.type, torch.cuda.current_device() if dev.index is None else dev.index)
+    if key not in _SAMPLES:
+        _SAMPLES[key] = torch.from_numpy(sample_tables()).to(dev)
+    keypoints = torch.empty((B, 3 * N), dtype=torch.float32, device=dev)
+    mask = torch.empty((B, N + 1), dtype=torch.int64, device=dev)
+    swapped = torch.zeros(B, dtype=torch.uint8, device=dev)
+    labels = torch.empty((B, 57, 2), dtype=torch.float64, device=dev) if return_labels else None
+    lpres = torch.empty((B, 57), dtype=torch.uint8, device=dev) if return_labels else None
+    if B:
+        d_in, (p_pts, p_off, p_present) = _lib.upload([points, offsets, present], dev)         # one upload: points | offsets | present
+        _lib.launch('sncal_keypoint_labels', dev, p_pts, len(points), p_off, p_present, B, len(ANNOT_CLASSES), int(img_size[0]),
+                    int(img_size[1]), int(bool(within_image)), float(margin), N, LABELS_FIX_LR if fix_lr else 0, _SAMPLES[key],
+                    keypoints, mask, labels, lpres, swapped, ws, ws.numel())
     return (keypoints, mask, swapped, labels, lpres) if return_labels else (keypoints, mask, swapped)

@@ -322,19 +322,13 @@ def augment_u8(image, params, noise=None, want_u8: bool = True, want_chw: bool =
         if tuple(noise.shape) != tuple(image.shape):
             raise _lib.SncalError(f'noise {tuple(noise.shape)} must be shaped like the image {tuple(image.shape)}')
     dev = image.device
-    n = ctypes.c_size_t()
-    _lib.check(_lib.lib().sncal_augment_workspace(B, max(H, 1), max(W, 1), ctypes.byref(n)), 'sncal_augment_workspace')
-    with torch.cuda.device(dev):
-        u8 = torch.empty_like(image) if want_u8 else None
-        chw = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev) if want_chw else None
-        if B == 0 or H == 0 or W == 0:
-            return u8, chw
-        host = torch.from_numpy(np.frombuffer(params, dtype=np.uint8, count=B * ctypes.sizeof(_lib.AugmentParams)).copy())
-        d_params = host.to(dev)
-        ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=dev)
-        _lib.check(_lib.lib().sncal_augment_u8(image.data_ptr(), B, H, W, d_params.data_ptr(), noise.data_ptr() if noise is not None else None,
-                                               u8.data_ptr() if want_u8 else None, chw.data_ptr() if want_chw else None,
-                                               ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()), 'sncal_augment_u8')
+    ws = _lib.workspace('sncal_augment_workspace', B, max(H, 1), max(W, 1), device=dev)
+    u8 = torch.empty_like(image) if want_u8 else None
+    chw = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev) if want_chw else None
+    if B == 0 or H == 0 or W == 0:
+        return u8, chw
+    host = torch.from_numpy(np.frombuffer(params, dtype=np.uint8, count=B * ctypes.sizeof(_lib.AugmentParams)).copy())
+    _lib.launch('sncal_augment_u8', dev, image, B, H, W, host.to(dev), noise, u8, chw, ws, ws.numel())
     return u8, chw
 
 

@@ -188,22 +188,19 @@ def line_cameras(peaks=None, pred_annots=None, img_size=(960, 540), refine: bool
         p_pts, p_off, _ = pred_annots if isinstance(pred_annots, tuple) else pack_annotations(pred_annots)
         B, dev, parts = len(p_off), torch.device(device), [p_pts, p_off]
     rec = ctypes.sizeof(_lib.Camera)
-    with torch.cuda.device(dev):
-        cams = torch.zeros((B, rec), dtype=torch.uint8, device=dev)
-        status = torch.zeros(B, dtype=torch.int32, device=dev)
-        Hm = torch.zeros((B, 9), dtype=torch.float64, device=dev)
-        n_lines = torch.zeros(B, dtype=torch.int32, device=dev)
-        slots = torch.full((B, len(END_POINTS)), -1, dtype=torch.int32, device=dev)
-        if B or peaks is not None:
-            if peaks is not None:
-                args = (peaks.data_ptr() if B else None, peaks.shape[1], float(scale), float(p_threshold), None, 0, None)
-            else:
-                flat = np.concatenate([np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in parts])
-                d_in = torch.from_numpy(flat).pin_memory().to(dev, non_blocking=True)       # one upload, pinned: extremity_counts' reason
-                args = (None, 0, float(scale), float(p_threshold), d_in.data_ptr(), len(p_pts), d_in.data_ptr() + p_pts.nbytes)
-            _lib.check(_lib.lib().sncal_baseline_cameras(*args, B, len(ANNOT_CLASSES), int(img_size[0]), int(img_size[1]), int(bool(refine)),
-                                                     cams.data_ptr(), status.data_ptr(), Hm.data_ptr(), n_lines.data_ptr(),
-                                                     slots.data_ptr(), len(END_POINTS), _lib.current_stream_ptr()), 'sncal_baseline_cameras')
+    cams = torch.zeros((B, rec), dtype=torch.uint8, device=dev)
+    status = torch.zeros(B, dtype=torch.int32, device=dev)
+    Hm = torch.zeros((B, 9), dtype=torch.float64, device=dev)
+    n_lines = torch.zeros(B, dtype=torch.int32, device=dev)
+    slots = torch.full((B, len(END_POINTS)), -1, dtype=torch.int32, device=dev)
+    if B or peaks is not None:
+        if peaks is not None:
+            args = (peaks, peaks.shape[1], float(scale), float(p_threshold), None, 0, None)      # an empty batch's peaks go as NULL
+        else:
+            d_in, ptr = _lib.upload(parts, dev, pinned=True)                                 # one upload, pinned: extremity_counts' reason
+            args = (None, 0, float(scale), float(p_threshold), ptr[0], len(p_pts), ptr[1])
+        _lib.launch('sncal_baseline_cameras', dev, *args, B, len(ANNOT_CLASSES), int(img_size[0]), int(img_size[1]), int(bool(refine)),
+                    cams, status, Hm, n_lines, slots, len(END_POINTS))
     return cams, status, Hm, n_lines, slots
 
 

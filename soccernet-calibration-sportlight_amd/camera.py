@@ -61,7 +61,7 @@ def unproject_image_point(homography, point2D):
 def _gpu_pnp(mode, calibration, rotation, position, point_matches, max_iters=0, eps=0.0):
     """One-frame call of sncal_solve_pnp (mode 1) / sncal_pnp_refine_lm (mode 0)."""
     import torch
-    L = _lib.lib()
+    _lib.lib()
     if not torch.cuda.is_available():
         raise _lib.SncalError('Camera.solve_pnp / refine_camera need a GPU (libsncal.so has no CPU path)')
     obj = np.array([pt[0] for pt in point_matches], dtype=np.float64).reshape(-1, 3)
@@ -77,16 +77,11 @@ def _gpu_pnp(mode, calibration, rotation, position, point_matches, max_iters=0, 
     d_n = torch.tensor([n], dtype=torch.int32, device=dev)
     rt = np.concatenate([np.asarray(rotation, dtype=np.float64).reshape(9), np.asarray(position, dtype=np.float64).reshape(3)])
     d_rt = torch.from_numpy(rt).to(dev)
-    d_rm = torch.full((1,), -2.0, dtype=torch.float64, device=dev)
-    s = _lib.current_stream_ptr()
     if mode == 1:
-        _lib.check(L.sncal_solve_pnp(d_K.data_ptr(), d_o.data_ptr(), d_i.data_ptr(), d_n.data_ptr(), 1, n,
-                                     d_rt.data_ptr(), s), 'sncal_solve_pnp')
-        d_rm = None
+        _lib.launch('sncal_solve_pnp', dev, d_K, d_o, d_i, d_n, 1, n, d_rt)
     else:
-        _lib.check(L.sncal_pnp_refine_lm(d_K.data_ptr(), d_o.data_ptr(), d_i.data_ptr(), d_n.data_ptr(), 1, n,
-                                         d_rt.data_ptr(), d_rm.data_ptr(), int(max_iters), float(eps), s),
-                   'sncal_pnp_refine_lm')
+        d_rm = torch.full((1,), -2.0, dtype=torch.float64, device=dev)
+        _lib.launch('sncal_pnp_refine_lm', dev, d_K, d_o, d_i, d_n, 1, n, d_rt, d_rm, int(max_iters), float(eps))
     out = d_rt.cpu().numpy()
     changed = not np.array_equal(out, rt)
     return out[:9].reshape(3, 3).copy(), out[9:].copy(), changed

@@ -169,12 +169,8 @@ class CameraEvaluator:
         C = len(CLASSES)
         err = torch.empty((B, 2, C, max_gt), dtype=torch.float64, device=self.device) if detail else None
         cls = torch.empty((B, 2, C, 4), dtype=torch.int32, device=self.device) if detail else None
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().sncal_evaluate_cameras_detail(
-                records.data_ptr(), B, self._field.data_ptr(), self._start.data_ptr(), self._mirror.data_ptr(), C,
-                d_gt.data_ptr(), d_cnt.data_ptr(), d_extra.data_ptr(), max_gt, self.threshold, self.width, self.height,
-                out.data_ptr(), err.data_ptr() if detail else None, cls.data_ptr() if detail else None,
-                _lib.current_stream_ptr()), 'sncal_evaluate_cameras_detail')
+        _lib.launch('sncal_evaluate_cameras_detail', self.device, records, B, self._field, self._start, self._mirror, C, d_gt, d_cnt,
+                    d_extra, max_gt, self.threshold, self.width, self.height, out, err, cls)
         return (out, err, cls) if detail else out
 
     def evaluate_outcomes(self, outcomes, annotations: Sequence[Dict[str, list]]):
@@ -191,11 +187,8 @@ class CameraEvaluator:
             return contrib
         gt, cnt, extra, max_gt = self.pack(annotations)
         d_gt, d_cnt, d_extra = (torch.from_numpy(a).to(self.device) for a in (gt, cnt, extra))
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().sncal_evaluate_outcomes(
-                outcomes.data_ptr(), B, S, self._field.data_ptr(), self._start.data_ptr(), self._mirror.data_ptr(), len(CLASSES),
-                d_gt.data_ptr(), d_cnt.data_ptr(), d_extra.data_ptr(), max_gt, self.threshold, self.width, self.height,
-                contrib.data_ptr(), _lib.current_stream_ptr()), 'sncal_evaluate_outcomes')
+        _lib.launch('sncal_evaluate_outcomes', self.device, outcomes, B, S, self._field, self._start, self._mirror, len(CLASSES), d_gt,
+                    d_cnt, d_extra, max_gt, self.threshold, self.width, self.height, contrib)
         return contrib
 
     def sweep_fold(self, contrib, choice):
@@ -207,9 +200,7 @@ class CameraEvaluator:
         if contrib.dim() != 3 or contrib.shape[2] != 8 or choice.dim() != 2 or choice.shape[1] != contrib.shape[0]:
             raise _lib.SncalError('contrib must be (B,S,8) and choice (n_grid,B)')
         acc = torch.empty((choice.shape[0], 8), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().sncal_sweep_fold(contrib.data_ptr(), choice.data_ptr(), contrib.shape[0], contrib.shape[1],
-                                                   choice.shape[0], acc.data_ptr(), _lib.current_stream_ptr()), 'sncal_sweep_fold')
+        _lib.launch('sncal_sweep_fold', self.device, contrib, choice, contrib.shape[0], contrib.shape[1], choice.shape[0], acc)
         return acc
 
     @staticmethod

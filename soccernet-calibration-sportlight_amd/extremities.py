@@ -206,30 +206,23 @@ def extremity_counts(gt, peaks=None, pred_annots=None, img_size=(960, 540), ts: 
         if len(p_off) != B:
             raise _lib.SncalError(f'{len(p_off)} predictions for {B} annotations')
         dev = torch.device(device)
-        parts = [g_pts, p_pts, g_off, p_off]                                 # the fp64 arrays first: every part starts 8-byte aligned
+        parts = [g_pts, g_off, p_pts, p_off]
     n_cls = len(ANNOT_CLASSES)
     c_ts = (ctypes.c_double * max(T, 1))(*[float(t) for t in ts])
-    with torch.cuda.device(dev):
-        frame = torch.empty((T, B, 4), dtype=torch.int32, device=dev)
-        cls = torch.empty((T, B, n_cls, 3), dtype=torch.int32, device=dev)
-        err = torch.empty((T, B, n_cls, 2), dtype=torch.float64, device=dev)
-        if B:
-            flat = np.concatenate([np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in parts])
-            # one upload, from pinned memory and without waiting: a copy from pageable memory would hold the host until the stream has
-            # drained, i.e. until the forward queued in front of it has finished, and the next batch's JPEG stage would wait with it
-            d_in = torch.from_numpy(flat).pin_memory().to(dev, non_blocking=True)
-            at, ptr = d_in.data_ptr(), []
-            for a in parts:
-                ptr.append(at)
-                at += a.nbytes
-            if peaks is not None:
-                args = (ptr[0], len(g_pts), ptr[1], peaks.data_ptr(), peaks.shape[1], float(scale), float(p_threshold), None, 0, None)
-            else:
-                args = (ptr[0], len(g_pts), ptr[2], None, 0, float(scale), float(p_threshold), ptr[1], len(p_pts), ptr[3])
-            _lib.check(_lib.lib().sncal_extremity_counts(*args, B, n_cls, int(img_size[0]), int(img_size[1]), c_ts, T, frame.data_ptr(),
-                                                         cls.data_ptr(), err.data_ptr(), _lib.current_stream_ptr()), 'sncal_extremity_counts')
-        elif not 1 <= T <= 8:
-            raise _lib.SncalError(f'{T} thresholds (1..8)')
+    frame = torch.empty((T, B, 4), dtype=torch.int32, device=dev)
+    cls = torch.empty((T, B, n_cls, 3), dtype=torch.int32, device=dev)
+    err = torch.empty((T, B, n_cls, 2), dtype=torch.float64, device=dev)
+    if B:
+        # one upload, from pinned memory and without waiting: a copy from pageable memory would hold the host until the stream has
+        # drained, i.e. until the forward queued in front of it has finished, and the next batch's JPEG stage would wait with it
+        d_in, ptr = _lib.upload(parts, dev, pinned=True)
+        if peaks is not None:
+            args = (ptr[0], len(g_pts), ptr[1], peaks, peaks.shape[1], float(scale), float(p_threshold), None, 0, None)
+        else:
+            args = (ptr[0], len(g_pts), ptr[1], None, 0, float(scale), float(p_threshold), ptr[2], len(p_pts), ptr[3])
+        _lib.launch('sncal_extremity_counts', dev, *args, B, n_cls, int(img_size[0]), int(img_size[1]), c_ts, T, frame, cls, err)
+    elif not 1 <= T <= 8:
+        raise _lib.SncalError(f'{T} thresholds (1..8)')
     return frame, cls, err
 
 

@@ -106,18 +106,19 @@ class HRNetHeatmap:
         if num_refinement_stages != 0:
             raise _lib.SncalError('refinement stages are never instantiated by the reference configs; unsupported')
         self.cfg = load_config(hrnet_config, head=head, upscale=upscale)
-        self._L = _lib.lib()
+        self._L = _lib.lib()         # the library handle, for the raw ABI calls of the tests; the methods here go through _lib.call / launch
+        x3 = self._L.sncal_x3_name().decode()
         if dtype is None:
-            dtype = self._L.sncal_x3_name().decode()
+            dtype = x3
         self.dtype_name = dtype
         self.dtype = DTYPES[dtype]
         self.device = torch.device(device)
-        if dtype in ('fp16x3', 'bf16x3') and dtype != self._L.sncal_x3_name().decode():
+        if dtype in ('fp16x3', 'bf16x3') and dtype != x3:
             raise _lib.SncalError(f"dtype {dtype!r}: this libsncal.so implements the split-arithmetic engine as "
-                                  f"{self._L.sncal_x3_name().decode()!r} (rebuild with -DSNCAL_X3_F16={int(dtype == 'fp16x3')} for the other split type)")
+                                  f"{x3!r} (rebuild with -DSNCAL_X3_F16={int(dtype == 'fp16x3')} for the other split type)")
         self._h = _lib.vp()
         desc = _desc(self.cfg)
-        _lib.check(self._L.sncal_hrnet_create(ctypes.byref(desc), self.dtype, ctypes.byref(self._h)), 'sncal_hrnet_create')
+        _lib.call('sncal_hrnet_create', ctypes.byref(desc), self.dtype, ctypes.byref(self._h))
         self.num_classes = desc.num_classes
         self._ws = None
         self._loaded = False
@@ -139,17 +140,16 @@ class HRNetHeatmap:
         name = ctypes.create_string_buffer(128)
         bn = ctypes.create_string_buffer(128)
         ci, co, k, s, hb = (ctypes.c_int() for _ in range(5))
-        for i in range(self._L.sncal_hrnet_num_convs(self._h)):
-            _lib.check(self._L.sncal_hrnet_conv_info(self._h, i, name, 128, bn, 128, ctypes.byref(ci), ctypes.byref(co),
-                                                     ctypes.byref(k), ctypes.byref(s), ctypes.byref(hb)), 'conv_info')
+        for i in range(_lib.lib().sncal_hrnet_num_convs(self._h)):
+            _lib.call('sncal_hrnet_conv_info', self._h, i, name, 128, bn, 128, ctypes.byref(ci), ctypes.byref(co), ctypes.byref(k),
+                      ctypes.byref(s), ctypes.byref(hb))
             out.append((name.value.decode(), bn.value.decode(), ci.value, co.value, k.value, s.value, bool(hb.value)))
         return out
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """Accepts the reference's nn_state_dict (keys 'model.conv1.weight', ... metamodel.py:108-124)."""
         self.set_convs(state_dict, strict)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.sncal_hrnet_finalize(self._h), 'sncal_hrnet_finalize')
+        _lib.call('sncal_hrnet_finalize', self._h, device=self.device)
         self._loaded = True
         return self
 
@@ -183,16 +183,16 @@ class HRNetHeatmap:
             wf = np.ascontiguousarray(w.to(torch.float32).numpy())
             sc = np.ascontiguousarray(scale.to(torch.float32).numpy())
             sh = np.ascontiguousarray(shift.to(torch.float32).numpy())
-            _lib.check(self._L.sncal_hrnet_set_conv(self._h, i, wf.ctypes.data, sc.ctypes.data, sh.ctypes.data), 'set_conv')
+            _lib.call('sncal_hrnet_set_conv', self._h, i, wf.ctypes.data, sc.ctypes.data, sh.ctypes.data)
         if strict:
             extra = [k for k in sd if k not in used and not k.endswith('num_batches_tracked')]
             if extra:
                 raise _lib.SncalError(f'unexpected keys in state dict: {extra[:5]}...')
         # fp16x3: block-internal channels are rebalanced by exact powers of two inside the library (sncal_hrnet_equalize = the first step
         # of sncal_hrnet_finalize; sncal.h "balance"), so that a caller of the C ABI gets what load_model gets
-        _lib.check(self._L.sncal_hrnet_set_equalize(self._h, int(self.equalize)), 'sncal_hrnet_set_equalize')
+        _lib.call('sncal_hrnet_set_equalize', self._h, int(self.equalize))
         moved = ctypes.c_int()
-        _lib.check(self._L.sncal_hrnet_equalize(self._h, ctypes.byref(moved)), 'sncal_hrnet_equalize')
+        _lib.call('sncal_hrnet_equalize', self._h, ctypes.byref(moved))
         self.equalized = moved.value
         return self
 
@@ -202,20 +202,18 @@ class HRNetHeatmap:
         name, bn, cin, cout, k, stride, has_bias = self.conv_units()[idx]
         w = np.empty((cout, cin, k, k), dtype=np.float32)
         sc, sh = np.empty(cout, dtype=np.float32), np.empty(cout, dtype=np.float32)
-        _lib.check(self._L.sncal_hrnet_get_conv(self._h, idx, w.ctypes.data, sc.ctypes.data, sh.ctypes.data), 'sncal_hrnet_get_conv')
+        _lib.call('sncal_hrnet_get_conv', self._h, idx, w.ctypes.data, sc.ctypes.data, sh.ctypes.data)
         return w, sc, sh
 
     # ---- forward --------------------------------------------------------------------------------
     def output_size(self, H, W):
         h, w = ctypes.c_int(), ctypes.c_int()
-        _lib.check(self._L.sncal_hrnet_output_size(self._h, H, W, ctypes.byref(h), ctypes.byref(w)), 'output_size')
+        _lib.call('sncal_hrnet_output_size', self._h, H, W, ctypes.byref(h), ctypes.byref(w))
         return h.value, w.value
 
     def workspace_bytes(self, B, H, W):
         """Bytes of workspace a forward of (B,3,H,W) needs; lays the plan out for that shape (plan_ops / plan_tensor), no device work."""
-        n = ctypes.c_size_t()
-        _lib.check(self._L.sncal_hrnet_workspace(self._h, B, H, W, ctypes.byref(n)), 'sncal_hrnet_workspace')
-        return n.value
+        return _lib.workspace_bytes('sncal_hrnet_workspace', self._h, B, H, W)
 
     def _workspace(self, B, H, W):
         n = self.workspace_bytes(B, H, W)
@@ -244,14 +242,9 @@ class HRNetHeatmap:
         if decode_size is not None:
             ih, iw = int(decode_size[0]), int(decode_size[1])
             kpts = torch.empty((B, self.num_classes - 1, 3), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            ws = self._workspace(B, H, W)
-            fn = self._L.sncal_hrnet_forward_u8 if u8 else self._L.sncal_hrnet_forward
-            _lib.check(fn(self._h, x.data_ptr(), B, H, W,
-                          heat.data_ptr() if heat is not None else None,
-                          kpts.data_ptr() if kpts is not None else None, ih, iw,
-                          ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
-                       'sncal_hrnet_forward')
+        ws = self._workspace(B, H, W)
+        _lib.launch('sncal_hrnet_forward_u8' if u8 else 'sncal_hrnet_forward', x.device, self._h, x, B, H, W, heat, kpts, ih, iw, ws,
+                    ws.numel())
         return heat, kpts
 
     def range_status(self, clear: bool = True, check: bool = False):
@@ -260,10 +253,11 @@ class HRNetHeatmap:
         predict() is fp32 and has no such limit (metamodel.py:127-134): a non-zero count means the forwards since the last clear are NOT
         its result.  check=True raises SncalRangeError instead of returning the counts.  Always (0, 0) on the other engines."""
         ov, nf = ctypes.c_uint(), ctypes.c_uint()
-        with torch.cuda.device(self.device):
-            st = self._L.sncal_hrnet_range_status(self._h, ctypes.byref(ov), ctypes.byref(nf), int(bool(clear)), _lib.current_stream_ptr())
-        if st != 0 and (check or st != _lib.ERR_RANGE):
-            _lib.check(st, 'sncal_hrnet_range_status')
+        try:
+            _lib.launch('sncal_hrnet_range_status', self.device, self._h, ctypes.byref(ov), ctypes.byref(nf), int(bool(clear)))
+        except _lib.SncalRangeError:            # ERR_RANGE comes with the counts filled in: an error only for check=True
+            if check:
+                raise
         return ov.value, nf.value
 
     # ---- C5: fp8 arithmetic in the wide 3x3 convolutions (dtype='fp8') -------------------------------------------
@@ -271,31 +265,28 @@ class HRNetHeatmap:
         """One bf16 forward of x (B,3,H,W) fp32 that records the per-tensor activation ranges the fp8 convolutions scale by."""
         _lib.require_device(x, torch.float32, 'x')
         B, C, H, W = x.shape
-        n = ctypes.c_size_t()        # the calibration forward has a layout of its own (no e4m3 twins): a calibrated handle can be calibrated again
-        _lib.check(self._L.sncal_hrnet_calibrate_fp8_workspace(self._h, B, H, W, ctypes.byref(n)), 'sncal_hrnet_calibrate_fp8_workspace')
-        with torch.cuda.device(x.device):
-            ws = torch.empty(n.value, dtype=torch.uint8, device=self.device)
-            _lib.check(self._L.sncal_hrnet_calibrate_fp8(self._h, x.data_ptr(), B, H, W, ws.data_ptr(), ws.numel(),
-                                                         _lib.current_stream_ptr()), 'sncal_hrnet_calibrate_fp8')
+        # the calibration forward has a layout of its own (no e4m3 twins): a calibrated handle can be calibrated again
+        ws = _lib.workspace('sncal_hrnet_calibrate_fp8_workspace', self._h, B, H, W, device=self.device)
+        _lib.launch('sncal_hrnet_calibrate_fp8', x.device, self._h, x, B, H, W, ws, ws.numel())
         self._ws = None            # the fp8 layout adds the e4m3 twins: re-query the workspace
         return self
 
     def set_fp8_layers(self, spec: str = 'all'):
         """Which wide 3x3 convolutions run in fp8: 'all', 'none', or e.g. 'stage4', 'stage3,stage4', 'c384', 'stage4,c192,c384'."""
-        _lib.check(self._L.sncal_hrnet_set_fp8_layers(self._h, spec.encode()), 'sncal_hrnet_set_fp8_layers')
+        _lib.call('sncal_hrnet_set_fp8_layers', self._h, spec.encode())
         self._ws = None
         return self
 
     def set_profiling(self, enable):
         """Per-launch HIP event timing (measurement only): False/0 off, True/1 every launch, 2 only the launches of
         the kernel variant that led the profile recorded so far."""
-        _lib.check(self._L.sncal_hrnet_set_profiling(self._h, int(enable)), 'set_profiling')
+        _lib.call('sncal_hrnet_set_profiling', self._h, int(enable))
 
     def get_profile(self):
         """[{kernel, flops, bytes, ms, launches}] accumulated since set_profiling(True) (synchronises)."""
         n = ctypes.c_int()
         buf = (_lib.KernelStat * 256)()
-        _lib.check(self._L.sncal_hrnet_get_profile(self._h, buf, 256, ctypes.byref(n)), 'get_profile')
+        _lib.call('sncal_hrnet_get_profile', self._h, buf, 256, ctypes.byref(n))
         return [dict(kernel=buf[i].kernel.decode(), flops=buf[i].flops, bytes=buf[i].bytes, ms=buf[i].ms,
                      launches=buf[i].launches) for i in range(min(n.value, 256))]
 
@@ -308,8 +299,8 @@ class HRNetHeatmap:
         launch writes the dense form / the twin of `out`; `prep_in`: 0 none, 1 quantize_fp8, 2 split_f32 in front of it for `in`."""
         out = []
         po = _lib.PlanOp()
-        for i in range(self._L.sncal_hrnet_plan_num_ops(self._h)):
-            _lib.check(self._L.sncal_hrnet_plan_op(self._h, i, ctypes.byref(po)), 'plan_op')
+        for i in range(_lib.lib().sncal_hrnet_plan_num_ops(self._h)):
+            _lib.call('sncal_hrnet_plan_op', self._h, i, ctypes.byref(po))
             out.append(dict(idx=i, type=self.OP_TYPES[po.type], active=bool(po.active), conv=po.conv, name=po.name.decode(),
                             cin=po.cin, cout=po.cout, ksize=po.ksize, stride=po.stride, col_off=po.col_off,
                             **{'in': po.in_}, res=po.res, out=po.out, base=po.base, src=list(po.src)[:po.nsrc],
@@ -321,12 +312,12 @@ class HRNetHeatmap:
 
     def plan_tensor(self, tid):
         pt = _lib.PlanTensor()
-        _lib.check(self._L.sncal_hrnet_plan_tensor(self._h, tid, ctypes.byref(pt)), 'plan_tensor')
+        _lib.call('sncal_hrnet_plan_tensor', self._h, tid, ctypes.byref(pt))
         return dict(id=tid, C=pt.C, H=pt.H, W=pt.W, dtype=('fp32', 'bf16', 'e4m3')[pt.dtype], twin=pt.twin, alive=bool(pt.alive),
                     scale=pt.scale, bytes=pt.bytes, sub_batch=pt.sub_batch, offset=pt.offset, first=pt.first, last=pt.last)
 
     def clear_taps(self):
-        _lib.check(self._L.sncal_hrnet_plan_tap(self._h, -1, 0, None), 'plan_tap')
+        _lib.call('sncal_hrnet_plan_tap', self._h, -1, 0, None)
         self._taps = []
 
     def tap(self, op_idx, tid):
@@ -336,7 +327,7 @@ class HRNetHeatmap:
         tdt = {'fp32': torch.float32, 'bf16': torch.bfloat16, 'e4m3': torch.uint8}[info['dtype']]
         dst = torch.empty((info['sub_batch'], info['H'], info['W'], info['C']), dtype=tdt, device=self.device)
         assert dst.numel() * dst.element_size() == info['bytes'], info
-        _lib.check(self._L.sncal_hrnet_plan_tap(self._h, op_idx, tid, dst.data_ptr()), 'plan_tap')
+        _lib.call('sncal_hrnet_plan_tap', self._h, op_idx, tid, dst)
         self._taps = getattr(self, '_taps', []) + [dst]          # keep the buffers alive while the taps are registered
         return dst
 

@@ -20,7 +20,7 @@ from . import _lib
 def probe(data: bytes) -> dict:
     """Header fields of one JPEG (host only)."""
     info = _lib.JpegInfo()
-    _lib.check(_lib.lib().sncal_jpeg_probe(data, len(data), ctypes.byref(info)), 'sncal_jpeg_probe')
+    _lib.call('sncal_jpeg_probe', data, len(data), ctypes.byref(info))
     return dict(width=info.width, height=info.height, components=info.components, h_samp=info.h_samp,
                 v_samp=info.v_samp, restart_interval=info.restart_interval, blocks=list(info.blocks))
 
@@ -32,8 +32,7 @@ def entropy_decode(data: bytes):
     n = sum(info['blocks']) * 64
     buf = np.zeros(n, np.int16)
     ci = _lib.JpegInfo()
-    _lib.check(_lib.lib().sncal_jpeg_entropy_decode(data, len(data), buf.ctypes.data, n, ctypes.byref(ci)),
-               'sncal_jpeg_entropy_decode')
+    _lib.call('sncal_jpeg_entropy_decode', data, len(data), buf.ctypes.data, n, ctypes.byref(ci))
     hs, vs = info['h_samp'], info['v_samp']
     mx = -(-info['width'] // (8 * hs))
     my = -(-info['height'] // (8 * vs))
@@ -73,8 +72,7 @@ def scaled_layout(info: dict, reduce: int) -> dict:
                        v_samp=info['v_samp'], restart_interval=info.get('restart_interval', 0))
     out_hw, block = (ctypes.c_int32 * 2)(), (ctypes.c_int32 * 3)()
     hw, up = (ctypes.c_int32 * 6)(), (ctypes.c_int32 * 6)()
-    _lib.check(_lib.lib().sncal_jpeg_scaled_layout(ctypes.byref(ci), check_reduce(reduce), out_hw, block, hw, up),
-               'sncal_jpeg_scaled_layout')
+    _lib.call('sncal_jpeg_scaled_layout', ctypes.byref(ci), check_reduce(reduce), out_hw, block, hw, up)
     n = info['components']
     return dict(out_hw=(out_hw[0], out_hw[1]), comp_block=list(block[:n]), comp_hw=[(hw[2 * c], hw[2 * c + 1]) for c in range(n)],
                 comp_up=[(up[2 * c], up[2 * c + 1]) for c in range(n)])
@@ -94,12 +92,11 @@ class JpegDecoder:
         self.reduce = check_reduce(reduce)
         self._h = None
         h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().sncal_jpeg_create_scaled(self.max_batch, self.height, self.width, self.reduce, int(threads),
-                                                           ctypes.byref(h)), 'sncal_jpeg_create_scaled')
+        _lib.call('sncal_jpeg_create_scaled', self.max_batch, self.height, self.width, self.reduce, int(threads), ctypes.byref(h),
+                  device=self.device)
         self._h = h
         oh, ow = ctypes.c_int(), ctypes.c_int()
-        _lib.check(_lib.lib().sncal_jpeg_output_size(self._h, ctypes.byref(oh), ctypes.byref(ow)), 'sncal_jpeg_output_size')
+        _lib.call('sncal_jpeg_output_size', self._h, ctypes.byref(oh), ctypes.byref(ow))
         self.out_height, self.out_width = oh.value, ow.value
 
     def decode(self, frames: Sequence[bytes], out: torch.Tensor = None) -> torch.Tensor:
@@ -111,9 +108,7 @@ class JpegDecoder:
             raise _lib.SncalError(f'out must be ({B},{self.out_height},{self.out_width},3)')
         ptrs = (ctypes.c_char_p * max(B, 1))(*[bytes(f) for f in frames])
         lens = (ctypes.c_size_t * max(B, 1))(*[len(f) for f in frames])
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().sncal_jpeg_decode(self._h, ptrs, lens, B, out.data_ptr(), _lib.current_stream_ptr()),
-                       'sncal_jpeg_decode')
+        _lib.launch('sncal_jpeg_decode', self.device, self._h, ptrs, lens, B, out)
         return out
 
     def decode_files(self, paths: Sequence[str], out: torch.Tensor = None) -> torch.Tensor:

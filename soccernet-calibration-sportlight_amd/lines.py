@@ -109,7 +109,5 @@ def lines_to_points_device(peaks, scale: float = 4.0, prob_thre: float = 0.2):
     if tuple(peaks.shape[1:]) != (23, 2, 3):
         raise _lib.SncalError('peaks must be (B,23,2,3)')
     out = torch.empty((peaks.shape[0], 30, 3), dtype=torch.float32, device=peaks.device)
-    with torch.cuda.device(peaks.device):
-        _lib.check(_lib.lib().sncal_lines_to_points(peaks.data_ptr(), peaks.shape[0], float(scale), float(prob_thre),
-                                                    out.data_ptr(), _lib.current_stream_ptr()), 'sncal_lines_to_points')
+    _lib.launch('sncal_lines_to_points', peaks.device, peaks, peaks.shape[0], float(scale), float(prob_thre), out)
     return out

@@ -34,9 +34,7 @@ def create_target(keypoints: torch.Tensor, sigma: float, pred_size: Tuple[int, i
     B, N = kp.shape[0], kp.shape[1]
     h, w = int(pred_size[0]), int(pred_size[1])
     out = torch.empty((B, N + 1, h, w), dtype=torch.float32, device=kp.device)
-    with torch.cuda.device(kp.device):
-        _lib.check(_lib.lib().sncal_create_target(kp.data_ptr(), B, N, float(sigma), h, w, out.data_ptr(),
-                                                  _lib.current_stream_ptr()), 'sncal_create_target')
+    _lib.launch('sncal_create_target', kp.device, kp, B, N, float(sigma), h, w, out)
     return out
 
 
@@ -50,17 +48,6 @@ def create_heatmaps(keypoints: torch.Tensor, sigma: float, pred_size: Tuple[int,
 
 
 TERM_MSE, TERM_KL, TERM_AWING = 1, 2, 4
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
-def _workspace(name, shape, device) -> torch.Tensor:
-    """The scratch buffer that the library's query function `name` asks for at `shape`, on `device`."""
-    n = ctypes.c_size_t()
-    _lib.check(getattr(_lib.lib(), name)(*shape, ctypes.byref(n)), name)
-    return torch.empty(max(n.value, 16), dtype=torch.uint8, device=device)
 
 
 def _coef(coef, n):
@@ -98,11 +85,9 @@ def heatmap_loss_sums(logp: torch.Tensor, keypoints: torch.Tensor, mask, sigma: 
     Asynchronous on the current stream."""
     logp, kp, mask, (B, C, h, w) = _heatmap_inputs(logp, keypoints, mask)
     out = torch.zeros((B, 3), dtype=torch.float64, device=logp.device)
-    with torch.cuda.device(logp.device):
-        ws = _workspace('sncal_heatmap_loss_workspace', (B, C - 1, h, w), logp.device)
-        _lib.check(_lib.lib().sncal_heatmap_loss(logp.data_ptr(), kp.data_ptr(), _ptr(mask), B, C - 1, h, w, float(sigma), float(stride),
-                                                 int(terms), out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
-                   'sncal_heatmap_loss')
+    ws = _lib.workspace('sncal_heatmap_loss_workspace', B, C - 1, h, w, device=logp.device)
+    _lib.launch('sncal_heatmap_loss', logp.device, logp, kp, mask, B, C - 1, h, w, float(sigma), float(stride), int(terms), out, ws,
+                ws.numel())
     return out
 
 
@@ -114,12 +99,10 @@ def heatmap_loss_grad(logp: torch.Tensor, keypoints: torch.Tensor, mask, sigma: 
     logp, kp, mask, (B, C, h, w) = _heatmap_inputs(logp, keypoints, mask)
     cf = _coef(coef, 3)
     gout = _grad_output(grad_output, logp.device)
-    with torch.cuda.device(logp.device):
-        grad = torch.empty_like(logp)
-        ws = _workspace('sncal_heatmap_loss_workspace', (B, C - 1, h, w), logp.device)
-        _lib.check(_lib.lib().sncal_heatmap_loss_grad(logp.data_ptr(), kp.data_ptr(), _ptr(mask), B, C - 1, h, w, float(sigma),
-                                                      float(stride), int(terms), cf, _ptr(gout), grad.data_ptr(), ws.data_ptr(),
-                                                      ws.numel(), _lib.current_stream_ptr()), 'sncal_heatmap_loss_grad')
+    grad = torch.empty_like(logp)
+    ws = _lib.workspace('sncal_heatmap_loss_workspace', B, C - 1, h, w, device=logp.device)
+    _lib.launch('sncal_heatmap_loss_grad', logp.device, logp, kp, mask, B, C - 1, h, w, float(sigma), float(stride), int(terms), cf,
+                gout, grad, ws, ws.numel())
     return grad
 
 
@@ -239,9 +222,7 @@ def create_keypoint_maps(keypoints: torch.Tensor, sigma: float = 1.0, stride: fl
     B, C = kp.shape[0], kp.shape[1]
     h, w = int(size[0]), int(size[1])
     out = torch.empty((B, C, h, w), dtype=torch.float32, device=kp.device)
-    with torch.cuda.device(kp.device):
-        _lib.check(_lib.lib().sncal_line_target(kp.data_ptr(), B, C, float(sigma), float(stride), h, w, out.data_ptr(),
-                                                _lib.current_stream_ptr()), 'sncal_line_target')
+    _lib.launch('sncal_line_target', kp.device, kp, B, C, float(sigma), float(stride), h, w, out)
     return out
 
 
@@ -274,11 +255,9 @@ def line_loss_sums(pred: torch.Tensor, target=None, keypoints=None, target_sigma
     adaptive-wing terms (0 where the term's bit is clear).  Asynchronous on the current stream."""
     pred, target, keypoints, (B, C, h, w) = _line_inputs(pred, target, keypoints)
     out = torch.zeros((B, 2), dtype=torch.float64, device=pred.device)
-    with torch.cuda.device(pred.device):
-        ws = _workspace('sncal_line_loss_workspace', (B, C, h, w), pred.device)
-        _lib.check(_lib.lib().sncal_line_loss(pred.data_ptr(), _ptr(target), _ptr(keypoints), B, C, h, w, float(target_sigma),
-                                              float(stride), float(gmse_sigma), int(terms), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                              _lib.current_stream_ptr()), 'sncal_line_loss')
+    ws = _lib.workspace('sncal_line_loss_workspace', B, C, h, w, device=pred.device)
+    _lib.launch('sncal_line_loss', pred.device, pred, target, keypoints, B, C, h, w, float(target_sigma), float(stride),
+                float(gmse_sigma), int(terms), out, ws, ws.numel())
     return out
 
 
@@ -290,12 +269,10 @@ def line_loss_grad(pred: torch.Tensor, target=None, keypoints=None, target_sigma
     pred, target, keypoints, (B, C, h, w) = _line_inputs(pred, target, keypoints)
     cf = _coef(coef, 2)
     gout = _grad_output(grad_output, pred.device)
-    with torch.cuda.device(pred.device):
-        grad = torch.empty_like(pred)
-        ws = _workspace('sncal_line_loss_workspace', (B, C, h, w), pred.device)
-        _lib.check(_lib.lib().sncal_ehm_loss_grad(pred.data_ptr(), _ptr(target), _ptr(keypoints), B, C, h, w, float(target_sigma),
-                                                   float(stride), float(gmse_sigma), int(terms), cf, _ptr(gout), grad.data_ptr(),
-                                                   ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()), 'sncal_ehm_loss_grad')
+    grad = torch.empty_like(pred)
+    ws = _lib.workspace('sncal_line_loss_workspace', B, C, h, w, device=pred.device)
+    _lib.launch('sncal_ehm_loss_grad', pred.device, pred, target, keypoints, B, C, h, w, float(target_sigma), float(stride),
+                float(gmse_sigma), int(terms), cf, gout, grad, ws, ws.numel())
     return grad
 
 

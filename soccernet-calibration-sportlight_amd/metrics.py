@@ -265,9 +265,7 @@ def line_acc_counts(gt: torch.Tensor, pred: torch.Tensor, p_threshold: float, ts
         raise _lib.SncalError(f'prediction {tuple(pred.shape)} and keypoints {tuple(gt.shape)} must both be (B,C,2,3)')
     out = torch.zeros((len(ts), 3), dtype=torch.int64, device=pred.device)
     c_ts = (ctypes.c_float * len(ts))(*[float(t) for t in ts])
-    with torch.cuda.device(pred.device):
-        _lib.check(_lib.lib().sncal_line_acc_counts(gt.data_ptr(), pred.data_ptr(), pred.shape[0], pred.shape[1], float(p_threshold),
-                                                    c_ts, len(ts), out.data_ptr(), _lib.current_stream_ptr()), 'sncal_line_acc_counts')
+    _lib.launch('sncal_line_acc_counts', pred.device, gt, pred, pred.shape[0], pred.shape[1], float(p_threshold), c_ts, len(ts), out)
     return out
 
 

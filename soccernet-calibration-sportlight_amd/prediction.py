@@ -173,14 +173,8 @@ class CameraCreator:
         if out is None:
             out = torch.empty((B, ctypes.sizeof(_lib.Camera)), dtype=torch.uint8, device=d_kpts.device)
         cfg = self._cfg()
-        n = ctypes.c_size_t()
-        _lib.check(_lib.lib().sncal_calibrate_workspace(B, ctypes.byref(cfg), ctypes.byref(n)), 'sncal_calibrate_workspace')
-        with torch.cuda.device(d_kpts.device):
-            ws = torch.empty(n.value, dtype=torch.uint8, device=d_kpts.device)
-            _lib.check(_lib.lib().sncal_calibrate_ws(d_kpts.data_ptr(), d_line_pts.data_ptr() if d_line_pts is not None else None,
-                                                     B, ctypes.byref(cfg), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                     _lib.current_stream_ptr()),
-                       'sncal_calibrate_ws')
+        ws = _lib.workspace('sncal_calibrate_workspace', B, ctypes.byref(cfg), device=d_kpts.device)
+        _lib.launch('sncal_calibrate_ws', d_kpts.device, d_kpts, d_line_pts, B, ctypes.byref(cfg), out, ws, ws.numel())
         return out
 
     def sweep_slots(self) -> int:
@@ -206,17 +200,12 @@ class CameraCreator:
         S = self.sweep_slots()
         grid = sweep_grid(max_rmse, max_rmse_rel)
         cfg = self._cfg()
-        n = ctypes.c_size_t()
-        _lib.check(_lib.lib().sncal_calibrate_sweep_workspace(B, ctypes.byref(cfg), len(grid), ctypes.byref(n)), 'sncal_calibrate_sweep_workspace')
-        with torch.cuda.device(d_kpts.device):
-            d_grid = torch.from_numpy(grid).to(d_kpts.device)
-            outcomes = torch.empty((B, S, ctypes.sizeof(_lib.Camera)), dtype=torch.uint8, device=d_kpts.device)
-            choice = torch.empty((len(grid), B), dtype=torch.int32, device=d_kpts.device)
-            ws = torch.empty(n.value, dtype=torch.uint8, device=d_kpts.device)
-            _lib.check(_lib.lib().sncal_calibrate_sweep(d_kpts.data_ptr(), d_line_pts.data_ptr() if d_line_pts is not None else None,
-                                                        B, ctypes.byref(cfg), d_grid.data_ptr(), len(grid), outcomes.data_ptr(),
-                                                        choice.data_ptr(), ws.data_ptr(), ws.numel(), _lib.current_stream_ptr()),
-                       'sncal_calibrate_sweep')
+        ws = _lib.workspace('sncal_calibrate_sweep_workspace', B, ctypes.byref(cfg), len(grid), device=d_kpts.device)
+        d_grid = torch.from_numpy(grid).to(d_kpts.device)
+        outcomes = torch.empty((B, S, ctypes.sizeof(_lib.Camera)), dtype=torch.uint8, device=d_kpts.device)
+        choice = torch.empty((len(grid), B), dtype=torch.int32, device=d_kpts.device)
+        _lib.launch('sncal_calibrate_sweep', d_kpts.device, d_kpts, d_line_pts, B, ctypes.byref(cfg), d_grid, len(grid), outcomes, choice,
+                    ws, ws.numel())
         return outcomes, choice
 
     @staticmethod

@@ -49,8 +49,8 @@ def tables(n_src: int, n_dst: int, zero_edges: bool):
     n_dst = int(n_dst)
     ofs = np.zeros(max(n_dst, 0), np.int32)
     coef = np.zeros((max(n_dst, 0), 2), np.int16)
-    _lib.check(_lib.lib().sncal_resize_tables(int(n_src), n_dst, int(bool(zero_edges)), ofs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                              coef.ctypes.data_as(ctypes.POINTER(ctypes.c_int16))), 'sncal_resize_tables')
+    _lib.call('sncal_resize_tables', int(n_src), n_dst, int(bool(zero_edges)), ofs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+              coef.ctypes.data_as(ctypes.POINTER(ctypes.c_int16)))
     return ofs, coef
 
 
@@ -68,7 +68,5 @@ def resize_u8(frames: torch.Tensor, size, out: torch.Tensor = None) -> torch.Ten
     _lib.require_device(out, torch.uint8, 'out')
     if tuple(out.shape) != (B, H, W, 3) or out.device != frames.device:
         raise _lib.SncalError(f'out must be ({B},{H},{W},3) on {frames.device}')
-    with torch.cuda.device(frames.device):
-        _lib.check(_lib.lib().sncal_resize_u8(frames.data_ptr() if B else None, B, h, w, out.data_ptr() if B else None, H, W,
-                                              _lib.current_stream_ptr()), 'sncal_resize_u8')
+    _lib.launch('sncal_resize_u8', frames.device, frames, B, h, w, out, H, W)         # an empty batch's tensors go as NULL
     return out

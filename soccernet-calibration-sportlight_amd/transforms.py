@@ -19,10 +19,7 @@ class HRNetPredictionTransform:
         _lib.require_device(preds, torch.float32, 'preds')
         B, C, h, w = preds.shape
         out = torch.empty((B, C - 1, 3), dtype=torch.float32, device=preds.device)
-        with torch.cuda.device(preds.device):
-            _lib.check(_lib.lib().sncal_heatmap_decode(preds.data_ptr(), B, C, h, w, int(self.H), int(self.W),
-                                                       out.data_ptr(), _lib.current_stream_ptr()),
-                       'sncal_heatmap_decode')
+        _lib.launch('sncal_heatmap_decode', preds.device, preds, B, C, h, w, int(self.H), int(self.W), out)
         return out
 
 
@@ -45,8 +42,5 @@ class EHMPredictionTransform:
         _lib.require_device(t, torch.float32, 'preds')
         B, C, H, W = t.shape
         out = torch.empty((B, C, 2, 3), dtype=torch.float32, device=t.device)
-        with torch.cuda.device(t.device):
-            _lib.check(_lib.lib().sncal_line_decode(t.data_ptr(), B, C, H, W, float(sigma), float(scale),
-                                                    out.data_ptr(), _lib.current_stream_ptr()),
-                       'sncal_line_decode')
+        _lib.launch('sncal_line_decode', t.device, t, B, C, H, W, float(sigma), float(scale), out)
         return out
